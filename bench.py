@@ -19,8 +19,10 @@ scaling.  Prints ONE JSON line on rank 0.
   fluid         configs[4]  water refit + trace, 1920x1080, 2 spp
   million                   8 x 125,000-triangle spheres: the workload of the reference's published fps
                             (Test game screenshots/readme.txt), with --preset fast|performance|balanced|quality|ultra
-Every default run also measures configs[3] over the same N ranks for a few frames and reports it in the extra field
-"configs3" of the line, so a scaling run over N = 1, 2, 4, 8 yields BASELINE's curve without changing the headline.
+A plain run sets up, warms up, times exactly --steps frames and prints the line.  With --full a default run also measures
+configs[3] over the same N ranks for a few frames and reports it in the extra field "configs3" of the line, so a scaling run
+over N = 1, 2, 4, 8 yields BASELINE's curve without changing the headline; --full also adds the CPU baseline, the fluid
+scene's other vertex sources and frames alone on the chip.  --dump-outputs DIR writes what the last timed frame computed.
 """
 import argparse
 import json
@@ -34,6 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "ptrt-game-engine_amd"))
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
 ALGO_BYTES_PER_PIXEL = 143.0   # RNG 48R+48W, accum 12W, normal 12W, depth 4W, id 4W, tonemap 12R+3W
 SIMDS, CLOCK_HZ, VALU_CYCLES = 256 * 4, 2.4e9, 2.0  # MI355X_MICROARCH.md: 256 CUs x 4 SIMD-32, a wave64 VALU op issues over 2 cycles
+DUMP_LIMIT_BYTES = 64 * 10**6 - 2**16  # --dump-outputs: at most 64 MB in all (room left for the .npy headers)
+DUMP_SEED = 1080                       # the fixed pixel sample of an output beyond that
 
 CONFIGS = {
     "cornell1080": dict(scene="cornell", width=1920, height=1080, spp=4, depth=4),
@@ -127,6 +131,26 @@ def cpu_baseline(P, scene_name, W, H, spp, depth, frame, threads):
     if all_core:
         out["all_core"] = all_core
     return out
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  The arrays hold the same pixels, channels last; when
+    together they exceed `limit` bytes, each keeps the same fixed, seeded sample of the pixels, in pixel order, as (samples,
+    channels), and pixel_index.npy (float64) holds the row-major indices of those pixels."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    npix = {a.size // a.shape[-1] for a in arrays.values()}
+    assert len(npix) == 1, "outputs of different sizes"
+    n = npix.pop()
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        per_pixel = sum(a.nbytes // n for a in arrays.values()) + 8  # (+ the float64 index)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, limit // per_pixel, replace=False))
+        arrays = {k: a.reshape(n, -1)[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
 
 
 class Farm:
@@ -235,7 +259,7 @@ class Farm:
                 move = s.rebuildFromDevice if self.rebuild else s.refitFromDevice
                 move(s.water_mesh, self.water[i].data_ptr())
             self.counter[0] += 1
-        b = self.counter[1] & 1
+        b = self.last_b = self.counter[1] & 1
         self.counter[1] += 1
         self._retire(b)
         if self.pending[b ^ 1] is not None and s.get_option("pipelined"):
@@ -281,6 +305,18 @@ class Farm:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
+    def snapshot(self):
+        """What the last frame handed to its caller, as host arrays (after fence()): the RGB8 image -- this rank's band for N = 1,
+        the assembled frame on rank 0 for N > 1 -- and, for N = 1, the HDR radiance the image was tonemapped from."""
+        b = self.last_b
+        if self.env["world"] == 1:
+            rgb8 = self.tiles[b][:self.rows]
+            accum = self.scene.read(self.P.BUF_ACCUM).reshape(self.rows, self.W, 3)
+            return {"rgb8": rgb8.cpu().numpy(), "accum": accum}
+        if self.env["rank"] != 0:
+            return None
+        return {"rgb8": (self.out_frame if self.post_on_rank0 else self.frames[b]).cpu().numpy()}
+
     def _max_over_ranks(self, x):
         if self.env["world"] == 1:
             return x
@@ -309,9 +345,10 @@ class Farm:
         self.ramp_ms = [round(h * 1e3, 4) for h in hist]
         return n
 
-    def measure(self, steps, warmup, ramp=True, time_launches=True):
+    def measure(self, steps, warmup, ramp=True, time_launches=True, alone=True, snapshot=False):
         """W untimed frames (+ the frames on which a scene settles its loop shape, + the clock-ramp guard's), then exactly
-        `steps` frames between barrier + synchronize brackets; the MAX over ranks."""
+        `steps` frames between barrier + synchronize brackets; the MAX over ranks.  `alone`: a few more frames afterwards, each
+        one launch alone on the chip (kernel_alone_ms); `snapshot`: self.outputs = what the last timed frame computed."""
         torch, env = self.torch, self.env
         for _ in range(warmup):
             self.step()
@@ -331,12 +368,22 @@ class Farm:
             for _ in range(2):
                 self.step()
         self.fence()
+        # the timed frames start from the same state in every run, whatever number of frames the ramp took, so that the last
+        # step's inputs (and --dump-outputs) repeat: generator states, frame index and water surface as after the upload, then
+        # two untimed frames (the first after the reset waits for the stream; from the second on frames overlap again)
+        self.scene.reset_rng()
+        self.scene.setFrameCount(0)
+        self.counter[0] = 0
+        for _ in range(2):
+            self.step()
+        self.fence()
         self.scene.stats()  # reset counters
         t0 = time.perf_counter()
         for _ in range(steps):
             self.step()
         self.fence()
         dt = time.perf_counter() - t0
+        self.outputs = self.snapshot() if snapshot else None
         st = self.scene.stats()
         rays = float(st["extension_rays"] + st["shadow_rays_walked"])  # rays actually traced
         rays_ref = float(st["extension_rays"] + st["shadow_rays"])     # rays the reference path traces
@@ -355,7 +402,7 @@ class Farm:
                           tail_ms=float(tl.mean()))
             kernel_ms = launch["ms"]
         kernel_alone_ms = None
-        if overlapped:
+        if overlapped and (alone or launch is None):
             # The timed frames overlapped on the device (ptrt_set_option "pipeline": a frame's launches follow the previous
             # frame's and do not wait for it to drain), so the events around a frame measured the frame INTERVAL.  For
             # reference, beside the timed launches' own durations: a few more frames, untimed, each ONE launch ordered behind
@@ -483,8 +530,16 @@ def main():
     ap.add_argument("--depth", type=int, default=None)
     ap.add_argument("--preset", default=None, choices=["fast", "performance", "balanced", "quality", "ultra"],
                     help="Scene::setPerformancePreset on the measured scene (N=1 only; not the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs3", action="store_true", help="skip the extra configs[3] measurement of a default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, configs[3] beside the headline, the "
+                         "fluid scene's other vertex sources, and frames alone on the chip (roofline.kernel_alone_ms)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; at most 64 MB, a "
+                         "fixed sample of the pixels beyond that): rgb8, the frame its caller receives, and for N=1 accum, its "
+                         "HDR radiance.  The timed steps start from fixed generator states, so equal arguments give equal inputs "
+                         "(the denoiser's temporal history, --denoise or a preset that enables it, still carries earlier frames)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-configs3", action="store_true", help="--full: skip the extra configs[3] measurement of a default run")
     ap.add_argument("--denoise", action="store_true",
                     help="also run motion vectors + the spatiotemporal denoiser each frame (N=1 only; not the headline)")
     ap.add_argument("--bloom", action="store_true", help="also run the bloom chain (N=1 only; not the headline)")
@@ -513,6 +568,8 @@ def main():
     ap.add_argument("--rebuild", action="store_true",
                     help="fluid scene: rebuild the water BVH on the GPU every frame (ptrt_build_bvh) instead of refitting it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.via_commit:
         args.fluid_source = "commit"
     cfg = dict(CONFIGS[args.config])
@@ -567,10 +624,12 @@ def main():
 
     W, H = cfg["width"], cfg["height"]
     farm = Farm(P, torch, dist, tilefarm, env, cfg["scene"], W, H, cfg["spp"], cfg["depth"], args=args, preset=args.preset)
-    m = farm.measure(args.steps, args.warmup, ramp=not args.no_ramp, time_launches=not args.no_time_launches)
+    m = farm.measure(args.steps, args.warmup, ramp=not args.no_ramp, time_launches=not args.no_time_launches, alone=args.full,
+                     snapshot=args.dump_outputs is not None)
+    outputs = farm.outputs
     settings = farm.scene.settings()
     fluid_sources = None
-    if cfg["scene"] == "fluid" and world == 1 and not args.rebuild:
+    if args.full and cfg["scene"] == "fluid" and world == 1 and not args.rebuild:
         # configs[4] three ways (the line's value is --fluid-source, default "device"): ms per frame of the same pipeline with
         # the positions already in HBM, crossing PCIe from pinned memory, and through the reference's caller + commit
         fluid_sources = {args.fluid_source + "_ms": round(m["dt"] / args.steps * 1e3, 4)}
@@ -639,7 +698,7 @@ def main():
 
     # configs[3] (showcase 3840x2160, 8 spp) over the same ranks, a few frames: the curve BASELINE asks for
     c3 = None
-    if headline and not args.no_configs3:
+    if args.full and headline and not args.no_configs3:
         c = CONFIGS["showcase4k8"]
         n3 = max(2, min(args.steps, 6))
         f3 = Farm(P, torch, dist, tilefarm, env, c["scene"], c["width"], c["height"], c["spp"], c["depth"])
@@ -696,9 +755,11 @@ def main():
     if present is not None:
         out["config"]["present_ms_per_frame"] = round(present, 4)
         out["config"]["present_slots"] = args.present
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(P, cfg["scene"], W, H, spp_used, depth_used, 0,
                                            min(16, len(os.sched_getaffinity(0))))
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -6,56 +6,38 @@ oracle/_ref/transfer_probe is the reference's own src/common/PTRTtransfer.cuh co
     updatePTScene(scene, unified)   ->  ... mesh->bvhDirty = mesh->vertsDirty = true ... scene.commitObjectChanges()
     updatePTCamera(scene, unified)
 then renders again -- under each dynamic-geometry policy (Scene::setDynamicGeometryPolicy: the one line an application
-adds).  Checked here: under GpuRefit / GpuRebuild the commits reach ptrt_update_vertices + ptrt_refit / ptrt_build_bvh (the
-geometry is uploaded ONCE), and under every policy each frame -- RGB8 and the HDR image -- equals the oracle's rendering of
-the scene the probe reports, which in turn equals, byte for byte, the scene the Python recipe builds the same way."""
+adds).  What it reported is held in tests/golden/transfer_probe_gpu.json (tests/golden/make_transfer_probe_golden.py); where
+the probe is built, it is run as well and must still report exactly that.  Checked here: under GpuRefit / GpuRebuild the
+commits reach ptrt_update_vertices + ptrt_refit / ptrt_build_bvh (the geometry is uploaded ONCE), and under every policy each
+frame -- RGB8 and the HDR image -- equals the oracle's rendering of the scene the probe reports, which in turn equals, byte
+for byte, the scene the Python recipe builds the same way."""
+import json
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
 from common import bits
+from make_transfer_probe_golden import EXE, digest, summarize  # (tests/golden is on the path: conftest.py)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "oracle", "_ref", "transfer_probe")
-
-
-def read_probe(path):
-    raw = open(path, "rb").read()
-    magic, w, h, frames, spp, depth = struct.unpack_from("<6I", raw, 0)
-    assert magic == 0x54525046
-    off, out = 24, []
-
-    def blob():
-        nonlocal off
-        (n,) = struct.unpack_from("<Q", raw, off)
-        off += 8
-        b = raw[off:off + n]
-        off += n
-        return b
-
-    for _ in range(frames):
-        gpu_commits, uploads = struct.unpack_from("<2Q", raw, off)
-        off += 16
-        scene, rgb, accum = blob(), blob(), blob()
-        out.append(dict(gpu_commits=gpu_commits, uploads=uploads, scene=scene,
-                        rgb8=np.frombuffer(rgb, np.uint8).reshape(-1, 3), accum=np.frombuffer(accum, np.float32).reshape(-1, 3)))
-    assert off == len(raw)
-    return w, h, spp, depth, out
+GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "transfer_probe_gpu.json")))
 
 
 @pytest.mark.parametrize("policy", ["HostRebuild", "GpuRefit", "GpuRebuild"])
 def test_update_pt_scene_then_commit_reaches_the_gpu_path(P, O, blue_noise, tmp_path, policy):
-    if not os.path.exists(EXE):
-        pytest.skip("oracle/_ref/transfer_probe not built (needs /root/reference: make -C tools/refapp)")
-    pid = P.Scene.POLICIES[policy]
-    dump = str(tmp_path / f"transfer_{pid}.bin")
-    r = subprocess.run([EXE, "gpu", str(pid), dump], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    w, h, spp, depth, frames = read_probe(dump)
+    w, h, spp, depth = GOLD["width"], GOLD["height"], GOLD["spp"], GOLD["depth"]
+    frames = GOLD["policies"][policy]
+    if os.path.exists(EXE):  # built from the reference's sources (tools/refapp): the probe itself still reports the golden
+        dump = str(tmp_path / f"transfer_{P.Scene.POLICIES[policy]}.bin")
+        # the probe links libptrt_amd.so by name and its run path is the directory it was built in: point the loader at this tree's
+        pkg = os.path.dirname(os.path.abspath(P.__file__))
+        env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (pkg, os.environ.get("LD_LIBRARY_PATH")) if p))
+        r = subprocess.run([EXE, "gpu", str(P.Scene.POLICIES[policy]), dump], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert summarize(dump) == dict(width=w, height=h, spp=spp, depth=depth, frames=frames)
     assert (w, h) == P.scenes.TRANSFER_SIZE and len(frames) == 3
 
     # the reference's caller reached the refit: two commits on the GPU path, the geometry uploaded once
@@ -82,14 +64,16 @@ def test_update_pt_scene_then_commit_reaches_the_gpu_path(P, O, blue_noise, tmp_
         assert fc == 0
         rgb = s.render_to_host()
         accum = s.read(P.BUF_ACCUM)
-        assert s.serialize() == f["scene"], f"step {k}: the probe's scene and the recipe's differ"
-        assert np.array_equal(rgb.reshape(-1, 3), f["rgb8"]) and np.array_equal(bits(accum), bits(f["accum"])), f"step {k}"
+        scene = s.serialize()
+        assert len(scene) == f["scene_bytes"] and digest(scene) == f["scene_sha256"], f"step {k}: the probe's scene and the recipe's differ"
+        assert digest(rgb.reshape(-1, 3).tobytes()) == f["rgb8_sha256"] and digest(bits(accum).tobytes()) == f["accum_sha256"], f"step {k}"
         c = O.render(s.flatten(), w, h, spp, depth, fc, blue_noise, rng, threads=8)
-        assert np.array_equal(bits(c["accum"]), bits(f["accum"])), f"step {k}: the probe's frame differs from the oracle's"
-        assert np.array_equal(O.tonemap(c["accum"], w, h, threads=4).reshape(-1, 3), f["rgb8"])
+        assert np.array_equal(bits(c["accum"]), bits(accum))
+        assert digest(bits(c["accum"]).tobytes()) == f["accum_sha256"], f"step {k}: the probe's frame differs from the oracle's"
+        assert digest(np.ascontiguousarray(O.tonemap(c["accum"], w, h, threads=4).reshape(-1, 3)).tobytes()) == f["rgb8_sha256"]
         assert np.array_equal(s.read(P.BUF_RNG), rng)
     assert s.commitCounts() == ((0, 3) if policy == "HostRebuild" else (2, 1))
-    assert frames[2]["accum"].any() and not np.array_equal(frames[1]["accum"], frames[2]["accum"])
+    assert accum.any() and frames[1]["accum_sha256"] != frames[2]["accum_sha256"]
     s.close()
 
 
