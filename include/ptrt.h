@@ -421,6 +421,20 @@ int ptrt_write_rng(ptrt_ctx *ctx, const uint32_t *states, size_t bytes);
 int ptrt_trace_rays(ptrt_ctx *ctx, const float *origins, const float *directions, int n,
                     ptrt_hit *out_hits);
 
+/* The body of Scene::render_to_device_wireframe (scene.cuh:1211-1245): render_kernel_wireframe
+ * (scene_kernels.cuh:53-117, wireframeMode true) over the full width x height -- the render size of the path tracer,
+ * bloom and the denoiser play no part.  Per pixel: the RNG-free Camera::get_ray(s, t) (camera.cuh:173-199, device branch:
+ * a thin lens takes its offset from random_in_unit_disk_hash), one closest hit; a hit with u, v or 1 - u - v below
+ * `thickness` is an edge, coloured by its mesh's emission if emission.x > 0 and white otherwise; every other pixel shows
+ * sampleSky (render_utils.cuh:115-137); then c / (c + 1), powf(c, 1 / 2.2), * 255.99 into RGB8, bottom-up.
+ * `out_rgb8` / `out_is_device` as for ptrt_render (PTRT_OUT_HOST synchronous, PTRT_OUT_DEVICE the context's rows,
+ * PTRT_OUT_DEVICE_FRAME the whole frame); a target is required.  Enqueued on the context's stream, behind any earlier
+ * ptrt_render of the context (pipelined ones included).  Touches no generator state, accumulation, G-buffer or
+ * PTRT_BUF_RGB8 image, no counter of ptrt_get_stats and no timing history: path frames before and after it are the
+ * frames they would be without it.  PTRT_E_INVALID for an interleaved context (the tile farm has no wireframe view),
+ * PTRT_E_NOT_READY before geometry and materials are uploaded.  (ABI 6, addition only.) */
+int ptrt_render_wireframe(ptrt_ctx *ctx, float thickness, void *out_rgb8, int out_is_device);
+
 /* counters accumulated by ptrt_render since the last call (reset on read);
  * only maintained when ptrt_set_option(ctx,"count_rays",1). */
 int ptrt_get_stats(ptrt_ctx *ctx, ptrt_stats *out);

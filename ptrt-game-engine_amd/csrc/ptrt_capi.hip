@@ -14,6 +14,7 @@
 #include "pt_render.hip.h"
 #include "pt_wavefront.hip.h"
 #include "pt_async.hip.h"
+#include "pt_wireframe.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,7 @@ struct ptrt_ctx {
     float *alt_accum = nullptr, *alt_normal = nullptr, *alt_depth = nullptr;
     int *alt_object_id = nullptr;
     unsigned char *d_rgb8 = nullptr;
+    unsigned char *wire_rgb8 = nullptr; // ptrt_render_wireframe to host memory: its own image (PTRT_BUF_RGB8 stays the path tracer's)
     unsigned char *last_rgb8 = nullptr; // where the last frame's RGB8 went
     void *last_frame_target = nullptr;  // ... or the caller's frame it was written into (PTRT_OUT_DEVICE_FRAME)
     int time_kernels = 1;               // option: record the two events per launch that ptrt_kernel_ms_history reads
@@ -1330,6 +1332,7 @@ void ptrt_destroy(ptrt_ctx *c) {
     dfree(c->alt_depth);
     dfree(c->alt_object_id);
     dfree(c->d_rgb8);
+    dfree(c->wire_rgb8);
     dfree(c->d_counters);
     dfree(c->d_queue);
     for (int k = 0; k < ptrt_ctx::STAGES; ++k) {
@@ -3102,6 +3105,55 @@ int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, 
     (void)hipFree(d_d);
     (void)hipFree(d_h);
     return rc;
+}
+
+int ptrt_render_wireframe(ptrt_ctx *c, float thickness, void *out_rgb8, int out_is_device) {
+    if (!ctx_live(c)) // (marks the context touched: a pipelined path frame that follows waits for the stream, and so for this)
+        return fail(c, PTRT_E_INVALID, "ptrt_render_wireframe: bad context");
+    if (c->il_period > 1)
+        return fail(c, PTRT_E_INVALID, "ptrt_render_wireframe: an interleaved context (its strips are assembled by the tile farm, "
+                                       "which has no wireframe view); use a full-frame or band context");
+    if (!out_rgb8 || out_is_device < PTRT_OUT_HOST || out_is_device > PTRT_OUT_DEVICE_FRAME)
+        return fail(c, PTRT_E_INVALID, "ptrt_render_wireframe: needs a target (out_rgb8 %p, out_is_device %d)", out_rgb8,
+                    out_is_device);
+    if (!c->have_geometry || !c->have_materials)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_render_wireframe: %s not uploaded", c->have_geometry ? "materials" : "geometry");
+    if (c->n_materials < c->n_meshes)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_render_wireframe: %d materials for %d meshes", c->n_materials, c->n_meshes);
+    if (int rc = set_device(c))
+        return rc;
+    if (!out_is_device && !c->wire_rgb8)
+        HIP_TRY(c, hipMalloc((void **)&c->wire_rgb8, c->npix * 3));
+    pt::KParams K = make_params(c);
+    // the full frame, whatever the render size of the path tracer (the reference launches width x height)
+    K.width = c->W;
+    K.height = c->H;
+    K.y0 = c->y0;
+    K.rows = c->rows;
+    K.tiles_x = (c->W + 7) / 8;
+    K.rng = nullptr;
+    K.accum = K.normal = K.depth = nullptr;
+    K.object_id = nullptr;
+    K.counters = nullptr;
+    K.rgb8 = out_is_device ? (unsigned char *)out_rgb8 : c->wire_rgb8;
+    K.rgb8_frame = out_is_device == PTRT_OUT_DEVICE_FRAME ? 1 : 0;
+    const int geom = pick_geom(c);
+    const size_t lds = (geom == 0) ? 0 : (size_t)c->stack_entries * 64 * sizeof(uint2);
+    const dim3 grid(K.tiles_x, (c->rows + 7) / 8);
+    if (geom == 0)
+        hipLaunchKernelGGL(pt::wireframe_kernel<0>, grid, dim3(64), lds, c->stream, K, thickness);
+    else if (geom == 1)
+        hipLaunchKernelGGL(pt::wireframe_kernel<1>, grid, dim3(64), lds, c->stream, K, thickness);
+    else
+        hipLaunchKernelGGL(pt::wireframe_kernel<2>, grid, dim3(64), lds, c->stream, K, thickness);
+    HIP_TRY(c, hipGetLastError());
+    if (out_is_device == PTRT_OUT_DEVICE)
+        ring_mark_rendered(out_rgb8, c->stream);
+    if (!out_is_device) {
+        HIP_TRY(c, hipMemcpyAsync(out_rgb8, c->wire_rgb8, c->npix * 3, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return PTRT_OK;
 }
 
 int ptrt_get_stats(ptrt_ctx *c, ptrt_stats *out) {

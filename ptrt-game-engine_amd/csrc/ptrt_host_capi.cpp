@@ -343,6 +343,14 @@ int hs_render_to_host(void *s, void *host_pixels) {
     HS_TRY(static_cast<Scene *>(s)->render_to_host(static_cast<unsigned char *>(host_pixels)));
     return 0;
 }
+int hs_render_wireframe_to_device(void *s, void *device_pixels, float thickness) {
+    HS_TRY(static_cast<Scene *>(s)->render_to_device_wireframe(static_cast<unsigned char *>(device_pixels), thickness));
+    return 0;
+}
+int hs_render_wireframe_to_host(void *s, void *host_pixels, float thickness) {
+    HS_TRY(static_cast<Scene *>(s)->render_wireframe_to_host(static_cast<unsigned char *>(host_pixels), thickness));
+    return 0;
+}
 int hs_post_frame(void *s, const float *accum, const float *normal, const float *depth, const int *object_id,
                   void *pixels, int is_device) {
     HS_TRY(static_cast<Scene *>(s)->postFrameFromDevice(accum, normal, depth, object_id,

@@ -5,9 +5,9 @@
 // renderer can switch headers.  What differs is underneath: the scene is
 // flattened once per change into plain arrays and handed to the C ABI of
 // include/ptrt.h, which owns every device allocation.  Out of scope here (see
-// DESIGN.md): denoiser, bloom, resolution scaling, HDRI sky, wireframe and
-// debug-visualisation helpers -- their setters are accepted and recorded so call
-// sites compile, and `render_to_device` reports when one is enabled.
+// DESIGN.md): the debug-visualisation helper meshes (frustum, ray arrows) -- their
+// setters are accepted and recorded so call sites compile, and
+// `updateVisualizationMeshes` reports when one is enabled.
 #pragma once
 #include "hdr.hpp"
 #include "mesh.hpp"
@@ -769,13 +769,15 @@ class Scene {
             }
         std::cout << "generated primary rays" << '\n';
     }
-    // the wireframe debug kernel is out of scope: says so once and shows the path-traced frame instead
-    void render_to_device_wireframe(unsigned char *device_pixels, float /*wireframeThickness*/) {
-        if (!warnedViz) {
-            std::cerr << "NOTE: wireframe rendering is not part of this back end; rendering the path-traced frame\n";
-            warnedViz = true;
-        }
-        render_to_device(device_pixels);
+    // scene.cuh:1211-1245: render_kernel_wireframe over the full frame (ptrt_render_wireframe), then a sync (ptrt_sync).
+    // Leaves the frame counter, the accumulation, the generator states and the denoiser history alone, as the reference
+    // does.  `device_pixels`: this scene's rows, bottom-up, as render_to_device writes them.
+    void render_to_device_wireframe(unsigned char *device_pixels, float wireframeThickness) {
+        renderWireframe(device_pixels, wireframeThickness, PTRT_OUT_DEVICE);
+    }
+    // the same image into HOST memory (synchronous), like render_to_host
+    void render_wireframe_to_host(unsigned char *host_pixels, float wireframeThickness) {
+        renderWireframe(host_pixels, wireframeThickness, PTRT_OUT_HOST);
     }
 
     // ---- upload + render -------------------------------------------------------------
@@ -1258,6 +1260,38 @@ class Scene {
         gpu_resources_initialized = true;
     }
 
+    // the acceleration structures, then the camera, sky and environment map the back end caches: what a frame reads
+    void updateDeviceScene() {
+        updateAccelerationStructures();
+        if (cameraDirty) {
+            ptrt_camera c = camera.flat();
+            check(ptrt_set_camera(ctx, &c), "Failed to set camera");
+            cameraDirty = false;
+        }
+        if (skyDirty) {
+            ptrt_vec3 t{sky_color_top.x, sky_color_top.y, sky_color_top.z},
+                b{sky_color_bottom.x, sky_color_bottom.y, sky_color_bottom.z};
+            check(ptrt_set_sky(ctx, &t, &b, use_sky ? 1 : 0), "Failed to set sky");
+            skyDirty = false;
+        }
+        if (envDirty) {
+            check(ptrt_set_env_map(ctx, envMap.empty() ? nullptr : envMap.data(), env_width, env_height),
+                  "Failed to upload the environment map");
+            envDirty = false;
+        }
+    }
+
+    void renderWireframe(unsigned char *pixels, float thickness, int is_device) {
+        if (meshes.empty()) {
+            std::cerr << "Error: no meshes in scene\n";
+            return;
+        }
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_render_wireframe(ctx, thickness, pixels, is_device), "Wireframe kernel failed");
+        check(ptrt_sync(ctx), "Wireframe kernel failed"); // cudaDeviceSynchronize (scene.cuh:1244)
+    }
+
     void renderInternal(unsigned char *pixels, int is_device) {
         // validateGPUResources: message on cerr and return without rendering (scene.cuh:216-251,1029-1031)
         if (meshes.empty()) {
@@ -1287,23 +1321,7 @@ class Scene {
                   "denoiser option");
             check(ptrt_set_prev_view_proj(ctx, prev_view_proj.m), "prev view-proj");
         }
-        updateAccelerationStructures();
-        if (cameraDirty) {
-            ptrt_camera c = camera.flat();
-            check(ptrt_set_camera(ctx, &c), "Failed to set camera");
-            cameraDirty = false;
-        }
-        if (skyDirty) {
-            ptrt_vec3 t{sky_color_top.x, sky_color_top.y, sky_color_top.z},
-                b{sky_color_bottom.x, sky_color_bottom.y, sky_color_bottom.z};
-            check(ptrt_set_sky(ctx, &t, &b, use_sky ? 1 : 0), "Failed to set sky");
-            skyDirty = false;
-        }
-        if (envDirty) {
-            check(ptrt_set_env_map(ctx, envMap.empty() ? nullptr : envMap.data(), env_width, env_height),
-                  "Failed to upload the environment map");
-            envDirty = false;
-        }
+        updateDeviceScene();
         int rc = ptrt_render(ctx, frame_count_, perfSettings.samplesPerPixel, perfSettings.maxBounceDepth, pixels,
                              is_device);
         if (rc != PTRT_OK) // launch errors are logged, not thrown (scene.cuh:1036-1042)

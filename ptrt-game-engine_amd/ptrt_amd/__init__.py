@@ -143,6 +143,7 @@ _sig("ptrt_read_buffer", C.c_int, _vp, C.c_int, _vp, C.c_size_t)
 _sig("ptrt_device_buffer", _vp, _vp, C.c_int)
 _sig("ptrt_write_rng", C.c_int, _vp, C.POINTER(C.c_uint32), C.c_size_t)
 _sig("ptrt_trace_rays", C.c_int, _vp, _fp, _fp, C.c_int, _vp)
+_sig("ptrt_render_wireframe", C.c_int, _vp, C.c_float, _vp, C.c_int)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
 _sig("ptrt_set_option", C.c_int, _vp, C.c_char_p, C.c_longlong)
 _sig("ptrt_get_option", C.c_int, _vp, C.c_char_p, C.POINTER(C.c_longlong))
@@ -249,6 +250,8 @@ _sig("hs_update_triangles", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
 _sig("hs_mesh_prim_indices", C.c_int, _vp, C.c_int, C.POINTER(C.c_int), C.c_int)
 _sig("hs_render_to_device", C.c_int, _vp, _vp)
 _sig("hs_render_to_host", C.c_int, _vp, _vp)
+_sig("hs_render_wireframe_to_device", C.c_int, _vp, _vp, C.c_float)
+_sig("hs_render_wireframe_to_host", C.c_int, _vp, _vp, C.c_float)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
 _sig("hs_get_frame_count", C.c_int, _vp)
 _sig("hs_set_frame_count", None, _vp, C.c_int)
@@ -539,6 +542,17 @@ class Scene:
     def render_to_host(self):
         out = np.empty((self.tile_rows, self.width, 3), dtype=np.uint8)
         self._chk(lib.hs_render_to_host(self._h, out.ctypes.data_as(_vp)))
+        return out
+
+    def render_to_device_wireframe(self, device_ptr, thickness):
+        """`Scene::render_to_device_wireframe(unsigned char*, float)`: the wireframe view (edges of every hit triangle
+        closer than `thickness` in barycentrics, the sky elsewhere), RGB8 bottom-up into device memory; synchronises."""
+        self._chk(lib.hs_render_wireframe_to_device(self._h, C.c_void_p(device_ptr), float(thickness)))
+
+    def render_wireframe_to_host(self, thickness):
+        """The wireframe view into a host array (tile_rows, width, 3), in the buffer's bottom-up order like render_to_host."""
+        out = np.empty((self.tile_rows, self.width, 3), dtype=np.uint8)
+        self._chk(lib.hs_render_wireframe_to_host(self._h, out.ctypes.data_as(_vp), float(thickness)))
         return out
 
     def post_frame(self, accum_ptr, normal_ptr, depth_ptr, object_id_ptr, out_device_ptr=None):
