@@ -606,6 +606,69 @@ int ptrt_launch_ms_history(ptrt_ctx *ctx, float *trace_ms, float *tail_ms, int m
  * (synchronises).  Either pointer may be NULL. */
 int ptrt_last_kernel_ms(ptrt_ctx *ctx, float *trace_ms, float *tonemap_ms);
 
+
+/* ---- the one-bounce ray tracer of src/raytracer/ (RTscene.cuh, RTmesh.cuh, RTcamera.cuh) ---------------------------
+ * A context of its own, separate from ptrt_ctx: the RT Scene keeps one geometry buffer and one BVH per mesh (no TLAS),
+ * a descriptor array (material + rigid transform per mesh) and a light array, and renders render_kernel
+ * (RTscene.cuh:1240-1293) into an RGB8 frame, bottom-up.  Every entry returns PTRT_OK or a negative code; the message,
+ * naming the entry point, is read with ptrt_rt_last_error.  (ABI 6, additions only.) */
+typedef struct ptrt_rt_ctx ptrt_rt_ctx;
+
+typedef struct ptrt_rt_material { /* Material, RTscene.cuh:21-61 (108 B) */
+    ptrt_vec3 albedo, specular;
+    float metallic, roughness;
+    ptrt_vec3 emission;
+    float ior, transmission, transmission_roughness, clearcoat, clearcoat_roughness;
+    ptrt_vec3 subsurface_color;
+    float subsurface_radius, anisotropy, sheen;
+    ptrt_vec3 sheen_tint;
+    float iridescence, iridescence_thickness;
+} ptrt_rt_material;
+
+typedef struct ptrt_rt_mesh { /* the per-mesh part of DeviceMesh (RTscene.cuh:84-102): material and rigid transform */
+    ptrt_rt_material material;
+    ptrt_vec3 translation;
+    float rotation[9], inv_rotation[9]; /* row-major mat3: rotY * rotX * rotZ and its transpose */
+} ptrt_rt_mesh;
+
+typedef struct ptrt_rt_light { /* Light, RTscene.cuh:64-80 (56 B): type 0 point, 1 directional, 2 spot; cones are cosines */
+    int32_t type;
+    ptrt_vec3 position, direction, color;
+    float intensity, range, inner_cone, outer_cone;
+} ptrt_rt_light;
+
+typedef struct ptrt_rt_view { /* what render_kernel takes besides the arrays: Camera's vectors, ambient, sky */
+    ptrt_vec3 origin, corner_minus_origin, horizontal, vertical;
+    ptrt_vec3 ambient, sky_top, sky_bottom;
+    int32_t use_sky;
+} ptrt_rt_view;
+
+/* Scene::Scene(w, h) of RTscene.cuh:789-796: a width x height frame on HIP device `device`.  PTRT_E_NO_DEVICE without
+ * one (there is no CPU path). */
+int ptrt_rt_create(int width, int height, int device, ptrt_rt_ctx **out);
+/* Scene::~Scene (RTscene.cuh:798-808).  NULL and dead handles are ignored. */
+void ptrt_rt_destroy(ptrt_rt_ctx *ctx);
+/* The message of the context's last failure (of the thread's last failure for NULL or a dead handle). */
+const char *ptrt_rt_last_error(const ptrt_rt_ctx *ctx);
+/* Mesh::upload (RTmesh.cuh:420-431) of mesh slot `index` (< the slot count replaces, == appends): its vertices and
+ * index triples, every index inside 0..vert_count-1.  The slot's BVH is kept: a tree uploaded earlier is walked over
+ * the new triangles, as in the reference when vertices change without bvhDirty. */
+int ptrt_rt_upload_mesh(ptrt_rt_ctx *ctx, int index, const ptrt_vec3 *verts, int vert_count, const ptrt_tri *faces,
+                        int face_count);
+/* Mesh::uploadBVH (RTmesh.cuh:554-568) of an existing slot: DeviceBVHNode array (node 0 the root, an inner node's
+ * children -1 or after it, a leaf's range inside the primitive array) and the face indices of the leaves. */
+int ptrt_rt_upload_bvh(ptrt_rt_ctx *ctx, int index, const ptrt_bvh_node *nodes, int node_count, const int32_t *prims,
+                       int prim_count);
+/* The descriptor part of Scene::uploadToGPU / render_to_device (RTscene.cuh:1031-1100, 1134-1196): material and
+ * transform of slots 0..mesh_count-1 and the lights.  Copies descriptors only; geometry stays where it is. */
+int ptrt_rt_set_scene(ptrt_rt_ctx *ctx, const ptrt_rt_mesh *meshes, int mesh_count, const ptrt_rt_light *lights,
+                      int light_count);
+/* The launch of Scene::render / render_to_device (RTscene.cuh:1102-1132, 1198-1210): render_kernel over the frame with
+ * the last ptrt_rt_set_scene, into out_rgb8 (PTRT_OUT_HOST: host memory, PTRT_OUT_DEVICE: device memory of the
+ * context's device, width*height*3 bytes each).  Synchronous, like the reference's cudaDeviceSynchronize.
+ * PTRT_E_NOT_READY before ptrt_rt_set_scene; PTRT_E_INVALID if a mesh's tree names a face its geometry lacks. */
+int ptrt_rt_render(ptrt_rt_ctx *ctx, const ptrt_rt_view *view, void *out_rgb8, int out_is_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include "pt_wavefront.hip.h"
 #include "pt_async.hip.h"
 #include "pt_wireframe.hip.h"
+#include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -3454,3 +3455,310 @@ int ptrt_debug_shade(ptrt_ctx *c, int op, int full, const float *in, int n, floa
 } // extern "C"
 
 #include "ptrt_farm.hip.h"
+
+// =====================================================================================
+// The one-bounce ray tracer (include/ptrt.h "ptrt_rt_*"; kernel rt_render.hip.h)
+static_assert(sizeof(ptrt_rt_material) == sizeof(rt::Mat), "ptrt_rt_material and rt::Mat differ");
+static_assert(sizeof(ptrt_rt_light) == sizeof(rt::LightDev), "ptrt_rt_light and rt::LightDev differ");
+
+struct ptrt_rt_ctx {
+    int device = 0, W = 0, H = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    struct Slot {
+        float4 *tris = nullptr; // 3 per face: v0, v1 - v0, v2 - v0
+        int faces = 0;
+        float4 *nodes = nullptr; // 2 per node
+        int node_count = 0;
+        int *prims = nullptr;
+        int max_prim = -1; // the largest face index the tree names
+    };
+    std::vector<Slot> slots;
+    std::vector<ptrt_rt_mesh> meshes; // the last ptrt_rt_set_scene
+    std::vector<ptrt_rt_light> lights;
+    bool have_scene = false;
+    rt::MeshDev *d_desc = nullptr;
+    int desc_cap = 0;
+    rt::LightDev *d_lights = nullptr;
+    int light_cap = 0;
+    unsigned char *d_out = nullptr; // staging of PTRT_OUT_HOST renders
+};
+
+namespace {
+std::set<ptrt_rt_ctx *> g_rt_live;
+
+bool rt_live(const ptrt_rt_ctx *c) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    return c && g_rt_live.count(const_cast<ptrt_rt_ctx *>(c));
+}
+
+// as fail(): a stale handle is never written to
+int rt_fail(ptrt_rt_ctx *c, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_last_error = buf;
+    if (c) {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        if (g_rt_live.count(c))
+            c->err = buf;
+    }
+    return code;
+}
+
+#define RT_TRY(c, call)                                                                                        \
+    do {                                                                                                       \
+        hipError_t e_ = (call);                                                                                \
+        if (e_ != hipSuccess)                                                                                  \
+            return rt_fail((c), PTRT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));                    \
+    } while (0)
+
+float rt_bits(int i) {
+    float f;
+    std::memcpy(&f, &i, sizeof f);
+    return f;
+}
+
+void rt_free_slot(ptrt_rt_ctx::Slot &s) {
+    dfree(s.tris);
+    dfree(s.nodes);
+    dfree(s.prims);
+    s = ptrt_rt_ctx::Slot{};
+}
+} // namespace
+
+extern "C" {
+
+int ptrt_rt_create(int width, int height, int device, ptrt_rt_ctx **out) {
+    if (!out)
+        return rt_fail(nullptr, PTRT_E_INVALID, "ptrt_rt_create: out is NULL");
+    *out = nullptr;
+    if (width <= 0 || height <= 0)
+        return rt_fail(nullptr, PTRT_E_INVALID, "ptrt_rt_create: bad frame size %dx%d", width, height);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return rt_fail(nullptr, PTRT_E_NO_DEVICE, "ptrt_rt_create: no HIP device available (%s); this library has no CPU path",
+                       e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+    if (device < 0 || device >= ndev)
+        return rt_fail(nullptr, PTRT_E_NO_DEVICE, "ptrt_rt_create: device %d out of range (have %d)", device, ndev);
+    RT_TRY(nullptr, hipSetDevice(device));
+    ptrt_rt_ctx *c = new ptrt_rt_ctx();
+    c->device = device;
+    c->W = width;
+    c->H = height;
+    if (hipStreamCreate(&c->stream) != hipSuccess) {
+        delete c;
+        return rt_fail(nullptr, PTRT_E_HIP, "ptrt_rt_create: hipStreamCreate failed");
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        g_rt_live.insert(c);
+    }
+    *out = c;
+    return PTRT_OK;
+}
+
+void ptrt_rt_destroy(ptrt_rt_ctx *c) {
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        if (!c || !g_rt_live.count(c))
+            return;
+        g_rt_live.erase(c);
+    }
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    for (auto &s : c->slots)
+        rt_free_slot(s);
+    dfree(c->d_desc);
+    dfree(c->d_lights);
+    dfree(c->d_out);
+    (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+const char *ptrt_rt_last_error(const ptrt_rt_ctx *c) {
+    if (rt_live(c))
+        return c->err.c_str();
+    return g_last_error.c_str();
+}
+
+int ptrt_rt_upload_mesh(ptrt_rt_ctx *c, int index, const ptrt_vec3 *verts, int vert_count, const ptrt_tri *faces,
+                        int face_count) {
+    if (!rt_live(c))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_mesh: bad context");
+    if (index < 0 || index > (int)c->slots.size())
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_mesh: slot %d of %d", index, (int)c->slots.size());
+    if (vert_count < 0 || face_count < 0 || (face_count > 0 && (!verts || !faces)))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_mesh: bad arrays (%d vertices, %d faces)", vert_count, face_count);
+    std::vector<float4> rec((size_t)face_count * 3);
+    for (int f = 0; f < face_count; ++f) {
+        const ptrt_tri t = faces[f];
+        if (t.v0 < 0 || t.v1 < 0 || t.v2 < 0 || t.v0 >= vert_count || t.v1 >= vert_count || t.v2 >= vert_count)
+            return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_mesh: face %d references a vertex out of range", f);
+        const ptrt_vec3 a = verts[t.v0], b = verts[t.v1], d = verts[t.v2];
+        rec[3 * f + 0] = make_float4(a.x, a.y, a.z, 0.0f);
+        rec[3 * f + 1] = make_float4(b.x - a.x, b.y - a.y, b.z - a.z, 0.0f);
+        rec[3 * f + 2] = make_float4(d.x - a.x, d.y - a.y, d.z - a.z, 0.0f);
+    }
+    RT_TRY(c, hipSetDevice(c->device));
+    RT_TRY(c, hipStreamSynchronize(c->stream)); // a render in flight may still read the old buffer
+    if (index == (int)c->slots.size())
+        c->slots.emplace_back();
+    ptrt_rt_ctx::Slot &s = c->slots[index];
+    dfree(s.tris);
+    s.faces = 0;
+    if (face_count > 0) {
+        RT_TRY(c, hipMalloc((void **)&s.tris, rec.size() * sizeof(float4)));
+        RT_TRY(c, hipMemcpy(s.tris, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    s.faces = face_count;
+    return PTRT_OK;
+}
+
+int ptrt_rt_upload_bvh(ptrt_rt_ctx *c, int index, const ptrt_bvh_node *nodes, int node_count, const int32_t *prims,
+                       int prim_count) {
+    if (!rt_live(c))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_bvh: bad context");
+    if (index < 0 || index >= (int)c->slots.size())
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_bvh: slot %d of %d (upload the mesh first)", index, (int)c->slots.size());
+    if (node_count < 0 || prim_count < 0 || (node_count > 0 && !nodes) || (prim_count > 0 && !prims))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_bvh: bad arrays (%d nodes, %d primitives)", node_count, prim_count);
+    std::vector<float4> rec((size_t)node_count * 2);
+    for (int i = 0; i < node_count; ++i) {
+        const ptrt_bvh_node &n = nodes[i];
+        int a, b;
+        if (n.count > 0) {
+            if (n.start < 0 || n.start > prim_count - n.count)
+                return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_bvh: leaf %d's range [%d, +%d) outside %d primitives", i, n.start,
+                               n.count, prim_count);
+            a = n.start;
+            b = ~n.count;
+        } else {
+            // children after their parent: the walk from node 0 ends
+            if ((n.left != -1 && (n.left <= i || n.left >= node_count)) || (n.right != -1 && (n.right <= i || n.right >= node_count)))
+                return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_bvh: node %d's children %d, %d (need -1 or %d..%d)", i, n.left,
+                               n.right, i + 1, node_count - 1);
+            a = n.left;
+            b = n.right;
+        }
+        rec[2 * i + 0] = make_float4(n.bmin.x, n.bmin.y, n.bmin.z, rt_bits(a));
+        rec[2 * i + 1] = make_float4(n.bmax.x, n.bmax.y, n.bmax.z, rt_bits(b));
+    }
+    int max_prim = -1;
+    for (int i = 0; i < prim_count; ++i) {
+        if (prims[i] < 0)
+            return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_upload_bvh: primitive %d is face %d", i, prims[i]);
+        max_prim = std::max(max_prim, (int)prims[i]);
+    }
+    RT_TRY(c, hipSetDevice(c->device));
+    RT_TRY(c, hipStreamSynchronize(c->stream));
+    ptrt_rt_ctx::Slot &s = c->slots[index];
+    dfree(s.nodes);
+    dfree(s.prims);
+    s.node_count = 0;
+    s.max_prim = -1;
+    if (node_count > 0) {
+        RT_TRY(c, hipMalloc((void **)&s.nodes, rec.size() * sizeof(float4)));
+        RT_TRY(c, hipMemcpy(s.nodes, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    if (prim_count > 0) {
+        RT_TRY(c, hipMalloc((void **)&s.prims, (size_t)prim_count * sizeof(int)));
+        RT_TRY(c, hipMemcpy(s.prims, prims, (size_t)prim_count * sizeof(int), hipMemcpyHostToDevice));
+    }
+    s.node_count = node_count;
+    s.max_prim = max_prim;
+    return PTRT_OK;
+}
+
+int ptrt_rt_set_scene(ptrt_rt_ctx *c, const ptrt_rt_mesh *meshes, int mesh_count, const ptrt_rt_light *lights, int light_count) {
+    if (!rt_live(c))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_set_scene: bad context");
+    if (mesh_count < 0 || mesh_count > (int)c->slots.size() || (mesh_count > 0 && !meshes) || light_count < 0 ||
+        (light_count > 0 && !lights))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_set_scene: %d meshes (%d uploaded), %d lights", mesh_count,
+                       (int)c->slots.size(), light_count);
+    c->meshes.assign(meshes, meshes + mesh_count);
+    c->lights.assign(lights, lights + light_count);
+    c->have_scene = true;
+    return PTRT_OK;
+}
+
+int ptrt_rt_render(ptrt_rt_ctx *c, const ptrt_rt_view *view, void *out_rgb8, int out_is_device) {
+    if (!rt_live(c))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_render: bad context");
+    if (!view || !out_rgb8 || (out_is_device != PTRT_OUT_HOST && out_is_device != PTRT_OUT_DEVICE))
+        return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_render: needs a view and a target (out_rgb8 %p, out_is_device %d)", out_rgb8,
+                       out_is_device);
+    if (!c->have_scene)
+        return rt_fail(c, PTRT_E_NOT_READY, "ptrt_rt_render: no scene (ptrt_rt_set_scene)");
+    const int n = (int)c->meshes.size(), nl = (int)c->lights.size();
+    std::vector<rt::MeshDev> desc(n);
+    for (int i = 0; i < n; ++i) {
+        const ptrt_rt_ctx::Slot &s = c->slots[i];
+        const ptrt_rt_mesh &m = c->meshes[i];
+        const bool has_tree = s.node_count > 0 && s.faces > 0;
+        if (has_tree && s.max_prim >= s.faces)
+            return rt_fail(c, PTRT_E_INVALID, "ptrt_rt_render: mesh %d's tree names face %d of %d (upload a tree built for these faces)",
+                           i, s.max_prim, s.faces);
+        rt::MeshDev &d = desc[i];
+        d.tris = s.tris;
+        d.nodes = s.nodes;
+        d.prims = s.prims;
+        d.face_count = has_tree ? s.faces : 0;
+        d.node_count = has_tree ? s.node_count : 0;
+        d.translation[0] = m.translation.x;
+        d.translation[1] = m.translation.y;
+        d.translation[2] = m.translation.z;
+        std::memcpy(d.rot, m.rotation, sizeof d.rot);
+        std::memcpy(d.inv, m.inv_rotation, sizeof d.inv);
+        std::memcpy(&d.mat, &m.material, sizeof d.mat);
+    }
+    RT_TRY(c, hipSetDevice(c->device));
+    RT_TRY(c, hipStreamSynchronize(c->stream));
+    if (n > c->desc_cap) {
+        dfree(c->d_desc);
+        RT_TRY(c, hipMalloc((void **)&c->d_desc, (size_t)n * sizeof(rt::MeshDev)));
+        c->desc_cap = n;
+    }
+    if (nl > c->light_cap) {
+        dfree(c->d_lights);
+        RT_TRY(c, hipMalloc((void **)&c->d_lights, (size_t)nl * sizeof(rt::LightDev)));
+        c->light_cap = nl;
+    }
+    if (n)
+        RT_TRY(c, hipMemcpy(c->d_desc, desc.data(), (size_t)n * sizeof(rt::MeshDev), hipMemcpyHostToDevice));
+    if (nl)
+        RT_TRY(c, hipMemcpy(c->d_lights, c->lights.data(), (size_t)nl * sizeof(rt::LightDev), hipMemcpyHostToDevice));
+    const size_t bytes = (size_t)c->W * c->H * 3;
+    if (out_is_device == PTRT_OUT_HOST && !c->d_out)
+        RT_TRY(c, hipMalloc((void **)&c->d_out, bytes));
+    auto v3 = [](ptrt_vec3 v) { return pt::f3{v.x, v.y, v.z}; };
+    rt::Params P{};
+    P.meshes = c->d_desc;
+    P.lights = c->d_lights;
+    P.n_meshes = n;
+    P.n_lights = nl;
+    P.cam_origin = v3(view->origin);
+    P.cam_cmo = v3(view->corner_minus_origin);
+    P.cam_horizontal = v3(view->horizontal);
+    P.cam_vertical = v3(view->vertical);
+    P.ambient = v3(view->ambient);
+    P.sky_top = v3(view->sky_top);
+    P.sky_bottom = v3(view->sky_bottom);
+    P.use_sky = view->use_sky ? 1 : 0;
+    P.out = out_is_device ? (unsigned char *)out_rgb8 : c->d_out;
+    P.width = c->W;
+    P.height = c->H;
+    const dim3 grid((c->W + 7) / 8, (c->H + 7) / 8);
+    hipLaunchKernelGGL(rt::rt_render_kernel, grid, dim3(64), 0, c->stream, P);
+    RT_TRY(c, hipGetLastError());
+    if (!out_is_device)
+        RT_TRY(c, hipMemcpyAsync(out_rgb8, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    RT_TRY(c, hipStreamSynchronize(c->stream));
+    return PTRT_OK;
+}
+
+} // extern "C"
