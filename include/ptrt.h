@@ -417,9 +417,33 @@ void *ptrt_device_buffer(ptrt_ctx *ctx, int kind);
 int ptrt_write_rng(ptrt_ctx *ctx, const uint32_t *states, size_t bytes);
 
 /* Scene::traceSingleRay -> trace_single_ray_kernel (scene.cuh:1367-1391,
- * scene_kernels.cuh:38-49); batched: n rays, origins/directions as n*3 floats. */
+ * scene_kernels.cuh:38-49); batched: n rays, origins/directions as n*3 floats in HOST memory.
+ * Stages them through device memory it allocates, runs the PTRT_QUERY_CLOSEST query of
+ * ptrt_query_rays and synchronises. */
 int ptrt_trace_rays(ptrt_ctx *ctx, const float *origins, const float *directions, int n,
                     ptrt_hit *out_hits);
+
+/* Batched ray queries on DEVICE memory (ABI 6, addition only; no counterpart in the reference).
+ *   PTRT_QUERY_CLOSEST   out = ptrt_hit[n]: per ray the record ptrt_trace_rays returns (traceRay + the HitInfo fields of
+ *                        traceSingleRay); `tmax` must be NULL.
+ *   PTRT_QUERY_OCCLUDED  out = int32_t[n]: 1 if bvh_any_hit_tlas(ray, tmax[i]) (intersection.cuh:481-524) finds a hit, else 0
+ *                        -- the reference's shadow query: meshes with transmission > 0.5 never occlude, the traversal
+ *                        stacks' limits and dropped pushes are the reference's.  `tmax` (n floats) is required.
+ * `origins` and `directions` are n*3 floats.  All four pointers must be device memory of the context's device, each
+ * allocation large enough for n rays.  The call is enqueued on the context's stream (ptrt_set_stream: the caller's) and
+ * returns without synchronising; it allocates and copies nothing.  It runs behind everything earlier on that stream --
+ * every earlier ptrt_render of the context (pipelined and split frames are joined onto the stream), geometry uploads,
+ * vertex updates, refits, rebuilds, instance updates -- and later frames are ordered behind it, as behind
+ * ptrt_render_wireframe.  It touches no generator state, accumulation, G-buffer, RGB8 image, counter of ptrt_get_stats
+ * or timing history.  The traversal is the path tracer's for the scene and options (ptrt_get_option "query_pmode":
+ * 0 one ray per lane, 1..3 the pair walks; options pair_trace / force_geom).  Band and interleaved contexts answer
+ * for the whole scene.  PTRT_E_INVALID for a bad kind, n < 0, a NULL pointer, tmax given for CLOSEST or missing for
+ * OCCLUDED, or memory that is not the context's device memory; PTRT_E_NOT_READY before geometry is uploaded; n == 0
+ * returns PTRT_OK and launches nothing. */
+#define PTRT_QUERY_CLOSEST 0  /* out: ptrt_hit[n]  */
+#define PTRT_QUERY_OCCLUDED 1 /* out: int32_t[n]   */
+int ptrt_query_rays(ptrt_ctx *ctx, int kind, const float *origins, const float *directions, const float *tmax, int n,
+                    void *out);
 
 /* The body of Scene::render_to_device_wireframe (scene.cuh:1211-1245): render_kernel_wireframe
  * (scene_kernels.cuh:53-117, wireframeMode true) over the full width x height -- the render size of the path tracer,
@@ -578,7 +602,8 @@ int ptrt_set_option(ptrt_ctx *ctx, const char *name, long long value);
 /* Reads an option back, and -- read-only -- what the last ptrt_render launched, so that a measurement can name the kernel it
  * timed: render_mode (0 megakernel, 1 wavefront stages, 2 asynchronous lanes), pmode (0 lock-step, 1 pairs over LDS-staged
  * triangles, 2 pair queue, 3 TLAS rounds, 4 merged queue), merged_eff (loop shape of that launch), merged_decided (0 while
- * merged = -1 is still sampling), launches.  ABI 5. */
+ * merged = -1 is still sampling), launches.  ABI 5.  Also read-only (ABI 6): query_pmode, the traversal of the last
+ * ptrt_query_rays / ptrt_trace_rays (-1 none yet), and stream, the hipStream_t the context enqueues on. */
 int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
 
 /* Render on a caller-owned HIP stream (a `hipStream_t` passed as void*; NULL returns to the

@@ -805,7 +805,7 @@ __global__ void rng_aos_to_planar(const uint32_t *aos, uint32_t *planar, size_t 
 }
 
 // ---------------------------------------------------------------------------------
-// trace_single_ray_kernel, batched: one lane per ray
+// trace_single_ray_kernel's record (ray_query_kernel, pt_query.hip.h, writes it)
 // ---------------------------------------------------------------------------------
 struct HitOut { // == ptrt_hit (include/ptrt.h)
     int hit;
@@ -816,47 +816,6 @@ struct HitOut { // == ptrt_hit (include/ptrt.h)
     int face_index;
     float local_point[3];
 };
-template <int GEOM>
-__global__ __launch_bounds__(64) void trace_rays_kernel(const KParams K, const float *origins, const float *dirs, int n,
-                                                        HitOut *out) {
-    extern __shared__ uint2 lds_stack[];
-    LdsStack stk{lds_stack + threadIdx.x};
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    const bool live = i < n;
-    const int j = live ? i : 0;
-    const f3 o = mk3(origins[j * 3], origins[j * 3 + 1], origins[j * 3 + 2]);
-    const f3 d = mk3(dirs[j * 3], dirs[j * 3 + 1], dirs[j * 3 + 2]);
-    const Hit h = closest_hit<GEOM>(K, live, o, d, stk);
-    if (!live)
-        return;
-    HitOut r;
-    if (h.mesh < 0) { // HitInfo() defaults (intersection.cuh:122-124)
-        r.hit = 0;
-        r.t = 1e30f;
-        r.point[0] = r.point[1] = r.point[2] = 0.0f;
-        r.normal[0] = r.normal[1] = r.normal[2] = 0.0f;
-        r.mesh_index = -1;
-        r.front_face = 1;
-        r.u = r.v = 0.0f;
-        r.face_index = -1;
-        r.local_point[0] = r.local_point[1] = r.local_point[2] = 0.0f;
-    } else {
-        f3 lp;
-        int face;
-        const Surface s = make_surface(K, h, o, d, &lp, &face);
-        r.hit = 1;
-        r.t = h.t;
-        r.point[0] = s.point.x; r.point[1] = s.point.y; r.point[2] = s.point.z;
-        r.normal[0] = s.normal.x; r.normal[1] = s.normal.y; r.normal[2] = s.normal.z;
-        r.mesh_index = h.mesh;
-        r.front_face = s.front_face ? 1 : 0;
-        r.u = h.u;
-        r.v = h.v;
-        r.face_index = face;
-        r.local_point[0] = lp.x; r.local_point[1] = lp.y; r.local_point[2] = lp.z;
-    }
-    out[i] = r;
-}
 
 // exhaustive check of rcp_ieee: every fp32 bit pattern, against the compiler's IEEE division.
 // out[0] = number of mismatching inputs, out[1..8] = first few offending bit patterns.

@@ -15,6 +15,7 @@
 #include "pt_wavefront.hip.h"
 #include "pt_async.hip.h"
 #include "pt_wireframe.hip.h"
+#include "pt_query.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -230,6 +231,7 @@ struct ptrt_ctx {
     int tune_n = 0, tune_choice = -1;    // auto: frames measured so far (variants alternate), the decision (-1: none yet)
     unsigned long long tune_key = ~0ull, tune_launch[2 * TUNE_SAMPLES] = {};
     int last_pmode = 0;                  // PMODE of the last megakernel launch (ptrt_get_option "pmode")
+    int query_pmode = -1;                // traversal of the last ray query (ptrt_get_option "query_pmode"; -1 none yet)
     bool last_merged_possible = false;   // ... and whether that scene has the two loop shapes to choose from
     bool timed = false;
     bool prev_post = false;              // the previous frame had a denoiser / bloom chain behind its trace (ptrt_render "pipeline")
@@ -3061,6 +3063,74 @@ int ptrt_write_rng(ptrt_ctx *c, const uint32_t *states, size_t bytes) {
     return PTRT_OK;
 }
 
+} // extern "C"
+
+// ray_query_kernel (pt_query.hip.h) over n rays in device memory, on the context's stream.  The traversal is the path kernel's
+// for this scene and these options: pair_mode(c, geom, false), the (ray, mesh) pair walk wherever [B] / [D] use one, one ray
+// per lane where they do not.  A persistent grid: about one 64-thread workgroup per wave slot of the chip.
+template <int GEOM, int PMODE, int KIND>
+int run_query(ptrt_ctx *c, const pt::KParams &K, size_t lds, const float *o, const float *d, const float *tmax, size_t n, void *out) {
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt::ray_query_kernel<GEOM, PMODE, KIND>, 64, lds));
+    const size_t chunks = (n + 63) / 64, slots = (size_t)(c->n_cus > 0 ? c->n_cus : 1) * (size_t)(per_cu > 0 ? per_cu : 1);
+    const unsigned grid = (unsigned)(chunks < slots ? chunks : slots);
+    hipLaunchKernelGGL((pt::ray_query_kernel<GEOM, PMODE, KIND>), dim3(grid), dim3(64), lds, c->stream, K, o, d, tmax, n, out);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+template <int KIND>
+int dispatch_query(ptrt_ctx *c, int geom, int pmode, const pt::KParams &K, size_t lds, const float *o, const float *d,
+                   const float *tmax, size_t n, void *out) {
+    switch (pmode) { // (the pair walks do not depend on GEOM: one instantiation each)
+    case 1: return run_query<0, 1, KIND>(c, K, lds, o, d, tmax, n, out);
+    case 2: return run_query<1, 2, KIND>(c, K, lds, o, d, tmax, n, out);
+    case 3: return run_query<2, 3, KIND>(c, K, lds, o, d, tmax, n, out);
+    default: break;
+    }
+    if (geom == 0)
+        return run_query<0, 0, KIND>(c, K, lds, o, d, tmax, n, out);
+    if (geom == 1)
+        return run_query<1, 0, KIND>(c, K, lds, o, d, tmax, n, out);
+    return run_query<2, 0, KIND>(c, K, lds, o, d, tmax, n, out);
+}
+int launch_query(ptrt_ctx *c, int kind, const float *o, const float *d, const float *tmax, size_t n, void *out) {
+    const pt::KParams K = make_params(c);
+    const int geom = pick_geom(c);
+    const int pmode = pair_mode(c, geom, false);
+    c->query_pmode = pmode;
+    const size_t lds = pmode ? pair_lds_bytes(c, pmode) : ((geom == 0) ? 0 : (size_t)c->stack_entries * 64 * sizeof(uint2));
+    if (pmode == 3 && !c->heads_fresh) { // the TLAS-leaf-order heads, as ptrt_render gathers them
+        c->heads_fresh = true;
+        hipLaunchKernelGGL(pt::gather_tlas_heads_kernel, dim3((c->n_tlas_index + 63) / 64), dim3(64), 0, c->stream,
+                           c->d_mesh_recs, c->d_inst_pre, c->d_tlas_mesh_ids, c->n_tlas_index, c->d_tlas_heads,
+                           c->inst_pre_ok ? 1 : 0);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return kind == PTRT_QUERY_CLOSEST ? dispatch_query<pt::QUERY_CLOSEST>(c, geom, pmode, K, lds, o, d, tmax, n, out)
+                                      : dispatch_query<pt::QUERY_OCCLUDED>(c, geom, pmode, K, lds, o, d, tmax, n, out);
+}
+
+// `bytes` of device memory at p, all inside one allocation on the context's device
+bool device_span(ptrt_ctx *c, const void *p, size_t bytes) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError(); // (memory HIP has never seen: an error it would report again later)
+        return false;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != c->device)
+        return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const size_t off = (size_t)((const char *)p - (const char *)base);
+    return off <= size && bytes <= size - off;
+}
+
+extern "C" {
+
 int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, int n, ptrt_hit *out) {
     static_assert(sizeof(pt::HitOut) == sizeof(ptrt_hit), "HitOut must mirror ptrt_hit");
     if (!ctx_live(c) || !origins || !directions || !out || n < 0)
@@ -3071,6 +3141,7 @@ int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, 
         return PTRT_OK;
     if (int rc = set_device(c))
         return rc;
+    // host staging around the CLOSEST query of ptrt_query_rays
     float *d_o = nullptr, *d_d = nullptr;
     pt::HitOut *d_h = nullptr;
     int rc = PTRT_OK;
@@ -3083,22 +3154,11 @@ int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, 
         e = hipMemcpyAsync(d_o, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(d_d, directions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        pt::KParams K = make_params(c);
-        const int geom = pick_geom(c);
-        const size_t lds = (geom == 0) ? 0 : (size_t)c->stack_entries * 64 * sizeof(uint2);
-        const int grid = (n + 63) / 64;
-        if (geom == 0)
-            hipLaunchKernelGGL(pt::trace_rays_kernel<0>, dim3(grid), dim3(64), lds, c->stream, K, d_o, d_d, n, d_h);
-        else if (geom == 1)
-            hipLaunchKernelGGL(pt::trace_rays_kernel<1>, dim3(grid), dim3(64), lds, c->stream, K, d_o, d_d, n, d_h);
-        else
-            hipLaunchKernelGGL(pt::trace_rays_kernel<2>, dim3(grid), dim3(64), lds, c->stream, K, d_o, d_d, n, d_h);
-        e = hipGetLastError();
-    }
     if (e == hipSuccess)
+        rc = launch_query(c, PTRT_QUERY_CLOSEST, d_o, d_d, nullptr, (size_t)n, d_h);
+    if (e == hipSuccess && rc == PTRT_OK)
         e = hipMemcpyAsync(out, d_h, (size_t)n * sizeof(pt::HitOut), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess)
+    if (e == hipSuccess && rc == PTRT_OK)
         e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess)
         rc = fail(c, PTRT_E_HIP, "ptrt_trace_rays: %s", hipGetErrorString(e));
@@ -3106,6 +3166,38 @@ int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, 
     (void)hipFree(d_d);
     (void)hipFree(d_h);
     return rc;
+}
+
+int ptrt_query_rays(ptrt_ctx *c, int kind, const float *origins, const float *directions, const float *tmax, int n, void *out) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: bad context");
+    if (kind != PTRT_QUERY_CLOSEST && kind != PTRT_QUERY_OCCLUDED)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: kind %d (PTRT_QUERY_CLOSEST or PTRT_QUERY_OCCLUDED)", kind);
+    if (n < 0 || !origins || !directions || !out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: bad argument (n %d, origins %p, directions %p, out %p)", n,
+                    (const void *)origins, (const void *)directions, out);
+    if (kind == PTRT_QUERY_OCCLUDED && !tmax)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: PTRT_QUERY_OCCLUDED needs tmax");
+    if (kind == PTRT_QUERY_CLOSEST && tmax)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: PTRT_QUERY_CLOSEST takes no tmax (pass NULL)");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_rays: geometry not uploaded");
+    if (n == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const size_t rays = (size_t)n, rec = kind == PTRT_QUERY_CLOSEST ? sizeof(pt::HitOut) : sizeof(int32_t);
+    const char *bad = !device_span(c, origins, rays * 12)                        ? "origins"
+                      : !device_span(c, directions, rays * 12)                   ? "directions"
+                      : (tmax && !device_span(c, tmax, rays * sizeof(float)))    ? "tmax"
+                      : !device_span(c, out, rays * rec)                         ? "out"
+                                                                                 : nullptr;
+    if (bad)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: %s is not %zu bytes of device memory on device %d", bad,
+                    rays * (bad[0] == 't' ? sizeof(float) : bad[0] == 'o' && bad[1] == 'u' ? rec : 12), c->device);
+    // a path frame that follows is ordered behind the query on the stream, as behind the wireframe view (option "pipeline")
+    c->touched = true;
+    return launch_query(c, kind, origins, directions, tmax, rays, out);
 }
 
 int ptrt_render_wireframe(ptrt_ctx *c, float thickness, void *out_rgb8, int out_is_device) {
@@ -3306,6 +3398,8 @@ int ptrt_get_option(ptrt_ctx *c, const char *name, long long *value) {
         {"merged_eff", c->merged_eff},   // loop shape of the last launch (1 = shadow rays ride with the next extension rays)
         {"merged_decided", (c->merged >= 0 || c->tune_choice >= 0 || !c->last_merged_possible) ? 1 : 0}, // 0 while "merged" = -1 is still sampling
         {"launches", (long long)c->launches},
+        {"query_pmode", c->query_pmode}, // traversal of the last ptrt_query_rays / ptrt_trace_rays: 0 one ray per lane, 1..3 pairs
+        {"stream", (long long)(intptr_t)c->stream}, // the hipStream_t the context enqueues on (stream-ordering its device results)
     };
     for (const auto &e : tab)
         if (n == e.first) {

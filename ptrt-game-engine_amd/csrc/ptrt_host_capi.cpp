@@ -347,6 +347,16 @@ int hs_render_wireframe_to_device(void *s, void *device_pixels, float thickness)
     HS_TRY(static_cast<Scene *>(s)->render_to_device_wireframe(static_cast<unsigned char *>(device_pixels), thickness));
     return 0;
 }
+int hs_query_closest(void *s, const void *d_origins, const void *d_dirs, int n, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryClosestDevice(static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n,
+                                                       static_cast<ptrt_hit *>(d_out)));
+    return 0;
+}
+int hs_query_occluded(void *s, const void *d_origins, const void *d_dirs, const void *d_tmax, int n, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryOccludedDevice(static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs),
+                                                        static_cast<const float *>(d_tmax), n, static_cast<int32_t *>(d_out)));
+    return 0;
+}
 int hs_render_wireframe_to_host(void *s, void *host_pixels, float thickness) {
     HS_TRY(static_cast<Scene *>(s)->render_wireframe_to_host(static_cast<unsigned char *>(host_pixels), thickness));
     return 0;

@@ -853,6 +853,21 @@ class Scene {
         return h;
     }
 
+    // NOT in the reference, which answers one ray per call (traceSingleRay): batched ray queries on device memory
+    // (ptrt_query_rays).  Pending object and instance changes are committed first, as a render commits them, so a query
+    // sees the geometry the next frame traces.  Enqueued on the back end's stream; no synchronisation.
+    // d_origins / d_dirs: n * 3 floats; d_out: n records (closest hit) or n flags (1 = blocked before d_tmax[i]).
+    void queryClosestDevice(const float *d_origins, const float *d_dirs, int n, ptrt_hit *d_out) {
+        needBackend();
+        updateAccelerationStructures();
+        check(ptrt_query_rays(ctx, PTRT_QUERY_CLOSEST, d_origins, d_dirs, nullptr, n, d_out), "Closest-hit query failed");
+    }
+    void queryOccludedDevice(const float *d_origins, const float *d_dirs, const float *d_tmax, int n, int32_t *d_out) {
+        needBackend();
+        updateAccelerationStructures();
+        check(ptrt_query_rays(ctx, PTRT_QUERY_OCCLUDED, d_origins, d_dirs, d_tmax, n, d_out), "Occlusion query failed");
+    }
+
     void saveAsPPM(const std::string &filename, unsigned char *pixels) const { // ASCII P3, scene.cuh:1694-1708
         std::ofstream ofs(filename, std::ios::binary);
         if (!ofs)

@@ -39,6 +39,7 @@ PTRT_OK = 0
 BUF_ACCUM, BUF_NORMAL, BUF_DEPTH, BUF_OBJECT_ID, BUF_RGB8, BUF_RNG, BUF_DENOISED, BUF_MOTION, BUF_RENDER_ACCUM = range(9)
 DEFAULT_SEED = 12345
 HOST_ONLY = -1
+QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1  # ptrt_query_rays kinds
 
 
 class Vec3(C.Structure):
@@ -144,6 +145,7 @@ _sig("ptrt_device_buffer", _vp, _vp, C.c_int)
 _sig("ptrt_write_rng", C.c_int, _vp, C.POINTER(C.c_uint32), C.c_size_t)
 _sig("ptrt_trace_rays", C.c_int, _vp, _fp, _fp, C.c_int, _vp)
 _sig("ptrt_render_wireframe", C.c_int, _vp, C.c_float, _vp, C.c_int)
+_sig("ptrt_query_rays", C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
 _sig("ptrt_set_option", C.c_int, _vp, C.c_char_p, C.c_longlong)
 _sig("ptrt_get_option", C.c_int, _vp, C.c_char_p, C.POINTER(C.c_longlong))
@@ -252,6 +254,8 @@ _sig("hs_render_to_device", C.c_int, _vp, _vp)
 _sig("hs_render_to_host", C.c_int, _vp, _vp)
 _sig("hs_render_wireframe_to_device", C.c_int, _vp, _vp, C.c_float)
 _sig("hs_render_wireframe_to_host", C.c_int, _vp, _vp, C.c_float)
+_sig("hs_query_closest", C.c_int, _vp, _vp, _vp, C.c_int, _vp)
+_sig("hs_query_occluded", C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
 _sig("hs_get_frame_count", C.c_int, _vp)
 _sig("hs_set_frame_count", None, _vp, C.c_int)
@@ -318,6 +322,27 @@ def blue_noise_table():
     t = np.zeros(64 * 64 * 2, dtype=np.float32)
     lib.hs_blue_noise_table(_fptr(t))
     return t
+
+
+def _is_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+# columns of the (n, 16) int32 rows of Scene.query_closest on torch tensors: the fields of ptrt_hit / HIT_DTYPE
+HIT_COLUMNS = dict(hit=(0, 1, False), t=(1, 2, True), point=(2, 5, True), normal=(5, 8, True), mesh_index=(8, 9, False),
+                   front_face=(9, 10, False), u=(10, 11, True), v=(11, 12, True), face_index=(12, 13, False),
+                   local_point=(13, 16, True))
+
+
+def hit_fields(hits):
+    """Named views of query_closest's (n, 16) int32 tensor: float fields reinterpreted as float32, scalars as (n,)."""
+    import torch
+    f = hits.view(torch.float32)
+    out = {}
+    for name, (a, b, is_f) in HIT_COLUMNS.items():
+        col = (f if is_f else hits)[:, a:b]
+        out[name] = col[:, 0] if b - a == 1 else col
+    return out
 
 
 class Scene:
@@ -649,6 +674,79 @@ class Scene:
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         out = np.zeros(o.shape[0], dtype=HIT_DTYPE)
         self._cchk(lib.ptrt_trace_rays(self.ctx, _fptr(o), _fptr(d), o.shape[0], out.ctypes.data_as(_vp)))
+        return out
+
+    # ---- batched ray queries (ptrt_query_rays through Scene::queryClosestDevice / queryOccludedDevice) ----
+    def query_closest(self, origins, directions):
+        """Closest hit of every ray.  torch tensors on this scene's device -- float32, contiguous, (n, 3) -- are read in place
+        and the answer is an (n, 16) int32 tensor, one 64-byte `ptrt_hit` per row (`hit_fields` names its columns); numpy
+        arrays are staged through the device and the answer is a numpy array of HIT_DTYPE, the record of `trace_rays`."""
+        return self._query(origins, directions, None)
+
+    def query_occluded(self, origins, directions, tmax):
+        """1 where something blocks the ray before `tmax` (the reference's shadow query; glass, transmission > 0.5, never
+        blocks), else 0: an (n,) int32 tensor for torch inputs, a numpy array for numpy inputs.  `tmax`: (n,) float32."""
+        if tmax is None:
+            raise ValueError("query_occluded needs tmax")
+        return self._query(origins, directions, tmax)
+
+    def _query(self, origins, directions, tmax):
+        arrays = [origins, directions] + ([] if tmax is None else [tmax])
+        shapes = [(3,), (3,), ()]
+        is_t = [_is_tensor(a) for a in arrays]
+        if any(is_t) and not all(is_t):
+            raise ValueError("ray query: pass all torch tensors or all numpy arrays")
+        n = None
+        for a, tail in zip(arrays, shapes):
+            if not is_t[0] and not isinstance(a, np.ndarray):
+                raise ValueError(f"ray query: expected a numpy array or a torch tensor, got {type(a).__name__}")
+            if tuple(a.shape[1:]) != tail or a.ndim != 1 + len(tail):
+                raise ValueError(f"ray query: shape {tuple(a.shape)}, expected (n, {tail[0]})" if tail else
+                                 f"ray query: tmax shape {tuple(a.shape)}, expected (n,)")
+            n = a.shape[0] if n is None else n
+            if a.shape[0] != n:
+                raise ValueError(f"ray query: {n} origins but {a.shape[0]} rows in another input")
+            if (str(a.dtype) != "torch.float32") if is_t[0] else (a.dtype != np.float32):
+                raise ValueError(f"ray query: dtype {a.dtype}, expected float32")
+        if n >= 2 ** 31:
+            raise ValueError(f"ray query: {n} rays (at most 2^31 - 1 per call)")
+        closest = tmax is None
+        for a in arrays if is_t[0] else []:
+            if a.device.type != "cuda" or a.device.index != self.device:
+                raise ValueError(f"ray query: tensor on {a.device}, this scene renders on " +
+                                 (f"cuda:{self.device}" if self.device >= 0 else "no device (host-only)"))
+            if not a.is_contiguous():
+                raise ValueError("ray query: tensors must be contiguous")
+        if self.device < 0:  # host-only: the mirror refuses (PtrtError) before it looks at the arguments
+            self._chk(lib.hs_query_closest(self._h, None, None, n, None) if closest else
+                      lib.hs_query_occluded(self._h, None, None, None, n, None))
+        import torch
+        if not is_t[0]:
+            dev = torch.device("cuda", self.device)
+            staged = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays]
+            out = self._query_tensors(torch, staged, n, closest).cpu().numpy()
+            return out.view(HIT_DTYPE).reshape(n) if closest else out
+        return self._query_tensors(torch, arrays, n, closest)
+
+    def _query_tensors(self, torch, arrays, n, closest):
+        dev = arrays[0].device
+        out = torch.empty((n, 16) if closest else (n,), dtype=torch.int32, device=dev)
+        if n == 0:
+            return out
+        # stream order both ways, by events: the context's stream waits for what torch enqueued before the call (the rays),
+        # torch's current stream for the query (whoever reads the answer)
+        cur = torch.cuda.current_stream(dev)
+        ctx_stream = torch.cuda.ExternalStream(self.get_option("stream"), device=dev)
+        other = ctx_stream.cuda_stream != cur.cuda_stream
+        if other:
+            ctx_stream.wait_stream(cur)
+        p = [_vp(a.data_ptr()) for a in arrays]
+        if closest:
+            self._chk(lib.hs_query_closest(self._h, p[0], p[1], n, _vp(out.data_ptr())))
+        else:
+            self._chk(lib.hs_query_occluded(self._h, p[0], p[1], p[2], n, _vp(out.data_ptr())))
+        if other:
+            cur.wait_stream(ctx_stream)
         return out
 
     def traceSingleRay(self, origin, direction):
