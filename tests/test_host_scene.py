@@ -61,13 +61,26 @@ def test_sphere_counts_and_plane(P):
     assert np.allclose(r, 0.5, atol=1e-6)
 
 
+def _invariant_scene(P, s, name):
+    if name == "showcase":
+        P.scenes.showcase(s, segments=10)
+    elif name == "fluid":
+        P.scenes.fluid(s, cells=24, t=0.3, ship_segments=10)
+    else:
+        P.scenes.many(s, 40)
+
+
 @pytest.mark.parametrize("leaf", [(12, 5), (4, 0), (1, 0)])
 def test_bvh_invariants(P, leaf):
-    s = P.Scene(32, 32, device=P.HOST_ONLY)
-    P.scenes.showcase(s, segments=10)
-    s.setBVHLeafTarget(*leaf)
-    d = s.flatten()
-    leaf_max = leaf[0] + leaf[1]
+    for name in ("showcase", "fluid", "many"):
+        s = P.Scene(32, 32, device=P.HOST_ONLY)
+        _invariant_scene(P, s, name)
+        s.setBVHLeafTarget(*leaf)
+        _check_bvh_invariants(s.flatten(), leaf[0] + leaf[1])
+
+
+def _check_bvh_invariants(d, leaf_max):
+    roots = []
     for m in range(d.contents.mesh_count):
         v, f, nodes, prims, M = np_mesh(d, m)
         assert sorted(prims.tolist()) == list(range(len(f)))            # a permutation of the faces
@@ -90,9 +103,38 @@ def test_bvh_invariants(P, leaf):
                     stack.append((ch, depth + 1))
             assert depth <= 23
         assert seen.all()
-    # TLAS covers every mesh exactly once
+        # the world-space corners of the root box: what the TLAS has to cover (the WORLD matrix, whatever the stored inverse is)
+        lo, hi = boxes[0, :3].astype(np.float64), boxes[0, 3:].astype(np.float64)
+        corners = np.array([[(lo, hi)[(k >> a) & 1][a] for a in range(3)] for k in range(8)])
+        if M.has_transform:
+            w = np.array(list(M.world), np.float32).astype(np.float64).reshape(4, 4)
+            corners = corners @ w[:3, :3].T + w[:3, 3]
+        roots.append(corners)
+    # TLAS: every mesh in exactly one leaf, every leaf box contains its meshes' root boxes, children inside parents, depth <= 23
     ids = np.ctypeslib.as_array(d.contents.tlas_mesh_indices, (d.contents.tlas_index_count,))
     assert sorted(ids.tolist()) == list(range(d.contents.mesh_count))
+    n = d.contents.tlas_node_count
+    raw = np.ctypeslib.as_array(C.cast(d.contents.tlas_nodes, C.POINTER(C.c_float)), (n, 10)).copy()
+    boxes, links = raw[:, :6].astype(np.float64), raw[:, 6:].view(np.int32)
+    seen, listed = np.zeros(n, bool), []
+    stack = [(0, 0)]
+    while stack:
+        i, depth = stack.pop()
+        assert not seen[i] and depth <= 23
+        seen[i] = True
+        left, right, start, count = links[i]
+        if count > 0:
+            assert count <= leaf_max and left == -1 and right == -1
+            for m in ids[start:start + count]:
+                listed.append(int(m))
+                slack = 4e-7 * np.abs(roots[m]).max()                        # the builder rounds the corners to float32
+                assert np.all(roots[m] >= boxes[i, :3] - slack) and np.all(roots[m] <= boxes[i, 3:] + slack), (i, m)
+        else:
+            assert left >= 0 and right >= 0
+            for ch in (left, right):
+                assert np.all(boxes[ch, :3] >= boxes[i, :3]) and np.all(boxes[ch, 3:] <= boxes[i, 3:])
+                stack.append((ch, depth + 1))
+    assert seen.all() and sorted(listed) == list(range(d.contents.mesh_count))
 
 
 def test_has_transform_flag_and_matrices(P):
