@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history (addition only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
+#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
 
 enum {
     PTRT_OK = 0,
@@ -264,8 +264,9 @@ int ptrt_set_env_map(ptrt_ctx *ctx, const float *rgba, int width, int height);
  * the triangle packets, every leaf and inner box of the dirty meshes (bottom-up over the
  * UNCHANGED tree), the mesh root boxes and the TLAS root box.  No host synchronisation.
  * With a TLAS that has inner nodes (more meshes than one TLAS leaf holds) the TLAS itself is left to the
- * caller: rebuild it over the moved meshes' boxes, as the reference's commit does, and hand it to
- * ptrt_update_instances (the Scene mirror's refitObjectChanges / rebuildObjectChanges do).  A refitted tree has the boxes a
+ * caller: follow with ptrt_refit_tlas(), which refits it on the device over the uploaded topology -- or rebuild it over
+ * the moved meshes' boxes, as the reference's commit does, and hand it to ptrt_update_instances (the Scene mirror's
+ * refitObjectChanges / rebuildObjectChanges do).  A refitted tree has the boxes a
  * host refit of the same topology gives (min/max are exact), so results stay bit-comparable
  * with the oracle run on those arrays; it is NOT the tree a fresh median-split build would give.
  * Host positions (verts_on_device == 0): the caller's buffer is its own again when the call returns, and the call does NOT
@@ -284,11 +285,41 @@ int ptrt_refit(ptrt_ctx *ctx);
  * leaf positions in Morton order of their current centroids (30-bit codes, stable radix sort on
  * the GPU), followed by ptrt_refit().  All on the context's stream, nothing returns to the host.
  * Depth and leaf sizes are the uploaded tree's, so the 24-entry stack bound keeps holding.
- * Needs: every face of the mesh in exactly one leaf position (any tree Mesh::buildBVH makes),
- * single-leaf TLAS.  ptrt_read_prim_order returns the resulting `primIndices` (mesh.cuh:57) so a
+ * Needs: every face of the mesh in exactly one leaf position (any tree Mesh::buildBVH makes).
+ * Behind a TLAS with inner nodes the mesh's new root box reaches the TLAS with ptrt_refit_tlas() (or a host rebuild
+ * handed to ptrt_update_instances), as after ptrt_refit; the build itself never depended on the TLAS' shape.
+ * ptrt_read_prim_order returns the resulting `primIndices` (mesh.cuh:57) so a
  * host copy of the tree (and the oracle) can follow. */
 int ptrt_build_bvh(ptrt_ctx *ctx, int mesh_index);
 int ptrt_read_prim_order(ptrt_ctx *ctx, int mesh_index, int32_t *prim_indices_out, int count);
+
+/* Moving instances and meshes behind ANY TLAS without a host round trip (not in the reference, which rebuilds the TLAS on
+ * the CPU: scene.cuh:458-594).  The TLAS topology that was uploaded -- child pairs, leaf ranges, mesh indices -- is kept;
+ * its boxes are refitted on the device.  A frame's order: any ptrt_update_vertices / ptrt_refit / ptrt_build_bvh, then any
+ * ptrt_set_instance_transforms, then ONE ptrt_refit_tlas.  All three are ABI 6 additions.
+ *
+ * ptrt_set_instance_transforms: the has_transform bit and the world / inverse / normal rows of meshes [first_mesh,
+ * first_mesh + count), the fields ptrt_update_instances reads from a descriptor, from HOST memory that is the caller's again
+ * on return (pinned staging of the context; the copy and a scatter kernel run on the stream).  No stream synchronisation,
+ * no allocation after the first call, root boxes untouched.  A flag that changes the traversal variant takes effect with
+ * the next launch.  PTRT_E_INVALID (nothing enqueued) for a range outside the uploaded meshes, a negative count or NULL.
+ *
+ * ptrt_refit_tlas: one launch on the stream (two beyond 4096 meshes) -- every mesh's world box from the root box the
+ * DEVICE holds and its world rows (Transform3D::transformAABB's arithmetic), every TLAS leaf box, the inner levels deepest
+ * first, the TLAS root box, and the instances' world-space first-pass boxes (PMODE 3), which a ptrt_refit / ptrt_build_bvh
+ * / ptrt_set_instance_transforms had invalidated.  The boxes equal a host refit over the same topology bit for bit.  Works
+ * for a single-leaf TLAS too.  A refitted TLAS degrades as instances travel (far-apart members of a leaf, overlapping
+ * boxes): ptrt_update_instances with a rebuilt TLAS gives a fresh topology.
+ *
+ * ptrt_read_tlas: synchronises; the uploaded nodes' left / right / start / count with the boxes the device holds now
+ * (the counterpart of ptrt_read_prim_order).  PTRT_E_INVALID unless node_count is the uploaded node count. */
+typedef struct ptrt_instance_xform {
+    float world[16], inverse[16], normal[16]; /* as in ptrt_mesh_desc */
+    int32_t has_transform;
+} ptrt_instance_xform;
+int ptrt_set_instance_transforms(ptrt_ctx *ctx, int first_mesh, int count, const ptrt_instance_xform *xf);
+int ptrt_refit_tlas(ptrt_ctx *ctx);
+int ptrt_read_tlas(ptrt_ctx *ctx, ptrt_bvh_node *nodes_out, int node_count);
 
 /* The `Triangles` path of updatePTScene with a CHANGING triangle count (PTRTtransfer.cuh:2204-2385:
  * a new triangle list every frame, e.g. a fluid surface).  For a triangle-soup mesh (face i =

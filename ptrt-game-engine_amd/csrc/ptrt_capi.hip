@@ -11,6 +11,7 @@
 #include "pt_denoise.hip.h"
 #include "pt_post.hip.h"
 #include "pt_refit.hip.h"
+#include "pt_tlas.hip.h"
 #include "pt_render.hip.h"
 #include "pt_wavefront.hip.h"
 #include "pt_async.hip.h"
@@ -91,6 +92,21 @@ struct ptrt_ctx {
     int n_meshes = 0, n_materials = 0, n_lights = 0;
     float4 *d_tlas_root_box = nullptr; // {bmin, bmax}
     int tlas_root_ref = 0;
+    // TLAS refit support (ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, pt_tlas.hip.h)
+    int *d_tlas_refit = nullptr;        // {per leaf: where its box is stored | per inner node: the same | inner nodes by depth}
+    float4 *d_tlas_world = nullptr;     // scratch: per TLAS index the mesh's world box
+    int n_tlas_leaves = 0, n_tlas_inner = 0, tlas_world_cap = 0;
+    pt::TopLevels tlas_levels{};        // the inner levels, deepest first, as offsets into the third part of d_tlas_refit
+    std::vector<ptrt_bvh_node> h_tlas_in; // the TLAS as it was uploaded ...
+    std::vector<int> h_tlas_in_dst;       // ... and where the device keeps each of its nodes' boxes (INT32_MIN: nowhere)
+    int tlas_refits = 0;                // ptrt_refit_tlas calls since the last geometry upload
+    bool inst_c2_all = false;           // inst_c2 covers every instance's matrices (host_inst_c2), not only the upload's finite boxes
+    // staged instance transforms: two halves of pinned host / device memory, each waited for when it comes round again
+    float *h_xf = nullptr, *d_xf = nullptr;
+    size_t xf_cap = 0, xf_used[2] = {0, 0}; // records per half / handed out of each
+    int xf_cur = 0;
+    hipEvent_t xf_ev[2] = {nullptr, nullptr};
+    bool xf_pending[2] = {false, false};
     // refit support (ptrt_update_vertices / ptrt_refit)
     float *d_verts = nullptr;       // all meshes' vertices, xyz packed
     int4 *d_slot_face = nullptr;    // per leaf slot: global vertex indices + face index
@@ -393,7 +409,7 @@ struct Relayout {
 template <class EmitLeaf>
 int convert_tree(const ptrt_bvh_node *in, int n_in, std::vector<float4> &out_nodes, EmitLeaf emit_leaf, int &max_depth,
                  std::string &why, int root_dst = -1, std::vector<int> *node_dst = nullptr,
-                 std::vector<int> *node_depth = nullptr) {
+                 std::vector<int> *node_depth = nullptr, std::vector<int> *old_dst = nullptr) {
     struct Item {
         int old_idx, new_idx, depth;
     };
@@ -414,6 +430,8 @@ int convert_tree(const ptrt_bvh_node *in, int n_in, std::vector<float4> &out_nod
             return INT32_MIN;
         }
         seen[old_idx] = 1;
+        if (old_dst)
+            (*old_dst)[old_idx] = dst; // (`old_dst`, optional, sized n_in: the code of every input node that was reached)
         const ptrt_bvh_node &N = in[old_idx];
         if (N.count > 0)
             return ~emit_leaf(N.start, N.count, dst);
@@ -479,16 +497,18 @@ int upload_tlas(ptrt_ctx *c, int mesh_count, const ptrt_bvh_node *tlas_nodes, in
     std::vector<int2> tleaves;
     bool bad = false;
     std::string why;
-    auto emit_tleaf = [&](int start, int count, int) -> int {
+    std::vector<int> leaf_dst, node_dst, node_depth, in_dst((size_t)tlas_node_count, INT32_MIN);
+    auto emit_tleaf = [&](int start, int count, int dst) -> int {
         if (count > 0 && (start < 0 || start + count > tlas_index_count)) {
             bad = true;
             count = 0;
         }
         tleaves.push_back(make_int2(start < 0 ? 0 : start, count));
+        leaf_dst.push_back(dst);
         return (int)tleaves.size() - 1;
     };
     int tdepth = 0;
-    const int troot = convert_tree(tlas_nodes, tlas_node_count, tnodes, emit_tleaf, tdepth, why);
+    const int troot = convert_tree(tlas_nodes, tlas_node_count, tnodes, emit_tleaf, tdepth, why, -1, &node_dst, &node_depth, &in_dst);
     if (troot == INT32_MIN || bad)
         return fail(c, PTRT_E_INVALID, "malformed TLAS (%s)", bad ? "leaf range out of bounds" : why.c_str());
     if (tdepth > 23)
@@ -511,6 +531,35 @@ int upload_tlas(ptrt_ctx *c, int mesh_count, const ptrt_bvh_node *tlas_nodes, in
         return rc;
     dfree(c->d_tlas_heads);
     HIP_TRY(c, hipMalloc((void **)&c->d_tlas_heads, (size_t)tlas_index_count * pt::TLAS_HEAD_F4 * sizeof(float4)));
+    // what a refit over this topology needs (pt_tlas.hip.h): the dst codes and the inner nodes level by level, deepest first
+    const int n_inner = (int)node_dst.size();
+    std::vector<int> refit(leaf_dst);
+    refit.insert(refit.end(), node_dst.begin(), node_dst.end());
+    c->tlas_levels = pt::TopLevels{};
+    for (int d = tdepth; d >= 1; --d) {
+        const int begin = (int)refit.size() - (int)leaf_dst.size() - n_inner;
+        for (int n = 0; n < n_inner; ++n)
+            if (node_depth[n] == d)
+                refit.push_back(n);
+        const int count = (int)refit.size() - (int)leaf_dst.size() - n_inner - begin;
+        if (count > 0) { // (tdepth <= 23 was checked above: at most 23 entries of 24)
+            c->tlas_levels.begin[c->tlas_levels.n] = begin;
+            c->tlas_levels.count[c->tlas_levels.n] = count;
+            ++c->tlas_levels.n;
+        }
+    }
+    if (int rc = upload(c, c->d_tlas_refit, refit))
+        return rc;
+    if (tlas_index_count > c->tlas_world_cap) {
+        dfree(c->d_tlas_world);
+        c->tlas_world_cap = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_tlas_world, (size_t)tlas_index_count * 2 * sizeof(float4)));
+        c->tlas_world_cap = tlas_index_count;
+    }
+    c->n_tlas_leaves = (int)leaf_dst.size();
+    c->n_tlas_inner = n_inner;
+    c->h_tlas_in.assign(tlas_nodes, tlas_nodes + tlas_node_count);
+    c->h_tlas_in_dst = in_dst;
     c->n_tlas_index = tlas_index_count;
     c->tlas_root_ref = troot;
     c->tlas_single_leaf = troot < 0;
@@ -538,6 +587,9 @@ void free_scene(ptrt_ctx *c) {
     dfree(c->d_tlas_heads);
     dfree(c->d_inst_pre);
     dfree(c->d_tlas_root_box);
+    dfree(c->d_tlas_refit);
+    dfree(c->d_tlas_world);
+    c->tlas_world_cap = 0;
     dfree(c->d_verts);
     dfree(c->d_slot_face);
     dfree(c->d_leaf_dst);
@@ -1345,6 +1397,12 @@ void ptrt_destroy(ptrt_ctx *c) {
             (void)hipEventDestroy(c->stage_ev[k]);
         dfree(c->d_stage[k]);
     }
+    if (c->h_xf)
+        (void)hipHostFree(c->h_xf);
+    dfree(c->d_xf);
+    for (int k = 0; k < 2; ++k)
+        if (c->xf_ev[k])
+            (void)hipEventDestroy(c->xf_ev[k]);
     if (c->copy_stream)
         (void)hipStreamDestroy(c->copy_stream);
     if (c->copy_ev)
@@ -1611,6 +1669,7 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
     if (int rc = upload_tlas(c, mesh_count, tlas_nodes, tlas_node_count, tlas_mesh_indices, tlas_index_count, false))
         return rc;
     c->n_geometry_uploads++;
+    c->tlas_refits = 0;
     c->all_single_leaf = all_leaf;
     c->any_transform = false;
     for (int m = 0; m < mesh_count; ++m)
@@ -1717,6 +1776,7 @@ int upload_instance_pretests(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh
                                      std::nextafterf((float)(wmax[2] + C1), INFINITY), 0.0f);
     }
     c->inst_c2 = std::nextafterf((float)c2max, INFINITY);
+    c->inst_c2_all = false;
     if (int rc = upload(c, c->d_inst_pre, pre))
         return rc;
     c->inst_pre_ok = true;
@@ -1774,6 +1834,192 @@ int ptrt_update_instances(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_co
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (int rc = upload_instance_pretests(c, meshes, mesh_count, dev_recs.data()))
         return rc;
+    return PTRT_OK;
+}
+
+// The growth factor C2 of the instances' first-pass boxes (see upload_instance_pretests) from the matrices alone, over
+// EVERY mesh of h_mesh_recs that is an instance: an upper bound of what the device derives per instance in
+// pt::instance_pretest, which gives an instance whose own factor exceeds the value handed to it the infinite box.
+float host_inst_c2(const ptrt_ctx *c) {
+    double c2max = 0.0;
+    for (int m = 0; m < c->n_meshes; ++m) {
+        const float4 *rec = &c->h_mesh_recs[(size_t)m * pt::MESH_REC_F4];
+        int flags;
+        std::memcpy(&flags, &rec[1].w, 4);
+        if (!(flags & 1))
+            continue;
+        const double A[3][3] = {{rec[2].x, rec[2].y, rec[2].z}, {rec[3].x, rec[3].y, rec[3].z}, {rec[4].x, rec[4].y, rec[4].z}};
+        const double co[3][3] = {{A[1][1] * A[2][2] - A[1][2] * A[2][1], A[0][2] * A[2][1] - A[0][1] * A[2][2], A[0][1] * A[1][2] - A[0][2] * A[1][1]},
+                                 {A[1][2] * A[2][0] - A[1][0] * A[2][2], A[0][0] * A[2][2] - A[0][2] * A[2][0], A[0][2] * A[1][0] - A[0][0] * A[1][2]},
+                                 {A[1][0] * A[2][1] - A[1][1] * A[2][0], A[0][1] * A[2][0] - A[0][0] * A[2][1], A[0][0] * A[1][1] - A[0][1] * A[1][0]}};
+        const double det = A[0][0] * co[0][0] - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) + A[0][2] * co[2][0];
+        if (!std::isfinite(det) || !(std::fabs(det) > 1e-30))
+            continue; // (infinite box on the device too)
+        double nA = 0.0, nI = 0.0;
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 3; ++k) {
+                nA += A[r][k] * A[r][k];
+                nI += (co[r][k] / det) * (co[r][k] / det);
+            }
+        const double C2 = 1e-4 * (std::sqrt(nI) * std::sqrt(nA) + 1.0) * (1.0 + 1e-9); // (a hair above the device's own rounding)
+        if (std::isfinite(C2) && C2 < 1e3)
+            c2max = std::fmax(c2max, C2);
+    }
+    return std::nextafterf((float)c2max, INFINITY);
+}
+
+// inst_c2 is an argument of the TLAS refit: a captured launch sequence holds the old value
+void set_inst_c2(ptrt_ctx *c, float v) {
+    if (v != c->inst_c2 || !c->inst_c2_all) {
+        auto it = c->graphs.find(-2);
+        if (it != c->graphs.end()) {
+            (void)hipGraphExecDestroy(it->second);
+            c->graphs.erase(it);
+        }
+    }
+    c->inst_c2 = v;
+    c->inst_c2_all = true;
+}
+
+int ptrt_set_instance_transforms(ptrt_ctx *c, int first_mesh, int count, const ptrt_instance_xform *xf) {
+    if (!ctx_live(c))
+        return fail(c, PTRT_E_INVALID, "ptrt_set_instance_transforms: bad context");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_set_instance_transforms: geometry not uploaded");
+    if (!xf || count < 0 || first_mesh < 0 || first_mesh > c->n_meshes || count > c->n_meshes - first_mesh)
+        return fail(c, PTRT_E_INVALID, "ptrt_set_instance_transforms: meshes [%d, %d + %d) of %d%s", first_mesh, first_mesh, count,
+                    c->n_meshes, xf ? "" : ", NULL transforms");
+    if (count == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    // Staging (as ptrt_update_vertices stages host positions): two halves of pinned memory and a device mirror.  Calls fill the
+    // current half; when it is full the other one is taken, after the event behind the last copy out of it -- enqueued at
+    // least a half's worth of records (two frames of every mesh moving) ago.  No allocation unless the mesh count grew.
+    const size_t need = std::max<size_t>((size_t)c->n_meshes * 2, 256);
+    if (c->xf_cap < need) {
+        for (int k = 0; k < 2; ++k)
+            if (c->xf_pending[k])
+                HIP_TRY(c, hipEventSynchronize(c->xf_ev[k]));
+        if (c->h_xf)
+            HIP_TRY(c, hipHostFree(c->h_xf));
+        c->h_xf = nullptr;
+        dfree(c->d_xf);
+        c->xf_cap = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_xf, need * 2 * pt::XFORM_F * sizeof(float), hipHostMallocDefault));
+        HIP_TRY(c, hipMalloc((void **)&c->d_xf, need * 2 * pt::XFORM_F * sizeof(float)));
+        for (int k = 0; k < 2; ++k) {
+            if (!c->xf_ev[k])
+                HIP_TRY(c, hipEventCreateWithFlags(&c->xf_ev[k], hipEventDisableTiming));
+            c->xf_used[k] = 0;
+            c->xf_pending[k] = false;
+        }
+        c->xf_cap = need;
+        c->xf_cur = 0;
+    }
+    if (c->xf_used[c->xf_cur] + (size_t)count > c->xf_cap) {
+        c->xf_cur ^= 1;
+        if (c->xf_pending[c->xf_cur])
+            HIP_TRY(c, hipEventSynchronize(c->xf_ev[c->xf_cur]));
+        c->xf_pending[c->xf_cur] = false;
+        c->xf_used[c->xf_cur] = 0;
+    }
+    const int half = c->xf_cur;
+    const size_t at = ((size_t)half * c->xf_cap + c->xf_used[half]) * pt::XFORM_F;
+    float *hs = c->h_xf + at;
+    for (int i = 0; i < count; ++i) {
+        const ptrt_instance_xform &X = xf[i];
+        float4 *rec = &c->h_mesh_recs[(size_t)(first_mesh + i) * pt::MESH_REC_F4];
+        int flags;
+        std::memcpy(&flags, &rec[1].w, 4);
+        flags = (flags & ~1) | (X.has_transform ? 1 : 0);
+        rec[1].w = as_f(flags);
+        for (int r = 0; r < 3; ++r) {
+            rec[2 + r] = f4(X.inverse[r * 4], X.inverse[r * 4 + 1], X.inverse[r * 4 + 2], X.inverse[r * 4 + 3]);
+            rec[5 + r] = f4(X.world[r * 4], X.world[r * 4 + 1], X.world[r * 4 + 2], X.world[r * 4 + 3]);
+            rec[8 + r] = f4(X.normal[r * 4], X.normal[r * 4 + 1], X.normal[r * 4 + 2], 0.0f);
+        }
+        float *o = hs + (size_t)i * pt::XFORM_F;
+        o[0] = rec[1].w;
+        o[1] = o[2] = o[3] = 0.0f;
+        std::memcpy(o + 4, &rec[2], 9 * sizeof(float4));
+    }
+    c->any_transform = false;
+    for (int m = 0; m < c->n_meshes && !c->any_transform; ++m) {
+        int flags;
+        std::memcpy(&flags, &c->h_mesh_recs[(size_t)m * pt::MESH_REC_F4 + 1].w, 4);
+        c->any_transform = (flags & 1) != 0;
+    }
+    set_inst_c2(c, host_inst_c2(c));
+    c->inst_pre_ok = false; // the first-pass boxes follow with the next ptrt_refit_tlas
+    HIP_TRY(c, hipMemcpyAsync(c->d_xf + at, hs, (size_t)count * pt::XFORM_F * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(pt::scatter_xforms_kernel, dim3((count * 37 + 255) / 256), dim3(256), 0, c->stream, c->d_xf + at,
+                       c->d_mesh_recs, first_mesh, count);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->xf_ev[half], c->stream)); // (this half's records are free again behind this)
+    c->xf_pending[half] = true;
+    c->xf_used[half] += (size_t)count;
+    return PTRT_OK;
+}
+
+int enqueue_refit_tlas(ptrt_ctx *c, hipStream_t st) {
+    const int *leaf_dst = c->d_tlas_refit, *node_dst = leaf_dst + c->n_tlas_leaves, *level_nodes = node_dst + c->n_tlas_inner;
+    const bool wide = c->n_tlas_index > pt::TLAS_WIDE;
+    if (wide)
+        hipLaunchKernelGGL(pt::tlas_world_boxes_kernel, dim3((c->n_tlas_index + pt::TLAS_BLOCK - 1) / pt::TLAS_BLOCK),
+                           dim3(pt::TLAS_BLOCK), 0, st, c->d_mesh_recs, c->d_tlas_mesh_ids, c->n_tlas_index, c->inst_c2,
+                           c->d_tlas_world, c->d_inst_pre);
+    hipLaunchKernelGGL(pt::refit_tlas_kernel, dim3(1), dim3(pt::TLAS_BLOCK), 0, st, c->d_mesh_recs, c->d_tlas_mesh_ids,
+                       c->n_tlas_index, c->d_tlas_leaves, leaf_dst, c->n_tlas_leaves, level_nodes, c->tlas_levels, node_dst,
+                       c->inst_c2, wide ? 0 : 1, c->d_tlas_world, c->d_inst_pre, c->d_tlas_nodes, c->d_tlas_root_box);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_refit_tlas(ptrt_ctx *c) {
+    if (!ctx_live(c))
+        return fail(c, PTRT_E_INVALID, "ptrt_refit_tlas: bad context");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_refit_tlas: geometry not uploaded");
+    if (int rc = set_device(c))
+        return rc;
+    if (!c->inst_c2_all)
+        set_inst_c2(c, host_inst_c2(c));
+    if (int rc = run_graphed(c, -2, [c](hipStream_t st) { return enqueue_refit_tlas(c, st); }))
+        return rc;
+    c->inst_pre_ok = true;
+    c->tlas_refits++;
+    return PTRT_OK;
+}
+
+int ptrt_read_tlas(ptrt_ctx *c, ptrt_bvh_node *nodes_out, int node_count) {
+    if (!ctx_live(c) || !nodes_out)
+        return fail(c, PTRT_E_INVALID, "ptrt_read_tlas: bad argument");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_read_tlas: geometry not uploaded");
+    if (node_count != (int)c->h_tlas_in.size())
+        return fail(c, PTRT_E_INVALID, "ptrt_read_tlas: the uploaded TLAS has %d nodes, asked for %d", (int)c->h_tlas_in.size(),
+                    node_count);
+    if (int rc = set_device(c))
+        return rc;
+    std::vector<float4> nodes((size_t)c->n_tlas_inner * 4), root(2);
+    if (!nodes.empty())
+        HIP_TRY(c, hipMemcpyAsync(nodes.data(), c->d_tlas_nodes, nodes.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(root.data(), c->d_tlas_root_box, 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < node_count; ++i) {
+        ptrt_bvh_node N = c->h_tlas_in[i];
+        const int dst = c->h_tlas_in_dst[i];
+        if (dst >= 0) {
+            const float *n = reinterpret_cast<const float *>(&nodes[(size_t)(dst >> 1) * 4]) + ((dst & 1) ? 6 : 0);
+            N.bmin = ptrt_vec3{n[0], n[1], n[2]};
+            N.bmax = ptrt_vec3{n[3], n[4], n[5]};
+        } else if (dst != INT32_MIN) {
+            N.bmin = ptrt_vec3{root[0].x, root[0].y, root[0].z};
+            N.bmax = ptrt_vec3{root[1].x, root[1].y, root[1].z};
+        }
+        nodes_out[i] = N;
+    }
     return PTRT_OK;
 }
 
@@ -3399,6 +3645,8 @@ int ptrt_get_option(ptrt_ctx *c, const char *name, long long *value) {
         {"merged_decided", (c->merged >= 0 || c->tune_choice >= 0 || !c->last_merged_possible) ? 1 : 0}, // 0 while "merged" = -1 is still sampling
         {"launches", (long long)c->launches},
         {"query_pmode", c->query_pmode}, // traversal of the last ptrt_query_rays / ptrt_trace_rays: 0 one ray per lane, 1..3 pairs
+        {"inst_pre_ok", c->inst_pre_ok ? 1 : 0}, // the instances' first-pass boxes (PMODE 3) match the device's root boxes and matrices
+        {"tlas_refits", c->tlas_refits},         // ptrt_refit_tlas calls since the last geometry upload
         {"stream", (long long)(intptr_t)c->stream}, // the hipStream_t the context enqueues on (stream-ordering its device results)
     };
     for (const auto &e : tab)

@@ -209,8 +209,8 @@ int hs_mesh_set_triangle_soup(void *s, int mesh, const float *verts9, int n_tris
     return 0;
 }
 int hs_set_dynamic_geometry_policy(void *s, int policy) {
-    if (policy < 0 || policy > 2) {
-        g_err = "policy must be 0 (HostRebuild), 1 (GpuRefit) or 2 (GpuRebuild)";
+    if (policy < 0 || policy > 3) {
+        g_err = "policy must be 0 (HostRebuild), 1 (GpuRefit), 2 (GpuRebuild) or 3 (GpuRefitAll)";
         return -1;
     }
     static_cast<Scene *>(s)->setDynamicGeometryPolicy((Scene::DynamicGeometryPolicy)policy);
@@ -308,6 +308,13 @@ void hs_get_view_proj(void *s, int which, float *out16) {
 int hs_upload(void *s) { HS_TRY(static_cast<Scene *>(s)->uploadToGPU()); return 0; }
 int hs_commit_object_changes(void *s) { HS_TRY(static_cast<Scene *>(s)->commitObjectChanges()); return 0; }
 int hs_refit_object_changes(void *s) { HS_TRY(static_cast<Scene *>(s)->refitObjectChanges()); return 0; }
+// moved instances behind a kept TLAS topology: new matrices + TLAS refit on the device, no synchronisation (host_only: the
+// host half alone, for a Scene without a back end); hs_reseat_tlas: the TLAS rebuilt on the host and uploaded
+int hs_refit_instance_changes(void *s, int host_only) {
+    HS_TRY(host_only ? static_cast<Scene *>(s)->refitInstanceChangesOnHost() : static_cast<Scene *>(s)->refitInstanceChanges());
+    return 0;
+}
+int hs_reseat_tlas(void *s) { HS_TRY(static_cast<Scene *>(s)->reseatTLAS()); return 0; }
 int hs_refit_from_device(void *s, int mesh, const void *device_xyz) {
     HS_TRY(static_cast<Scene *>(s)->refitFromDevice((size_t)mesh, static_cast<const float *>(device_xyz)));
     return 0;

@@ -527,11 +527,14 @@ class Scene {
     //   GpuRefit   -- the uploaded tree is kept: the new positions go to the device (ptrt_update_vertices) and the boxes are
     //                 refitted there (ptrt_refit); no host build, no re-upload of the arena;
     //   GpuRebuild -- as GpuRefit, but the faces are re-assigned to the leaves in Morton order first (ptrt_build_bvh).
+    //   GpuRefitAll -- as GpuRefit, and a mesh whose instance transform changed goes through refitInstanceChanges(): the TLAS
+    //                 is refitted on the device over the uploaded topology (ptrt_refit_tlas) and rebuilt nowhere; reseatTLAS()
+    //                 gives it a fresh topology when the caller wants one.
     // A changed face list, vertex count, a new mesh, or a mesh without an uploaded tree falls back to HostRebuild for that
     // commit.  The host copy of a tree kept on the GPU is brought up to date when something reads it (flatten(), a real
     // TLAS, the next full upload).  So the UNCHANGED call sequence updatePTScene(scene, unified) -> commitObjectChanges()
     // reaches the GPU refit once the application has said  scene.setDynamicGeometryPolicy(...)  after building it.
-    enum class DynamicGeometryPolicy { HostRebuild = 0, GpuRefit = 1, GpuRebuild = 2 };
+    enum class DynamicGeometryPolicy { HostRebuild = 0, GpuRefit = 1, GpuRebuild = 2, GpuRefitAll = 3 };
     void setDynamicGeometryPolicy(DynamicGeometryPolicy p) {
         // (chosen after the upload: the face lists of the meshes nobody has touched since are what the device holds)
         if (p != DynamicGeometryPolicy::HostRebuild && gpu_resources_initialized && !geometryDirty && uploadedFaces.size() == meshes.size())
@@ -575,6 +578,7 @@ class Scene {
     // rebuilds it as the reference's commit does)
     void syncTLAS() {
         buildTLAS();
+        hostTlasStale = false;
         flat.tlas_nodes = h_tlasNodes.data();
         flat.tlas_node_count = (int)h_tlasNodes.size();
         flat.tlas_mesh_indices = h_tlasMeshIndices.data();
@@ -591,11 +595,9 @@ class Scene {
         Mesh *m = getMesh(mesh);
         if (!m)
             throw std::runtime_error("refitFromDevice: no such mesh");
-        if (h_tlasNodes.size() > 1)
-            throw std::runtime_error("refitFromDevice: a TLAS with inner nodes is rebuilt on the host, which needs the "
-                                     "vertices (use setVertices + refitObjectChanges)");
         check(ptrt_update_vertices(ctx, (int)mesh, device_xyz, (int)m->vertices.size(), 1), "Failed to update vertices");
         check(ptrt_refit(ctx), "Failed to refit");
+        refitDeviceTLAS();
         resetAccumulation();
     }
 
@@ -606,10 +608,9 @@ class Scene {
         Mesh *m = getMesh(mesh);
         if (!m)
             throw std::runtime_error("refitFromHost: no such mesh");
-        if (h_tlasNodes.size() > 1)
-            throw std::runtime_error("refitFromHost: a TLAS with inner nodes is rebuilt on the host (use setVertices + refitObjectChanges)");
         check(ptrt_update_vertices(ctx, (int)mesh, host_xyz, (int)m->vertices.size(), 0), "Failed to update vertices");
         check(ptrt_refit(ctx), "Failed to refit");
+        refitDeviceTLAS();
         resetAccumulation();
     }
 
@@ -631,11 +632,17 @@ class Scene {
             check(ptrt_build_bvh(ctx, (int)i), "Failed to build BVH");
             if (syncHostCopy)
                 syncPrimOrder(i);
+            else if (h_tlasNodes.size() > 1 && i < hostTreeStale.size()) {
+                // behind a TLAS with inner nodes the host copy follows lazily, as under the GpuRebuild policy: left dirty, the
+                // mesh would be rebuilt on the host and everything uploaded again by the next frame, a second topology
+                hostTreeStale[i] = 2;
+                m->bvhDirty = false;
+            }
         }
         if (syncHostCopy)
             syncTLAS();
-        else if (h_tlasNodes.size() > 1)
-            throw std::runtime_error("rebuildObjectChanges: a TLAS with inner nodes needs the host copy (syncHostCopy)");
+        else
+            refitDeviceTLAS();
         resetAccumulation();
     }
     // same, new positions already in device memory (host copy not updated)
@@ -644,11 +651,9 @@ class Scene {
         Mesh *m = getMesh(mesh);
         if (!m)
             throw std::runtime_error("rebuildFromDevice: no such mesh");
-        if (h_tlasNodes.size() > 1)
-            throw std::runtime_error("rebuildFromDevice: a TLAS with inner nodes is rebuilt on the host, which needs the "
-                                     "vertices (use setVertices + rebuildObjectChanges)");
         check(ptrt_update_vertices(ctx, (int)mesh, device_xyz, (int)m->vertices.size(), 1), "Failed to update vertices");
         check(ptrt_build_bvh(ctx, (int)mesh), "Failed to build BVH");
+        refitDeviceTLAS();
         resetAccumulation();
     }
     // updatePTScene's `Triangles` path (PTRTtransfer.cuh:2204-2385) for a soup mesh made by
@@ -671,6 +676,101 @@ class Scene {
             syncPrimOrder(mesh);
             syncTLAS();
         }
+        resetAccumulation();
+    }
+    // Instances moved, nothing else changed, and the TLAS keeps the topology it was uploaded with (not in the reference, whose
+    // commit rebuilds the TLAS on the CPU: scene.cuh:458-594, 656-743).  Every mesh whose transform is dirty or whose world
+    // matrix differs from the last one handed over gets new matrices on the device -- one ptrt_set_instance_transforms per run
+    // of consecutive meshes -- and ptrt_refit_tlas refits the TLAS there; nothing waits for the stream.  The host TLAS is
+    // refitted over the same topology (refitTLAS), so flatten() describes what the GPU traverses.
+    void refitInstanceChanges() {
+        needBackend();
+        if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
+            throw std::runtime_error("refitInstanceChanges: call uploadToGPU() first (the TLAS topology must already be on the GPU)");
+        refitMovedInstances();
+        resetAccumulation();
+    }
+    void refitMovedInstances() { // (the work of refitInstanceChanges; a commit under GpuRefitAll comes here as well)
+        std::vector<ptrt_instance_xform> run;
+        int first = 0;
+        auto flush = [&] {
+            if (!run.empty())
+                check(ptrt_set_instance_transforms(ctx, first, (int)run.size(), run.data()), "Failed to set instance transforms");
+            run.clear();
+        };
+        for (size_t i = 0; i < meshes.size(); ++i) {
+            if (!takeInstanceMove(i)) {
+                flush();
+                continue;
+            }
+            if (run.empty())
+                first = (int)i;
+            const ptrt_mesh_desc &d = flatMeshes[i];
+            ptrt_instance_xform x;
+            std::memcpy(x.world, d.world, sizeof x.world);
+            std::memcpy(x.inverse, d.inverse, sizeof x.inverse);
+            std::memcpy(x.normal, d.normal, sizeof x.normal);
+            x.has_transform = d.has_transform;
+            run.push_back(x);
+        }
+        flush();
+        check(ptrt_refit_tlas(ctx), "Failed to refit the TLAS");
+        bool roots_lag = hostTlasStale; // (host root boxes that lag the device's: the host TLAS follows by read-back, lazily)
+        for (unsigned char st : hostTreeStale)
+            roots_lag = roots_lag || st != 0;
+        if (roots_lag)
+            hostTlasStale = true;
+        else
+            refitTLAS();
+    }
+    // the host half alone, for a Scene without a back end (tests, tools that only flatten())
+    void refitInstanceChangesOnHost() {
+        if (geometryDirty && ctx)
+            throw std::runtime_error("refitInstanceChangesOnHost: geometry is dirty");
+        if (flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
+            prepareHostStructures();
+        for (size_t i = 0; i < meshes.size(); ++i)
+            takeInstanceMove(i);
+        refitTLAS();
+        resetAccumulation();
+    }
+    // Host twin of ptrt_refit_tlas: the boxes of h_tlasNodes over the topology they have -- every mesh's world box from its
+    // root box through Transform3D::transformAABB (as buildTLAS takes it), every leaf the union of its members, every inner
+    // node the union of its children.  min / max are exact: the device's refit gives the same bits.
+    void refitTLAS() {
+        if (h_tlasNodes.empty())
+            throw std::runtime_error("refitTLAS: no TLAS built yet");
+        std::vector<AABB> world(meshes.size());
+        for (size_t i = 0; i < meshes.size(); ++i) {
+            const Mesh *m = meshes[i].get();
+            if (m->bvhNodes.empty())
+                throw std::runtime_error("Mesh BVH not built before TLAS");
+            const DeviceBVHNode &root = m->bvhNodes[0];
+            world[i] = m->transform.transformAABB(AABB{vec3(root.bmin.x, root.bmin.y, root.bmin.z), vec3(root.bmax.x, root.bmax.y, root.bmax.z)});
+        }
+        refitTLASNode(0, world, 0);
+    }
+    // A refitted TLAS degrades as instances travel: the topology is the upload's, and the boxes of far-apart members of a leaf
+    // overlap their neighbours'.  reseatTLAS() is the reference's way for the TLAS alone -- rebuilt on the host over the meshes'
+    // current boxes and handed to the device with the matrices (ptrt_update_instances; synchronises) -- for a caller that wants a
+    // fresh topology, say once the refitted one has cost a few per cent of frame time.
+    void reseatTLAS() {
+        needBackend();
+        if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size())
+            throw std::runtime_error("reseatTLAS: call uploadToGPU() first");
+        hostTlasStale = false; // (rebuilt below; only the meshes' own trees have to follow the device first)
+        syncHostTrees();
+        for (size_t i = 0; i < meshes.size(); ++i)
+            takeInstanceMove(i);
+        buildTLAS();
+        flat.tlas_nodes = h_tlasNodes.data();
+        flat.tlas_node_count = (int)h_tlasNodes.size();
+        flat.tlas_mesh_indices = h_tlasMeshIndices.data();
+        flat.tlas_index_count = (int)h_tlasMeshIndices.size();
+        check(ptrt_update_instances(ctx, flat.meshes, flat.mesh_count, flat.tlas_nodes, flat.tlas_node_count, flat.tlas_mesh_indices,
+                                    flat.tlas_index_count),
+              "Failed to update the TLAS");
+        instancesDirty = false;
         resetAccumulation();
     }
     // host copy of mesh `i`'s tree := what the GPU now traverses
@@ -980,6 +1080,7 @@ class Scene {
     std::vector<std::vector<Tri>> uploadedFaces;
     std::vector<size_t> uploadedVerts;
     std::vector<unsigned char> hostTreeStale, uploadedSoup;
+    bool hostTlasStale = false; // the device refitted its TLAS (ptrt_refit_tlas) over root boxes the host has not followed yet
     size_t gpuDynamicCommits = 0, geometryUploads = 0;
     double commitMicros = 0.0, compareMicros = 0.0;
 
@@ -1002,6 +1103,52 @@ class Scene {
         lights.push_back(l);
         lightsDirty = true;
         resetAccumulation();
+    }
+
+    // mesh i's instance transform changed since its descriptor was written: matrices, descriptor and lastWorld brought up to
+    // date as prepareHostStructures does for a moved instance; false if nothing changed
+    bool takeInstanceMove(size_t i) {
+        Mesh *m = meshes[i].get();
+        if (m->transform.dirty)
+            m->transform.updateMatrices();
+        else if (std::memcmp(&lastWorld[i], &m->transform.worldMatrix, sizeof(mat4)) == 0)
+            return false;
+        lastWorld[i] = m->transform.worldMatrix;
+        ptrt_mesh_desc &d = flatMeshes[i];
+        std::memcpy(d.world, m->transform.worldMatrix.m, sizeof d.world);
+        std::memcpy(d.inverse, m->transform.inverseMatrix.m, sizeof d.inverse);
+        std::memcpy(d.normal, m->transform.normalMatrix.m, sizeof d.normal);
+        d.has_transform = (m->transform.position.length() > 0.001f || m->transform.rotation.length() > 0.001f ||
+                           fabsf(m->transform.scale.x - 1.0f) > 0.001f)
+                              ? 1
+                              : 0; // scene.cuh:718-721
+        return true;
+    }
+    AABB refitTLASNode(int n, const std::vector<AABB> &world, int depth) {
+        if (n < 0 || n >= (int)h_tlasNodes.size() || depth > 64)
+            throw std::runtime_error("refitTLAS: malformed TLAS");
+        DeviceBVHNode &N = h_tlasNodes[n];
+        AABB b = AABB::make_invalid();
+        if (N.count > 0) {
+            for (int k = 0; k < N.count; ++k)
+                b.expand(world[(size_t)h_tlasMeshIndices[(size_t)N.start + k]]);
+        } else {
+            if (N.left >= 0)
+                b.expand(refitTLASNode(N.left, world, depth + 1));
+            if (N.right >= 0)
+                b.expand(refitTLASNode(N.right, world, depth + 1));
+        }
+        N.bmin = {b.bmin.x, b.bmin.y, b.bmin.z};
+        N.bmax = {b.bmax.x, b.bmax.y, b.bmax.z};
+        return b;
+    }
+    // behind a TLAS with inner nodes the root boxes a GPU refit / rebuild moved reach the TLAS by a refit on the device; the
+    // host copy follows when something reads it (syncHostTrees).  A single-leaf TLAS got its box from ptrt_refit itself.
+    void refitDeviceTLAS() {
+        if (h_tlasNodes.size() <= 1)
+            return;
+        check(ptrt_refit_tlas(ctx), "Failed to refit the TLAS");
+        hostTlasStale = true;
     }
 
     // TLAS over the meshes' world AABBs, same builder and leaf limit as the BLAS
@@ -1037,14 +1184,16 @@ class Scene {
     void prepareHostStructures(bool forRead = true) {
         if (meshes.empty())
             return;
-        bool need_trees = forRead || geometryDirty || flatMeshes.size() != meshes.size() || h_tlasNodes.size() != 1;
+        // (a TLAS the DEVICE refitted needs no host trees until something reads or moves them)
+        bool need_trees = forRead || geometryDirty || flatMeshes.size() != meshes.size() || (h_tlasNodes.size() != 1 && !hostTlasStale);
         for (size_t i = 0; i < meshes.size() && !need_trees; ++i) {
             const Mesh *m = meshes[i].get();
             need_trees = m->vertsDirty || m->bvhDirty || m->bvhNodes.empty() || m->transform.dirty ||
                          std::memcmp(&lastWorld[i], &m->transform.worldMatrix, sizeof(mat4)) != 0;
         }
         const bool synced = need_trees && syncHostTrees(); // (trees the GPU refitted / rebuilt since the host last looked)
-        bool tlas_dirty = h_tlasNodes.empty() || synced;
+        // (refitted trees move the box of a single-leaf TLAS; one with inner nodes was refitted on the device and read back)
+        bool tlas_dirty = h_tlasNodes.empty() || (synced && h_tlasNodes.size() == 1);
         if (flatMeshes.size() != meshes.size()) {
             flatMeshes.assign(meshes.size(), ptrt_mesh_desc{});
             lastWorld.assign(meshes.size(), mat4());
@@ -1162,7 +1311,11 @@ class Scene {
                 return false;
             moved.push_back(i);
         }
-        if (moved.empty())
+        const bool all = dynPolicy == DynamicGeometryPolicy::GpuRefitAll;
+        bool instances = false;
+        for (size_t i = 0; all && i < meshes.size() && !instances; ++i)
+            instances = meshes[i]->transform.dirty || std::memcmp(&lastWorld[i], &meshes[i]->transform.worldMatrix, sizeof(mat4)) != 0;
+        if (moved.empty() && !instances)
             return false;
         const bool rebuild = dynPolicy == DynamicGeometryPolicy::GpuRebuild;
         for (size_t i : moved) {
@@ -1176,9 +1329,14 @@ class Scene {
             flatMeshes[i].verts = reinterpret_cast<const ptrt_vec3 *>(m->vertices.data()); // (the caller may have re-allocated them)
             flatMeshes[i].faces = m->faces.data();
         }
-        if (!rebuild)
+        if (!rebuild && !moved.empty())
             check(ptrt_refit(ctx), "Failed to refit");
-        if (h_tlasNodes.size() > 1) { // a real TLAS is rebuilt on the host over the new boxes, as the reference's commit does
+        if (all) { // the TLAS is refitted on the device and rebuilt nowhere
+            if (instances)
+                refitMovedInstances();
+            else
+                refitDeviceTLAS();
+        } else if (h_tlasNodes.size() > 1) { // a real TLAS is rebuilt on the host over the new boxes, as the reference's commit does
             syncHostTrees();
             syncTLAS();
         }
@@ -1217,6 +1375,10 @@ class Scene {
             hostTreeStale[i] = 0;
             any = true;
         }
+        if (hostTlasStale && ctx && !h_tlasNodes.empty()) { // the TLAS as the device refitted it (ptrt_read_tlas synchronises)
+            check(ptrt_read_tlas(ctx, h_tlasNodes.data(), (int)h_tlasNodes.size()), "Failed to read the TLAS");
+            hostTlasStale = false;
+        }
         return any;
     }
 
@@ -1239,6 +1401,7 @@ class Scene {
                                        flat.tlas_mesh_indices, flat.tlas_index_count),
                   "Failed to upload geometry");
             geometryDirty = instancesDirty = false;
+            hostTlasStale = false;
             ++geometryUploads;
             // what the device now holds, for the dynamic-geometry policy
             uploadedFaces.resize(meshes.size());
@@ -1263,6 +1426,7 @@ class Scene {
                                         flat.tlas_mesh_indices, flat.tlas_index_count),
                   "Failed to update instances");
             instancesDirty = false;
+            hostTlasStale = false;
         }
         if (materialsDirty) {
             check(ptrt_upload_materials(ctx, &flat.materials), "Failed to upload materials");

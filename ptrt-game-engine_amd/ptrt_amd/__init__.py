@@ -64,6 +64,11 @@ class MeshDesc(C.Structure):
                 ("has_transform", C.c_int32)]
 
 
+class InstanceXform(C.Structure):
+    _fields_ = [("world", C.c_float * 16), ("inverse", C.c_float * 16), ("normal", C.c_float * 16),
+                ("has_transform", C.c_int32)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_int32), ("position", Vec3), ("direction", Vec3), ("color", Vec3),
                 ("intensity", C.c_float), ("range", C.c_float), ("inner_cone", C.c_float),
@@ -112,6 +117,9 @@ HIT_DTYPE = np.dtype([("hit", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("norma
                       ("mesh_index", "<i4"), ("front_face", "<i4"), ("u", "<f4"), ("v", "<f4"),
                       ("face_index", "<i4"), ("local_point", "<f4", 3)])
 assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
+TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
+                            ("count", "<i4")])
+assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
 
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -246,6 +254,11 @@ _sig("ptrt_refit", C.c_int, _vp)
 _sig("ptrt_build_bvh", C.c_int, _vp, C.c_int)
 _sig("ptrt_read_prim_order", C.c_int, _vp, C.c_int, C.POINTER(C.c_int), C.c_int)
 _sig("ptrt_update_triangles", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
+_sig("ptrt_set_instance_transforms", C.c_int, _vp, C.c_int, C.c_int, C.POINTER(InstanceXform))
+_sig("ptrt_refit_tlas", C.c_int, _vp)
+_sig("ptrt_read_tlas", C.c_int, _vp, C.POINTER(BvhNode), C.c_int)
+_sig("hs_refit_instance_changes", C.c_int, _vp, C.c_int)
+_sig("hs_reseat_tlas", C.c_int, _vp)
 _sig("hs_rebuild_object_changes", C.c_int, _vp, C.c_int)
 _sig("hs_rebuild_from_device", C.c_int, _vp, C.c_int, _vp)
 _sig("hs_update_triangles", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
@@ -434,7 +447,7 @@ class Scene:
         a = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
         self._chk(lib.hs_mesh_set_triangle_soup(self._h, mesh, _fptr(a), a.shape[0]))
 
-    POLICIES = {"HostRebuild": 0, "GpuRefit": 1, "GpuRebuild": 2}
+    POLICIES = {"HostRebuild": 0, "GpuRefit": 1, "GpuRebuild": 2, "GpuRefitAll": 3}
 
     def setDynamicGeometryPolicy(self, policy):
         self._chk(lib.hs_set_dynamic_geometry_policy(self._h, self.POLICIES.get(policy, policy)))
@@ -525,6 +538,23 @@ class Scene:
     def refitObjectChanges(self):
         """Dynamic vertices, same topology: host + GPU BVH refit instead of the reference's rebuild."""
         self._chk(lib.hs_refit_object_changes(self._h))
+
+    def refitInstanceChanges(self, host_only=False):
+        """Moved instances behind the TLAS topology that was uploaded: new matrices (ptrt_set_instance_transforms) and a TLAS
+        refit on the device (ptrt_refit_tlas), no host synchronisation; the host TLAS is refitted the same way.
+        `host_only`: the host half alone, for a device=-1 scene."""
+        self._chk(lib.hs_refit_instance_changes(self._h, int(bool(host_only))))
+
+    def reseatTLAS(self):
+        """A fresh TLAS topology: rebuilt on the host over the meshes' current boxes and uploaded (ptrt_update_instances)."""
+        self._chk(lib.hs_reseat_tlas(self._h))
+
+    def read_tlas(self):
+        """The TLAS as the device holds it (ptrt_read_tlas; synchronises): structured array bmin, bmax, left, right, start, count."""
+        n = self.flatten().contents.tlas_node_count
+        out = np.zeros(n, dtype=TLAS_NODE_DTYPE)
+        self._cchk(lib.ptrt_read_tlas(self.ctx, out.ctypes.data_as(C.POINTER(BvhNode)), n))
+        return out
 
     def refitFromDevice(self, mesh, device_ptr):
         """New vertex positions (n x 3 float32) already in device memory -> update + GPU refit, no host sync."""

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""What moving instances behind a real TLAS costs per frame: the `many` recipe at bench.py's size (136 meshes), k instances
+moved every frame for a run of frames, committed
+  (a) by commitObjectChanges() under the default policy: TLAS rebuilt on the host, ptrt_update_instances (synchronises);
+  (b) by refitInstanceChanges(): ptrt_set_instance_transforms + ptrt_refit_tlas on the stream, TLAS topology kept.
+Per frame: host microseconds inside the commit call (perf_counter around it) and the frame time -- HIP events on the context's
+stream around the whole run of commit + render_to_device, divided by the frames, so a stall of the host shows as a gap.  The two
+paths alternate, window by window, in one process; medians over the windows are reported with their range.
+
+Also: the PMODE 3 frame time after a vertex refit of one mesh, with the instances' first-pass boxes left invalid (ptrt_refit
+alone: inst_pre_ok 0) and recomputed on the device (ptrt_refit + ptrt_refit_tlas: inst_pre_ok 1), same frames otherwise.
+
+    python3 tools/tlas_refit_time.py --out profiles/tlas_refit_time.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "ptrt-game-engine_amd"))
+import torch  # noqa: E402  (one HIP runtime per process: torch first)
+import ptrt_amd as P  # noqa: E402
+
+N_EXTRA, BASE = 128, 8  # bench.py's `many`: the Cornell box's 8 meshes + 128
+
+
+def build(width, height, spp, depth):
+    s = P.Scene(width, height)
+    P.scenes.many(s, N_EXTRA, sphere_segments=32)
+    s.setPerfSamplesPerPixel(spp)
+    s.setMaxBounceDepth(depth)
+    s.setDenoiserEnabled(False)
+    s.setBloomEnabled(False)
+    s.initBlueNoise()
+    s.uploadToGPU()
+    return s
+
+
+def run_frames(s, stream, out, frames, k, commit, frame0):
+    """`frames` frames of: move k instances (every third extra mesh is one), commit, render.  Returns (host us per commit,
+    ms per frame by events on the stream)."""
+    inst = [BASE + j for j in range(0, N_EXTRA, 3)][:k]
+    host = 0.0
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for f in range(frames):
+        a = 0.05 * (frame0 + f)
+        for j, m in enumerate(inst):
+            s.setPosition(m, (3.0 * np.sin(a + j), -1.0 + 2.0 * np.cos(0.7 * a + j), -5.0 + 2.0 * np.sin(0.3 * a + 2 * j)))
+        t0 = time.perf_counter()
+        commit()
+        host += time.perf_counter() - t0
+        s.render_to_device(out.data_ptr())
+    e1.record(stream)
+    e1.synchronize()
+    return 1e6 * host / frames, e0.elapsed_time(e1) / frames
+
+
+def summary(v):
+    return {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3), "n": len(v)}
+
+
+def measure_moves(a):
+    rows = []
+    for k in (int(x) for x in a.moved.split(",")):
+        scenes = {"commit": build(a.width, a.height, a.spp, a.depth), "refit": build(a.width, a.height, a.spp, a.depth)}
+        stream = torch.cuda.Stream()
+        out = torch.empty(a.width * a.height * 3, dtype=torch.uint8, device="cuda")
+        res = {name: {"host_us": [], "frame_ms": []} for name in scenes}
+        for s in scenes.values():
+            s.set_stream(stream.cuda_stream)
+        commits = {"commit": scenes["commit"].commitObjectChanges, "refit": scenes["refit"].refitInstanceChanges}
+        with torch.cuda.stream(stream):
+            for w in range(a.windows + 1):  # (window 0 warms both paths up)
+                for name, s in scenes.items():
+                    h, ms = run_frames(s, stream, out, a.frames, k, commits[name], w * a.frames)
+                    if w:
+                        res[name]["host_us"].append(h)
+                        res[name]["frame_ms"].append(ms)
+        counts = {name: s.get_option("tlas_refits") for name, s in scenes.items()}
+        row = {"case": "moved_instances", "meshes": BASE + N_EXTRA, "moved_per_frame": k, "frames_per_window": a.frames,
+               "size": [a.width, a.height], "spp": a.spp, "depth": a.depth, "pmode": scenes["refit"].get_option("pmode"),
+               "tlas_refits": counts, "library": P.library_info()["sha16"]}
+        for name in scenes:
+            row[f"{name}_host_us"] = summary(res[name]["host_us"])
+            row[f"{name}_frame_ms"] = summary(res[name]["frame_ms"])
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        for s in scenes.values():
+            s.sync()
+            s.close()
+    return rows
+
+
+def measure_pretest(a):
+    """frames after a vertex refit of one mesh, first-pass boxes invalid vs recomputed on the device"""
+    s = build(a.width, a.height, a.spp, a.depth)
+    stream = torch.cuda.Stream()
+    s.set_stream(stream.cuda_stream)
+    out = torch.empty(a.width * a.height * 3, dtype=torch.uint8, device="cuda")
+    mesh = BASE + 1  # a sphere with baked vertices
+    md = s.flatten().contents.meshes[mesh]
+    import ctypes as C
+    base = np.ctypeslib.as_array(C.cast(md.verts, C.POINTER(C.c_float)), (md.vert_count, 3)).copy()
+    dev = torch.from_numpy(base).cuda()
+    res = {0: [], 1: []}
+    with torch.cuda.stream(stream):
+        for w in range(a.windows + 1):
+            for ok in (0, 1):
+                s._cchk(P.lib.ptrt_update_vertices(s.ctx, mesh, C.cast(dev.data_ptr(), C.POINTER(C.c_float)), len(base), 1))
+                s._cchk(P.lib.ptrt_refit(s.ctx))
+                if ok:
+                    s._cchk(P.lib.ptrt_refit_tlas(s.ctx))
+                assert s.get_option("inst_pre_ok") == ok
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.render_to_device(out.data_ptr())  # (gathers the heads with this state)
+                e0.record(stream)
+                for _ in range(a.frames):
+                    s.render_to_device(out.data_ptr())
+                e1.record(stream)
+                e1.synchronize()
+                if w:
+                    res[ok].append(e0.elapsed_time(e1) / a.frames)
+    row = {"case": "first_pass_boxes_after_vertex_refit", "meshes": BASE + N_EXTRA, "size": [a.width, a.height], "spp": a.spp,
+           "depth": a.depth, "pmode": s.get_option("pmode"), "frame_ms_inst_pre_ok_0": summary(res[0]),
+           "frame_ms_inst_pre_ok_1": summary(res[1]), "library": P.library_info()["sha16"]}
+    print(json.dumps(row), flush=True)
+    s.sync()
+    s.close()
+    return [row]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--moved", default="1,8,44", help="instances moved per frame (the recipe has 43 instances; more are clipped)")
+    ap.add_argument("--frames", type=int, default=100, help="frames per window")
+    ap.add_argument("--windows", type=int, default=5, help="timed windows per path (they alternate)")
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--spp", type=int, default=1)
+    ap.add_argument("--depth", type=int, default=4)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    rows = measure_moves(a) + measure_pretest(a)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump({"command": f"python3 tools/tlas_refit_time.py --moved {a.moved} --frames {a.frames} --windows {a.windows} "
+                                  f"--width {a.width} --height {a.height} --spp {a.spp} --depth {a.depth}",
+                       "device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
