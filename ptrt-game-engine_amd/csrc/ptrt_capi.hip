@@ -33,6 +33,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "ptrt_frame_ring.hip.h"
+
 namespace {
 
 constexpr int EV_RING = 256;
@@ -163,13 +165,7 @@ struct ptrt_ctx {
     size_t rpix() const { return scaled() ? (size_t)rw * rh : npix; } // pixels the path tracer renders
 
     // presentation ring (ptrt_present_*): device RGB8 frames mirrored into pinned host memory
-    struct PresentSlot {
-        unsigned char *dev = nullptr, *host = nullptr;
-        hipEvent_t rendered = nullptr, done = nullptr;
-        bool in_flight = false;
-    };
-    std::vector<PresentSlot> present;
-    hipStream_t present_stream = nullptr;
+    FrameRing present;
 
     // wavefront stages (pt_wavefront.hip.h): per-path state, planar, tile-ordered
     int wavefront = 0; // option: 1 = render scenes with a single-leaf TLAS through the trace/shade stages
@@ -266,37 +262,7 @@ struct ptrt_ctx {
     hipEvent_t tm_fork[MAX_SPLIT] = {nullptr, nullptr, nullptr, nullptr}, tm_join[MAX_SPLIT] = {nullptr, nullptr, nullptr, nullptr};
 };
 
-// Presentation ring without a context (ptrt_ring_*): the CUDA-registered GL pixel-buffer object of
-// rtgl::init_interop_viewer as `slots` device frames mirrored into pinned host memory.
-struct ptrt_ring {
-    int device = 0;
-    size_t bytes = 0;
-    struct Slot {
-        unsigned char *dev = nullptr, *host = nullptr;
-        hipEvent_t rendered = nullptr, done = nullptr;
-        bool in_flight = false; // a download of this slot has been enqueued and not yet waited for
-        bool marked = false;    // `rendered` was recorded by the render call that wrote the slot
-    };
-    std::vector<Slot> slots;
-    hipStream_t copy_stream = nullptr;
-};
-
 namespace {
-
-std::mutex g_ring_mutex;
-std::set<ptrt_ring *> g_rings;
-
-// ptrt_render / ptrt_post_frame wrote their RGB8 frame to `out` on `stream`: if that is a ring slot, the slot's
-// download must wait for exactly this point of the stream.
-void ring_mark_rendered(const void *out, hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(g_ring_mutex);
-    for (ptrt_ring *r : g_rings)
-        for (auto &s : r->slots)
-            if (s.dev == out) {
-                s.marked = hipEventRecord(s.rendered, stream) == hipSuccess;
-                return;
-            }
-}
 
 // Records the message for ptrt_last_error.  `c` may be a stale (already destroyed) handle -- every entry point
 // reports "bad context" through here -- so it is only written to while it is in the live set.
@@ -328,6 +294,19 @@ template <class T> void dfree(T *&p) {
         p = nullptr;
     }
 }
+// A function-local device allocation of n elements: freed when it goes out of scope, so that no early return (HIP_TRY) leaks
+// it.  Move-only.  The context's long-lived buffers stay raw pointers: they feed the kernel-parameter structs directly.
+template <class T> struct DeviceTemp {
+    T *p = nullptr;
+    DeviceTemp() = default;
+    DeviceTemp(DeviceTemp &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DeviceTemp &operator=(DeviceTemp &&o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~DeviceTemp() { dfree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, n * sizeof(T)); }
+};
 template <class T> int upload(ptrt_ctx *c, T *&dst, const std::vector<T> &src) {
     dfree(dst);
     const size_t n = src.empty() ? 1 : src.size();
@@ -633,7 +612,16 @@ int set_device(ptrt_ctx *c) {
     return PTRT_OK;
 }
 
-int merged_pair_cap(const ptrt_ctx *c);
+// PMODE 4 keeps extension and shadow pairs in one list: 64 * meshes entries always fit the extension pairs; the
+// shadow pairs get what is left of a 10-KB LDS budget (16 waves per CU), at least 64 (one mesh per pass), at most
+// another 64 * meshes (everything in one pass)
+int merged_pair_cap(const ptrt_ctx *c) {
+    const size_t rest = (size_t)c->pair_meshes * 32 + 512 + 256 + (size_t)c->stack_entries * 64 * sizeof(uint2) + pt::LEAF_PAIR_BYTES + 24;
+    const int lo = 64 * c->pair_meshes + 64, hi = 128 * c->pair_meshes;
+    int cap = rest < 10240 ? (int)((10240 - rest) / 2) / 64 * 64 : 0;
+    cap = cap < lo ? lo : cap;
+    return cap > hi ? hi : cap;
+}
 pt::KParams make_params(ptrt_ctx *c) {
     pt::KParams K{};
     K.mesh_recs = c->d_mesh_recs;
@@ -710,6 +698,24 @@ int pick_geom(ptrt_ctx *c) {
     return g;
 }
 
+// The 3 * EV_RING events of option "time_launches" for auxiliary stream i, all of them or none: a failure part-way destroys
+// what it made and turns the option off for this context, so that no later frame records on a null event.
+int create_launch_events(ptrt_ctx *c, int i) {
+    std::vector<hipEvent_t> ev(3 * EV_RING, nullptr);
+    for (auto &e : ev) {
+        const hipError_t err = hipEventCreate(&e);
+        if (err != hipSuccess) {
+            for (hipEvent_t made : ev)
+                if (made)
+                    (void)hipEventDestroy(made);
+            c->time_launches = 0;
+            return fail(c, PTRT_E_HIP, "hipEventCreate failed: %s (time_launches is off now)", hipGetErrorString(err));
+        }
+    }
+    c->launch_ev[i].swap(ev);
+    return PTRT_OK;
+}
+
 // One 8x8 tile per 64-thread workgroup.  The frame's tile rows may be dealt to `c->split_eff` launches that run concurrently
 // on the context's stream and its auxiliary streams (forked and joined by events around them: render_split_begin / _end).
 template <int GEOM, int PMODE> int launch_trace(ptrt_ctx *c, const pt::KParams &K0, bool full, int grid, size_t lds) {
@@ -728,11 +734,9 @@ template <int GEOM, int PMODE> int launch_trace(ptrt_ctx *c, const pt::KParams &
         hipStream_t st = n > 1 ? c->aux_stream[i] : c->stream;
         hipEvent_t *ev = nullptr;
         if (timed) {
-            if (c->launch_ev[i].empty()) {
-                c->launch_ev[i].assign(3 * EV_RING, nullptr);
-                for (auto &e : c->launch_ev[i])
-                    HIP_TRY(c, hipEventCreate(&e));
-            }
+            if (c->launch_ev[i].empty())
+                if (int rc = create_launch_events(c, i))
+                    return rc;
             ev = &c->launch_ev[i][3 * slot];
             HIP_TRY(c, hipEventRecord(ev[0], st));
             c->launch_timed[slot] = (unsigned char)(c->launch_timed[slot] | (1u << i));
@@ -799,16 +803,6 @@ template <int GEOM, int PMODE> int launch_trace(ptrt_ctx *c, const pt::KParams &
 
 // in-wave (ray, mesh) pair compaction needs every BLAS to be one leaf and the staged
 // triangle packets to fit a modest LDS budget
-// PMODE 4 keeps extension and shadow pairs in one list: 64 * meshes entries always fit the extension pairs; the
-// shadow pairs get what is left of a 10-KB LDS budget (16 waves per CU), at least 64 (one mesh per pass), at most
-// another 64 * meshes (everything in one pass)
-int merged_pair_cap(const ptrt_ctx *c) {
-    const size_t rest = (size_t)c->pair_meshes * 32 + 512 + 256 + (size_t)c->stack_entries * 64 * sizeof(uint2) + pt::LEAF_PAIR_BYTES + 24;
-    const int lo = 64 * c->pair_meshes + 64, hi = 128 * c->pair_meshes;
-    int cap = rest < 10240 ? (int)((10240 - rest) / 2) / 64 * 64 : 0;
-    cap = cap < lo ? lo : cap;
-    return cap > hi ? hi : cap;
-}
 size_t pair_lds_bytes(const ptrt_ctx *c, int pmode) {
     if (pmode == 4)
         return (size_t)c->pair_meshes * 32 + 512 + 256 + (size_t)merged_pair_cap(c) * 2 +
@@ -1183,25 +1177,6 @@ int run_bloom(ptrt_ctx *c, float *image, int w, int h, unsigned char *rgb8) {
     return PTRT_OK;
 }
 
-void free_present(ptrt_ctx *c) {
-    for (auto &s : c->present) {
-        if (s.dev)
-            (void)hipFree(s.dev);
-        if (s.host)
-            (void)hipHostFree(s.host);
-        if (s.rendered)
-            (void)hipEventDestroy(s.rendered);
-        if (s.done)
-            (void)hipEventDestroy(s.done);
-    }
-    c->present.clear();
-    if (c->present_stream) {
-        (void)hipStreamSynchronize(c->present_stream);
-        (void)hipStreamDestroy(c->present_stream);
-        c->present_stream = nullptr;
-    }
-}
-
 void free_post(ptrt_ctx *c) {
     dfree(c->s_accum);
     dfree(c->s_normal);
@@ -1214,6 +1189,8 @@ void free_post(ptrt_ctx *c) {
 
 } // namespace
 
+#include "ptrt_present.hip.h"
+
 // =====================================================================================
 extern "C" {
 
@@ -1223,45 +1200,6 @@ const char *ptrt_last_error(const ptrt_ctx *ctx) {
     if (ctx && ctx_live(const_cast<ptrt_ctx *>(ctx), false))
         return ctx->err.c_str();
     return g_last_error.c_str();
-}
-
-namespace {
-int create_ctx(int full_w, int full_h, int tile_y0, int tile_rows, int il_period, int il_phase, int device, ptrt_ctx **out);
-}
-
-int ptrt_create(int full_w, int full_h, int tile_y0, int tile_rows, int device, ptrt_ctx **out) {
-    if (!out)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_create: out is NULL");
-    *out = nullptr;
-    if (full_w <= 0 || full_h <= 0)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_create: bad frame size %dx%d", full_w, full_h);
-    if (tile_rows <= 0) {
-        tile_y0 = 0;
-        tile_rows = full_h;
-    }
-    if (tile_y0 < 0 || tile_y0 + tile_rows > full_h)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_create: tile rows [%d,%d) outside 0..%d", tile_y0,
-                    tile_y0 + tile_rows, full_h);
-    return create_ctx(full_w, full_h, tile_y0, tile_rows, 1, 0, device, out);
-}
-
-int ptrt_create_interleaved(int full_w, int full_h, int phase, int period, int device, ptrt_ctx **out) {
-    if (!out)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_create_interleaved: out is NULL");
-    *out = nullptr;
-    if (full_w <= 0 || full_h <= 0)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_create_interleaved: bad frame size %dx%d", full_w, full_h);
-    const int strips = (full_h + 7) / 8;
-    if (period < 1 || phase < 0 || phase >= period || phase >= strips)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_create_interleaved: strip %d of every %d (the frame has %d strips of 8 rows)",
-                    phase, period, strips);
-    if (period == 1)
-        return create_ctx(full_w, full_h, 0, full_h, 1, 0, device, out);
-    // rows of the strips phase, phase + period, ...; only the frame's last strip can be short, and it is the owner's last
-    int rows = 0;
-    for (int t = phase; t < strips; t += period)
-        rows += (t * 8 + 8 <= full_h) ? 8 : full_h - t * 8;
-    return create_ctx(full_w, full_h, phase * 8, rows, period, phase, device, out);
 }
 
 namespace {
@@ -1337,6 +1275,41 @@ int create_ctx(int full_w, int full_h, int tile_y0, int tile_rows, int il_period
     return PTRT_OK;
 }
 } // namespace
+
+int ptrt_create(int full_w, int full_h, int tile_y0, int tile_rows, int device, ptrt_ctx **out) {
+    if (!out)
+        return fail(nullptr, PTRT_E_INVALID, "ptrt_create: out is NULL");
+    *out = nullptr;
+    if (full_w <= 0 || full_h <= 0)
+        return fail(nullptr, PTRT_E_INVALID, "ptrt_create: bad frame size %dx%d", full_w, full_h);
+    if (tile_rows <= 0) {
+        tile_y0 = 0;
+        tile_rows = full_h;
+    }
+    if (tile_y0 < 0 || tile_y0 + tile_rows > full_h)
+        return fail(nullptr, PTRT_E_INVALID, "ptrt_create: tile rows [%d,%d) outside 0..%d", tile_y0,
+                    tile_y0 + tile_rows, full_h);
+    return create_ctx(full_w, full_h, tile_y0, tile_rows, 1, 0, device, out);
+}
+
+int ptrt_create_interleaved(int full_w, int full_h, int phase, int period, int device, ptrt_ctx **out) {
+    if (!out)
+        return fail(nullptr, PTRT_E_INVALID, "ptrt_create_interleaved: out is NULL");
+    *out = nullptr;
+    if (full_w <= 0 || full_h <= 0)
+        return fail(nullptr, PTRT_E_INVALID, "ptrt_create_interleaved: bad frame size %dx%d", full_w, full_h);
+    const int strips = (full_h + 7) / 8;
+    if (period < 1 || phase < 0 || phase >= period || phase >= strips)
+        return fail(nullptr, PTRT_E_INVALID, "ptrt_create_interleaved: strip %d of every %d (the frame has %d strips of 8 rows)",
+                    phase, period, strips);
+    if (period == 1)
+        return create_ctx(full_w, full_h, 0, full_h, 1, 0, device, out);
+    // rows of the strips phase, phase + period, ...; only the frame's last strip can be short, and it is the owner's last
+    int rows = 0;
+    for (int t = phase; t < strips; t += period)
+        rows += (t * 8 + 8 <= full_h) ? 8 : full_h - t * 8;
+    return create_ctx(full_w, full_h, phase * 8, rows, period, phase, device, out);
+}
 
 void ptrt_destroy(ptrt_ctx *c) {
     {
@@ -1418,7 +1391,7 @@ void ptrt_destroy(ptrt_ctx *c) {
     dfree(c->d_env);
     free_denoiser(c);
     free_post(c);
-    free_present(c);
+    c->present.free();
     for (auto &ev : c->ev_ring)
         if (ev)
             (void)hipEventDestroy(ev);
@@ -2941,206 +2914,6 @@ int ptrt_sync(ptrt_ctx *c) {
     return PTRT_OK;
 }
 
-int ptrt_present_destroy(ptrt_ctx *c) {
-    if (!ctx_live(c))
-        return fail(c, PTRT_E_INVALID, "ptrt_present_destroy: bad context");
-    if (c->present.empty())
-        return PTRT_OK;
-    if (int rc = set_device(c))
-        return rc;
-    (void)hipStreamSynchronize(c->stream);
-    free_present(c);
-    return PTRT_OK;
-}
-
-int ptrt_present_create(ptrt_ctx *c, int slots) {
-    if (!ctx_live(c) || slots < 1 || slots > 8)
-        return fail(c, PTRT_E_INVALID, "ptrt_present_create: 1..8 slots");
-    if (int rc = ptrt_present_destroy(c))
-        return rc;
-    const size_t bytes = c->npix * 3;
-    c->present.resize((size_t)slots);
-    for (auto &s : c->present) {
-        HIP_TRY(c, hipMalloc((void **)&s.dev, bytes));
-        HIP_TRY(c, hipHostMalloc((void **)&s.host, bytes, hipHostMallocDefault));
-        HIP_TRY(c, hipEventCreateWithFlags(&s.rendered, hipEventDisableTiming));
-        HIP_TRY(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    }
-    if (!c->present_stream)
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->present_stream, hipStreamNonBlocking));
-    return PTRT_OK;
-}
-
-int ptrt_present_map(ptrt_ctx *c, int slot, void **device_pixels) {
-    if (!ctx_live(c) || !device_pixels || slot < 0 || slot >= (int)c->present.size())
-        return fail(c, PTRT_E_INVALID, "ptrt_present_map: no such slot (ptrt_present_create first)");
-    if (int rc = set_device(c))
-        return rc;
-    auto &s = c->present[(size_t)slot];
-    if (s.in_flight) { // the frame about to be overwritten must have reached the host
-        HIP_TRY(c, hipEventSynchronize(s.done));
-        s.in_flight = false;
-    }
-    *device_pixels = s.dev;
-    return PTRT_OK;
-}
-
-int ptrt_present_unmap(ptrt_ctx *c, int slot) {
-    if (!ctx_live(c) || slot < 0 || slot >= (int)c->present.size())
-        return fail(c, PTRT_E_INVALID, "ptrt_present_unmap: no such slot");
-    if (int rc = set_device(c))
-        return rc;
-    auto &s = c->present[(size_t)slot];
-    // the download runs on its own stream behind an event, so it overlaps the NEXT frame's kernels
-    // (a copy enqueued on the render stream would only be asynchronous to the host)
-    HIP_TRY(c, hipEventRecord(s.rendered, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->present_stream, s.rendered, 0));
-    HIP_TRY(c, hipMemcpyAsync(s.host, s.dev, c->npix * 3, hipMemcpyDeviceToHost, c->present_stream));
-    HIP_TRY(c, hipEventRecord(s.done, c->present_stream));
-    s.in_flight = true;
-    return PTRT_OK;
-}
-
-int ptrt_present_acquire(ptrt_ctx *c, int slot, const unsigned char **host_pixels) {
-    if (!ctx_live(c) || !host_pixels || slot < 0 || slot >= (int)c->present.size())
-        return fail(c, PTRT_E_INVALID, "ptrt_present_acquire: no such slot");
-    if (int rc = set_device(c))
-        return rc;
-    auto &s = c->present[(size_t)slot];
-    if (s.in_flight) {
-        HIP_TRY(c, hipEventSynchronize(s.done));
-        s.in_flight = false;
-    }
-    *host_pixels = s.host;
-    return PTRT_OK;
-}
-
-namespace {
-bool ring_live(ptrt_ring *r) {
-    std::lock_guard<std::mutex> lock(g_ring_mutex);
-    return r && g_rings.count(r);
-}
-void ring_free(ptrt_ring *r) {
-    (void)hipSetDevice(r->device);
-    if (r->copy_stream) {
-        (void)hipStreamSynchronize(r->copy_stream);
-        (void)hipStreamDestroy(r->copy_stream);
-    }
-    for (auto &s : r->slots) {
-        if (s.dev)
-            (void)hipFree(s.dev);
-        if (s.host)
-            (void)hipHostFree(s.host);
-        if (s.rendered)
-            (void)hipEventDestroy(s.rendered);
-        if (s.done)
-            (void)hipEventDestroy(s.done);
-    }
-    delete r;
-}
-} // namespace
-
-int ptrt_ring_create(int device, size_t frame_bytes, int slots, ptrt_ring **out) {
-    if (!out)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_ring_create: out is NULL");
-    *out = nullptr;
-    if (frame_bytes == 0 || slots < 1 || slots > 8)
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_ring_create: %zu bytes, %d slots (1..8)", frame_bytes, slots);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, PTRT_E_NO_DEVICE, "no HIP device available; this library has no CPU path");
-    if (device < 0 || device >= ndev)
-        return fail(nullptr, PTRT_E_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    ptrt_ring *r = new ptrt_ring;
-    r->device = device;
-    r->bytes = frame_bytes;
-    r->slots.resize((size_t)slots);
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess)
-        e = hipStreamCreateWithFlags(&r->copy_stream, hipStreamNonBlocking);
-    for (auto &s : r->slots) {
-        if (e == hipSuccess)
-            e = hipMalloc((void **)&s.dev, frame_bytes);
-        if (e == hipSuccess)
-            e = hipHostMalloc((void **)&s.host, frame_bytes, hipHostMallocDefault);
-        if (e == hipSuccess)
-            e = hipEventCreateWithFlags(&s.rendered, hipEventDisableTiming);
-        if (e == hipSuccess)
-            e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-    }
-    if (e != hipSuccess) {
-        ring_free(r);
-        return fail(nullptr, PTRT_E_HIP, "ptrt_ring_create: %s", hipGetErrorString(e));
-    }
-    {
-        std::lock_guard<std::mutex> lock(g_ring_mutex);
-        g_rings.insert(r);
-    }
-    *out = r;
-    return PTRT_OK;
-}
-
-int ptrt_ring_map(ptrt_ring *r, int slot, void **device_pixels) {
-    if (!ring_live(r) || !device_pixels || slot < 0 || slot >= (int)r->slots.size())
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_ring_map: bad ring or slot");
-    HIP_TRY(nullptr, hipSetDevice(r->device));
-    auto &s = r->slots[(size_t)slot];
-    if (s.in_flight) { // the frame about to be overwritten must have reached the host
-        HIP_TRY(nullptr, hipEventSynchronize(s.done));
-        s.in_flight = false;
-    }
-    {
-        std::lock_guard<std::mutex> lock(g_ring_mutex);
-        s.marked = false;
-    }
-    *device_pixels = s.dev;
-    return PTRT_OK;
-}
-
-int ptrt_ring_unmap(ptrt_ring *r, int slot) {
-    if (!ring_live(r) || slot < 0 || slot >= (int)r->slots.size())
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_ring_unmap: bad ring or slot");
-    HIP_TRY(nullptr, hipSetDevice(r->device));
-    auto &s = r->slots[(size_t)slot];
-    bool marked;
-    {
-        std::lock_guard<std::mutex> lock(g_ring_mutex);
-        marked = s.marked;
-    }
-    // a slot not written through ptrt_render: behind everything already submitted to the device's blocking
-    // streams, which is what cudaGraphicsUnmapResources guarantees the GL side
-    if (!marked)
-        HIP_TRY(nullptr, hipEventRecord(s.rendered, nullptr));
-    HIP_TRY(nullptr, hipStreamWaitEvent(r->copy_stream, s.rendered, 0));
-    HIP_TRY(nullptr, hipMemcpyAsync(s.host, s.dev, r->bytes, hipMemcpyDeviceToHost, r->copy_stream));
-    HIP_TRY(nullptr, hipEventRecord(s.done, r->copy_stream));
-    s.in_flight = true;
-    return PTRT_OK;
-}
-
-int ptrt_ring_acquire(ptrt_ring *r, int slot, const unsigned char **host_pixels) {
-    if (!ring_live(r) || !host_pixels || slot < 0 || slot >= (int)r->slots.size())
-        return fail(nullptr, PTRT_E_INVALID, "ptrt_ring_acquire: bad ring or slot");
-    HIP_TRY(nullptr, hipSetDevice(r->device));
-    auto &s = r->slots[(size_t)slot];
-    if (s.in_flight) {
-        HIP_TRY(nullptr, hipEventSynchronize(s.done));
-        s.in_flight = false;
-    }
-    *host_pixels = s.host;
-    return PTRT_OK;
-}
-
-void ptrt_ring_destroy(ptrt_ring *r) {
-    {
-        std::lock_guard<std::mutex> lock(g_ring_mutex);
-        if (!r || !g_rings.count(r))
-            return;
-        g_rings.erase(r);
-    }
-    ring_free(r);
-}
-
 int ptrt_last_kernel_ms(ptrt_ctx *c, float *trace_ms, float *tonemap_ms) {
     if (!ctx_live(c) || !c->timed)
         return fail(c, PTRT_E_NOT_READY, "ptrt_last_kernel_ms: nothing rendered yet");
@@ -3272,16 +3045,12 @@ int ptrt_read_buffer(ptrt_ctx *c, int kind, void *dst, size_t bytes) {
     if (kind == PTRT_BUF_RGB8 && !src) // (the last frame went straight into a caller's frame: PTRT_OUT_DEVICE_FRAME)
         return fail(c, PTRT_E_NOT_READY, "ptrt_read_buffer: the last frame was written into the caller's frame, the context holds no RGB8 image of it");
     if (kind == PTRT_BUF_RNG) {
-        uint32_t *tmp = nullptr;
-        HIP_TRY(c, hipMalloc((void **)&tmp, need));
+        DeviceTemp<uint32_t> tmp;
+        HIP_TRY(c, tmp.alloc(c->npix * 6));
         hipLaunchKernelGGL(pt::rng_planar_to_aos, dim3((unsigned)((c->npix + 255) / 256)), dim3(256), 0, c->stream,
-                           c->d_rng, tmp, c->npix);
-        hipError_t e = hipMemcpyAsync(dst, tmp, need, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(c->stream);
-        (void)hipFree(tmp);
-        if (e != hipSuccess)
-            return fail(c, PTRT_E_HIP, "RNG read-back failed: %s", hipGetErrorString(e));
+                           c->d_rng, tmp.p, c->npix);
+        HIP_TRY(c, hipMemcpyAsync(dst, tmp.p, need, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         return PTRT_OK;
     }
     HIP_TRY(c, hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, c->stream));
@@ -3294,17 +3063,12 @@ int ptrt_write_rng(ptrt_ctx *c, const uint32_t *states, size_t bytes) {
         return fail(c, PTRT_E_INVALID, "ptrt_write_rng: bad argument");
     if (int rc = set_device(c))
         return rc;
-    uint32_t *tmp = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&tmp, c->npix * 24));
-    hipError_t e = hipMemcpyAsync(tmp, states, c->npix * 24, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pt::rng_aos_to_planar, dim3((unsigned)((c->npix + 255) / 256)), dim3(256), 0, c->stream, tmp,
-                           c->d_rng, c->npix);
-        e = hipStreamSynchronize(c->stream);
-    }
-    (void)hipFree(tmp);
-    if (e != hipSuccess)
-        return fail(c, PTRT_E_HIP, "RNG upload failed: %s", hipGetErrorString(e));
+    DeviceTemp<uint32_t> tmp;
+    HIP_TRY(c, tmp.alloc(c->npix * 6));
+    HIP_TRY(c, hipMemcpyAsync(tmp.p, states, c->npix * 24, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(pt::rng_aos_to_planar, dim3((unsigned)((c->npix + 255) / 256)), dim3(256), 0, c->stream, tmp.p,
+                       c->d_rng, c->npix);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->rng_ready = true;
     return PTRT_OK;
 }
@@ -3388,30 +3152,18 @@ int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, 
     if (int rc = set_device(c))
         return rc;
     // host staging around the CLOSEST query of ptrt_query_rays
-    float *d_o = nullptr, *d_d = nullptr;
-    pt::HitOut *d_h = nullptr;
-    int rc = PTRT_OK;
-    hipError_t e = hipMalloc((void **)&d_o, (size_t)n * 12);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_d, (size_t)n * 12);
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_h, (size_t)n * sizeof(pt::HitOut));
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_o, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_d, directions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        rc = launch_query(c, PTRT_QUERY_CLOSEST, d_o, d_d, nullptr, (size_t)n, d_h);
-    if (e == hipSuccess && rc == PTRT_OK)
-        e = hipMemcpyAsync(out, d_h, (size_t)n * sizeof(pt::HitOut), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && rc == PTRT_OK)
-        e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-        rc = fail(c, PTRT_E_HIP, "ptrt_trace_rays: %s", hipGetErrorString(e));
-    (void)hipFree(d_o);
-    (void)hipFree(d_d);
-    (void)hipFree(d_h);
-    return rc;
+    DeviceTemp<float> d_o, d_d;
+    DeviceTemp<pt::HitOut> d_h;
+    HIP_TRY(c, d_o.alloc((size_t)n * 3));
+    HIP_TRY(c, d_d.alloc((size_t)n * 3));
+    HIP_TRY(c, d_h.alloc((size_t)n));
+    HIP_TRY(c, hipMemcpyAsync(d_o.p, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_d.p, directions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    if (int rc = launch_query(c, PTRT_QUERY_CLOSEST, d_o.p, d_d.p, nullptr, (size_t)n, d_h.p))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, d_h.p, (size_t)n * sizeof(pt::HitOut), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PTRT_OK;
 }
 
 int ptrt_query_rays(ptrt_ctx *c, int kind, const float *origins, const float *directions, const float *tmax, int n, void *out) {
@@ -3516,285 +3268,9 @@ int ptrt_get_stats(ptrt_ctx *c, ptrt_stats *out) {
     return PTRT_OK;
 }
 
-int ptrt_set_option(ptrt_ctx *c, const char *name, long long value) {
-    if (!ctx_live(c, false) || !name)
-        return fail(c, PTRT_E_INVALID, "ptrt_set_option: bad argument");
-    const std::string n(name);
-    if (n == "count_rays")
-        c->count_rays = value ? 1 : 0;
-    else if (n == "force_geom") { // -1 auto; 1 / 2 force a more general traversal variant (tests)
-        if (value < -1 || value > 2)
-            return fail(c, PTRT_E_INVALID, "force_geom must be -1..2");
-        c->force_geom = (int)value;
-    } else if (n == "force_full")
-        c->force_full = value ? 1 : 0;
-    else if (n == "pair_trace") // 0: lock-step mesh loop instead of (ray, mesh) pair compaction (A/B, tests)
-        c->pair_trace = value ? 1 : 0;
-    else if (n == "steal") { // PMODE 2 shadow rays: 0 = no subtree stealing; n = node steps between steal rounds
-        if (value < 0 || value > 64)
-            return fail(c, PTRT_E_INVALID, "steal must be 0..64");
-        c->steal = (int)value;
-    } else if (n == "csteal") { // PMODE 2 closest hit: 0 = no subtree stealing; n = node steps between steal rounds (verified: same bits)
-        if (value < 0 || value > 64)
-            return fail(c, PTRT_E_INVALID, "csteal must be 0..64");
-        c->csteal = (int)value;
-    } else if (n == "atrous_exp")
-        c->atrous_exp = value ? 1 : 0;
-    else if (n == "csteal_follow")
-        c->csteal_follow = value ? 1 : 0;
-    else if (n == "csteal_leaf_min") {
-        if (value < 1 || value > 64)
-            return fail(c, PTRT_E_INVALID, "csteal_leaf_min must be 1..64");
-        c->csteal_leaf_min = (int)value;
-    }
-    else if (n == "csteal_min") {
-        if (value < 0 || value > 1024)
-            return fail(c, PTRT_E_INVALID, "csteal_min must be 0..1024");
-        c->csteal_min = (int)value;
-    } else if (n == "lds_nodes") // PMODE 2 in 4-wave workgroups with the BLAS top levels staged in LDS (A/B, tests)
-        c->lds_nodes = value < 0 ? 0 : (value > 2 ? 2 : (int)value); // (2: the larger workgroups without reading the staged nodes)
-    else if (n == "merged") // PMODE 4 instead of 2: shadow rays ride with the next extension rays (A/B, tests)
-        c->merged = value < 0 ? -1 : (value ? 1 : 0);
-    else if (n == "leaf_pairs") // PMODE 2: 0 = every lane walks its own leaf (A/B, tests)
-        c->leaf_pairs = value ? 1 : 0;
-    else if (n == "lds_pad") { // extra bytes of LDS per workgroup: fewer waves per CU (A/B of the occupancy, tests)
-        if (value < 0 || value > 32768)
-            return fail(c, PTRT_E_INVALID, "lds_pad must be 0..32768");
-        c->lds_pad = (int)value;
-    }
-    else if (n == "time_kernels") // 0: no start / stop events around the trace kernel (two driver calls per frame; ptrt_kernel_ms_history then has nothing)
-        c->time_kernels = value ? 1 : 0;
-    else if (n == "time_launches") // 1: events around every launch of a frame dealt to the auxiliary streams (ptrt_launch_ms_history)
-        c->time_launches = value ? 1 : 0;
-    else if (n == "tm_prio") // lane refill's tonemap pass: | 1 on a stream of the highest priority, | 2 its waves at s_setprio 3
-        c->tm_prio = (int)(value & 3);
-    else if (n == "pipeline") // 1 (default): consecutive frames may overlap on the device when that is safe (ptrt_render); 0: never
-        c->pipeline = value ? 1 : 0;
-    else if (n == "persist")
-        c->persist = value < 0 ? 0 : value;
-    else if (n == "sample_sync")
-        c->sample_sync = value < 0 ? -1 : (value != 0);
-    else if (n == "tile_run") {
-        if (value < 0 || value > 64)
-            return fail(c, PTRT_E_INVALID, "tile_run: 0 (tile k on workgroup k) or the tiles per XCD and run, 1..64");
-        c->tile_run = value;
-    }
-    else if (n == "ticket_tiles")
-        c->ticket_tiles = value < 1 ? 1 : (value > 16 ? 16 : (int)value);
-    else if (n == "refill")
-        c->refill = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (n == "split") { // tile rows of the frame dealt to that many concurrent launches of the megakernel (1 = one launch)
-        if (value < 1 || value > ptrt_ctx::MAX_SPLIT)
-            return fail(c, PTRT_E_INVALID, "split must be 1..%d", ptrt_ctx::MAX_SPLIT);
-        c->split = (int)value;
-    } else if (n == "tlas_rounds") // PMODE 3 shadow rays: one TLAS leaf per ray and fill instead of all of them (A/B, tests)
-        c->tlas_rounds = value ? 1 : 0;
-    else if (n == "pm1_wg") { // PMODE 1: one or two tiles per workgroup (0 = choose by the LDS budget; A/B, tests)
-        if (value < 0 || value > 20)
-            return fail(c, PTRT_E_INVALID, "pm1_wg must be 0..2");
-        c->pm1_wg = (int)value;
-    }
-    else if (n == "stage") // PMODE 1: shading inputs staged in LDS (0 none; else jitter inputs, | 1 lights, | 2 materials; A/B, tests)
-        c->stage = (int)(value & 7);
-    else if (n == "pair_split") // PMODE 1: 0 = one lane per pair also in batches that do not fill the wave (A/B, tests)
-        c->pair_split = value ? 1 : 0;
-    else if (n == "async_lanes") // 1: persistent megakernel with asynchronous lanes for single-leaf-TLAS scenes
-        c->async_lanes = value ? 1 : 0;
-    else if (n == "shade_min") { // async_lanes: lanes that wait for the shading block before it runs
-        if (value < 1 || value > 64)
-            return fail(c, PTRT_E_INVALID, "shade_min must be 1..64");
-        c->shade_min = (int)value;
-    } else if (n == "leaf_min") { // PMODE 2 and async_lanes: lanes waiting at a leaf that end the node loop
-        if (value < 1 || value > 64)
-            return fail(c, PTRT_E_INVALID, "leaf_min must be 1..64");
-        c->leaf_min = c->as_leaf_min = (int)value;
-    } else if (n == "wavefront") // 1: trace/shade stages over the whole frame's rays instead of the megakernel
-        c->wavefront = value ? 1 : 0;
-    else if (n == "wf_sort") // wavefront stages: the shade stage sorts its paths by class (material, bounce) in LDS first, 1 / 2 / 4 groups of 256 together
-        c->wf_sort = value <= 0 ? 0 : (value >= 4 ? 4 : (value >= 2 ? 2 : 1));
-    else if (n == "fetch_min") { // PMODE 2: refill threshold in idle lanes; 0 = static batches of 64 pairs (A/B, tests)
-        if (value < 0 || value > 64)
-            return fail(c, PTRT_E_INVALID, "fetch_min must be 0..64");
-        c->fetch_min = (int)value;
-    } else if (n == "denoiser_active") // perfSettings.enableDenoiser: use the (already allocated) denoiser or not
-        c->dn_active = value ? 1 : 0;
-    else if (n == "motion_vectors") // perfSettings.enableMotionVectors
-        c->mv_active = value ? 1 : 0;
-    else if (n == "use_graphs") // 0: issue the refit / rebuild launches one by one instead of replaying a hipGraph
-        c->use_graphs = value ? 1 : 0;
-    else
-        return fail(c, PTRT_E_INVALID, "unknown option '%s'", name);
-    return PTRT_OK;
-}
-
-// what ptrt_set_option set, plus read-only facts about the last ptrt_render (so that a measurement can say what ran)
-int ptrt_get_option(ptrt_ctx *c, const char *name, long long *value) {
-    if (!ctx_live(c, false) || !name || !value)
-        return fail(c, PTRT_E_INVALID, "ptrt_get_option: bad argument");
-    const std::string n(name);
-    const std::pair<const char *, long long> tab[] = {
-        {"count_rays", c->count_rays}, {"force_geom", c->force_geom}, {"force_full", c->force_full}, {"pair_trace", c->pair_trace},
-        {"steal", c->steal}, {"csteal", c->csteal}, {"csteal_min", c->csteal_min}, {"csteal_follow", c->csteal_follow}, {"atrous_exp", c->atrous_exp}, {"csteal_leaf_min", c->csteal_leaf_min}, {"lds_nodes", c->lds_nodes}, {"merged", c->merged}, {"leaf_pairs", c->leaf_pairs}, {"lds_pad", c->lds_pad},
-        {"stage", c->stage}, {"pm1_wg", c->pm1_wg}, {"tlas_rounds", c->tlas_rounds}, {"time_kernels", c->time_kernels}, {"time_launches", c->time_launches}, {"tm_prio", c->tm_prio}, {"persist", c->persist}, {"refill", c->refill}, {"sample_sync", c->sample_sync}, {"sample_sync_eff", c->sample_sync_eff}, {"tile_run", c->tile_run}, {"ticket_tiles", c->ticket_tiles}, {"refilled", c->refill_eff ? 1 : 0}, {"split", c->split}, {"split_eff", c->split_eff}, {"pipeline", c->pipeline}, {"pipelined", c->pipelined_last ? 1 : 0}, {"pair_split", c->pair_split}, {"async_lanes", c->async_lanes}, {"shade_min", c->shade_min},
-        {"leaf_min", c->leaf_min}, {"wavefront", c->wavefront}, {"wf_sort", c->wf_sort}, {"fetch_min", c->fetch_min}, {"denoiser_active", c->dn_active},
-        {"motion_vectors", c->mv_active}, {"use_graphs", c->use_graphs},
-        // read-only: the last launch
-        {"render_mode", c->last_mode},   // 0 megakernel, 1 wavefront stages, 2 asynchronous lanes
-        {"pmode", c->last_pmode},        // PMODE of the megakernel: 0 lock-step, 1 pairs/LDS triangles, 2 queue, 3 TLAS rounds, 4 merged queue
-        {"merged_eff", c->merged_eff},   // loop shape of the last launch (1 = shadow rays ride with the next extension rays)
-        {"merged_decided", (c->merged >= 0 || c->tune_choice >= 0 || !c->last_merged_possible) ? 1 : 0}, // 0 while "merged" = -1 is still sampling
-        {"launches", (long long)c->launches},
-        {"query_pmode", c->query_pmode}, // traversal of the last ptrt_query_rays / ptrt_trace_rays: 0 one ray per lane, 1..3 pairs
-        {"inst_pre_ok", c->inst_pre_ok ? 1 : 0}, // the instances' first-pass boxes (PMODE 3) match the device's root boxes and matrices
-        {"tlas_refits", c->tlas_refits},         // ptrt_refit_tlas calls since the last geometry upload
-        {"stream", (long long)(intptr_t)c->stream}, // the hipStream_t the context enqueues on (stream-ordering its device results)
-    };
-    for (const auto &e : tab)
-        if (n == e.first) {
-            *value = e.second;
-            return PTRT_OK;
-        }
-    return fail(c, PTRT_E_INVALID, "unknown option '%s'", name);
-}
-
-// test hook: which kernels rendered the last frame (0 megakernel, 1 wavefront stages)
-int ptrt_debug_last_render_mode(ptrt_ctx *c) { return ctx_live(c) ? c->last_mode : -1; }
-
-// profiling hook (not part of the drop-in surface): reads and clears pt::g_trav_stats (32 words); all zero unless
-// the library was built with -DPT_TRAV_STATS
-int ptrt_debug_trav_stats(ptrt_ctx *c, unsigned long long *out32) {
-    if (!ctx_live(c) || !out32)
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_trav_stats: bad argument");
-    if (int rc = set_device(c))
-        return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpyFromSymbol(out32, HIP_SYMBOL(pt::g_trav_stats), 32 * sizeof(unsigned long long)));
-    unsigned long long zero[32] = {};
-    HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(pt::g_trav_stats), zero, sizeof(zero)));
-    return PTRT_OK;
-}
-
-// ... and pt::g_trav_bounce (64 words: the sixteen traversal counters split by the rays' bounce 0, 1, 2, >= 3)
-int ptrt_debug_trav_bounce(ptrt_ctx *c, unsigned long long *out64) {
-    if (!ctx_live(c) || !out64)
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_trav_bounce: bad argument");
-    if (int rc = set_device(c))
-        return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpyFromSymbol(out64, HIP_SYMBOL(pt::g_trav_bounce), 64 * sizeof(unsigned long long)));
-    unsigned long long zero[64] = {};
-    HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(pt::g_trav_bounce), zero, sizeof(zero)));
-    return PTRT_OK;
-}
-
-#ifdef PT_TRAV_STATS
-int ptrt_debug_trav_dbg(ptrt_ctx *c, unsigned long long *out1033) {
-    if (!ctx_live(c) || !out1033)
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_trav_dbg: bad argument");
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpyFromSymbol(out1033, HIP_SYMBOL(pt::g_trav_dbg), 1033 * sizeof(unsigned long long)));
-    static unsigned long long zero[1033] = {};
-    HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(pt::g_trav_dbg), zero, sizeof(zero)));
-    return PTRT_OK;
-}
-#endif
-
-// test hook: exhaustive rcp_ieee check; out9[0] = mismatches, out9[1..8] = first offending inputs
-int ptrt_debug_rcp_check(ptrt_ctx *c, unsigned int *out9) {
-    if (!ctx_live(c) || !out9)
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_rcp_check: bad argument");
-    if (int rc = set_device(c))
-        return rc;
-    unsigned int *d = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d, 9 * sizeof(unsigned int)));
-    HIP_TRY(c, hipMemset(d, 0, 9 * sizeof(unsigned int)));
-    hipLaunchKernelGGL(pt::rcp_check_kernel, dim3(4096), dim3(256), 0, c->stream, d);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out9, d, 9 * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    return PTRT_OK;
-}
-
-// test hook: exhaustive sqrt_ieee check; out9[0] = mismatches, out9[1] = mismatches of the bare core in its range, out9[2..8] = inputs
-int ptrt_debug_sqrt_check(ptrt_ctx *c, unsigned int *out9) {
-    if (!ctx_live(c) || !out9)
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_sqrt_check: bad argument");
-    if (int rc = set_device(c))
-        return rc;
-    unsigned int *d = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d, 9 * sizeof(unsigned int)));
-    HIP_TRY(c, hipMemset(d, 0, 9 * sizeof(unsigned int)));
-    hipLaunchKernelGGL(pt::sqrt_check_kernel, dim3(4096), dim3(256), 0, c->stream, d);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out9, d, 9 * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    return PTRT_OK;
-}
-
-// test hook: div3's core for the divisors 1.m, m in [first, first + count), against every numerator significand (mode 0), or
-// div3 with out-of-range exponents (modes 1, 2); out9[0] = mismatches, out9[1..8] = first offending {a, t} bit patterns
-int ptrt_debug_div3_check(ptrt_ctx *c, unsigned int first, unsigned int count, int mode, unsigned int *out9) {
-    if (!ctx_live(c) || !out9 || count == 0 || count > (1u << 23) || mode < 0 || mode > 3)
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_div3_check: bad argument");
-    if (int rc = set_device(c))
-        return rc;
-    unsigned int *d = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d, 9 * sizeof(unsigned int)));
-    HIP_TRY(c, hipMemset(d, 0, 9 * sizeof(unsigned int)));
-    hipLaunchKernelGGL(pt::div3_check_kernel, dim3((count + 63) / 64), dim3(64), 0, c->stream, first, count, mode, d);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out9, d, 9 * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    return PTRT_OK;
-}
-
-// test hook (not part of the drop-in surface): the kernels' deterministic math on the GPU
-int ptrt_debug_detmath(ptrt_ctx *c, int op, const float *x, const float *y, int n, float *out) {
-    if (!ctx_live(c) || !x || !out || n <= 0)
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_detmath: bad argument");
-    if (int rc = set_device(c))
-        return rc;
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&dx, (size_t)n * 4));
-    HIP_TRY(c, hipMalloc((void **)&dy, (size_t)n * 4));
-    HIP_TRY(c, hipMalloc((void **)&dout, (size_t)n * 4));
-    HIP_TRY(c, hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(dy, y ? y : x, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pt::detmath_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, op, dx, dy, n, dout);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    (void)hipFree(dout);
-    return PTRT_OK;
-}
-
-// test hook: the shading functions one by one on the device (pt::shade_probe_kernel) over the context's uploaded materials;
-// op 0: n items of 11 floats -> 4 floats each; op 1: n items of 14 -> 13 (see the kernel).  full = 0: the simple-material variant
-int ptrt_debug_shade(ptrt_ctx *c, int op, int full, const float *in, int n, float *out) {
-    if (!ctx_live(c) || !in || !out || n <= 0 || (op != 0 && op != 1))
-        return fail(c, PTRT_E_INVALID, "ptrt_debug_shade: bad argument");
-    if (!c->have_materials)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_debug_shade: materials not uploaded");
-    if (int rc = set_device(c))
-        return rc;
-    const size_t ni = (size_t)n * (op == 0 ? 11 : 14) * 4, no = (size_t)n * (op == 0 ? 4 : 13) * 4;
-    float *din = nullptr, *dout = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&din, ni));
-    HIP_TRY(c, hipMalloc((void **)&dout, no));
-    HIP_TRY(c, hipMemcpy(din, in, ni, hipMemcpyHostToDevice));
-    if (full)
-        hipLaunchKernelGGL(pt::shade_probe_kernel<true>, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->d_materials, op, din, n, dout);
-    else
-        hipLaunchKernelGGL(pt::shade_probe_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->d_materials, op, din, n, dout);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out, dout, no, hipMemcpyDeviceToHost));
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    return PTRT_OK;
-}
-
 } // extern "C"
+
+#include "ptrt_options.hip.h"
 
 #include "ptrt_farm.hip.h"
 
