@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
+#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
 
 enum {
     PTRT_OK = 0,
@@ -304,12 +304,31 @@ int ptrt_read_prim_order(ptrt_ctx *ctx, int mesh_index, int32_t *prim_indices_ou
  * no allocation after the first call, root boxes untouched.  A flag that changes the traversal variant takes effect with
  * the next launch.  PTRT_E_INVALID (nothing enqueued) for a range outside the uploaded meshes, a negative count or NULL.
  *
+ * ptrt_set_instance_transforms_device: the same records, ranges and refusals, the records lying in DEVICE memory that is
+ * ordered on the context's stream (the convention of ptrt_query_rays and verts_on_device).  One scatter launch reads them in
+ * place: no copy, no staging, no synchronisation.  World, inverse and normal matrices remain the caller's to compute.  The
+ * context's host copy of these fields lags afterwards and is fetched (a synchronisation) by the next call that needs it -- a
+ * material upload; until then the growth factor of the instances' first-pass boxes stays what the host last knew, and an
+ * instance it does not cover is tested without that box: slower for that instance, never wrong.
+ *
  * ptrt_refit_tlas: one launch on the stream (two beyond 4096 meshes) -- every mesh's world box from the root box the
  * DEVICE holds and its world rows (Transform3D::transformAABB's arithmetic), every TLAS leaf box, the inner levels deepest
  * first, the TLAS root box, and the instances' world-space first-pass boxes (PMODE 3), which a ptrt_refit / ptrt_build_bvh
  * / ptrt_set_instance_transforms had invalidated.  The boxes equal a host refit over the same topology bit for bit.  Works
  * for a single-leaf TLAS too.  A refitted TLAS degrades as instances travel (far-apart members of a leaf, overlapping
- * boxes): ptrt_update_instances with a rebuilt TLAS gives a fresh topology.
+ * boxes): ptrt_reorder_tlas in its place gives the meshes a fresh order on the device; ptrt_update_instances with a TLAS
+ * rebuilt on the host gives the reference's own tree, at the price of a synchronisation.
+ *
+ * ptrt_reorder_tlas: called where ptrt_refit_tlas would be, and instead of it.  The TLAS keeps its shape (the reference's
+ * builder gives a mesh count one shape whatever the boxes are) and the meshes are re-dealt to its indices in Morton order of
+ * their world boxes' centres, ties by mesh index -- an object-median split along the Z-order curve, as ptrt_build_bvh does
+ * for the faces of a mesh -- followed by the refit above.  One more launch than ptrt_refit_tlas up to 4096 meshes (a sort in
+ * LDS), the radix passes of ptrt_build_bvh beyond.  No synchronisation, no allocation, use_graphs 0 and 1; counted by the
+ * read-only option "tlas_reorders".  A single-leaf TLAS has nothing to re-deal: the call is ptrt_refit_tlas there.
+ * PTRT_E_INVALID (nothing enqueued) if the uploaded tlas_mesh_indices are not a permutation of 0 .. mesh_count - 1.
+ *
+ * ptrt_read_tlas_order: synchronises; the TLAS index array the device holds now (the counterpart of ptrt_read_prim_order).
+ * PTRT_E_INVALID unless count is the uploaded index count.
  *
  * ptrt_read_tlas: synchronises; the uploaded nodes' left / right / start / count with the boxes the device holds now
  * (the counterpart of ptrt_read_prim_order).  PTRT_E_INVALID unless node_count is the uploaded node count. */
@@ -318,8 +337,11 @@ typedef struct ptrt_instance_xform {
     int32_t has_transform;
 } ptrt_instance_xform;
 int ptrt_set_instance_transforms(ptrt_ctx *ctx, int first_mesh, int count, const ptrt_instance_xform *xf);
+int ptrt_set_instance_transforms_device(ptrt_ctx *ctx, int first_mesh, int count, const ptrt_instance_xform *d_xf);
 int ptrt_refit_tlas(ptrt_ctx *ctx);
 int ptrt_read_tlas(ptrt_ctx *ctx, ptrt_bvh_node *nodes_out, int node_count);
+int ptrt_reorder_tlas(ptrt_ctx *ctx);
+int ptrt_read_tlas_order(ptrt_ctx *ctx, int32_t *mesh_indices_out, int count);
 
 /* The `Triangles` path of updatePTScene with a CHANGING triangle count (PTRTtransfer.cuh:2204-2385:
  * a new triangle list every frame, e.g. a fluid surface).  For a triangle-soup mesh (face i =

@@ -40,23 +40,9 @@ __device__ __forceinline__ float from_ordered_bits(uint32_t u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
-// cbounds[0..2] = min, [3..5] = max of the centroids, as ordered bits (memset to ff.. / 00.. before)
-__global__ __launch_bounds__(256) void centroid_bounds_kernel(const float *__restrict__ verts,
-                                                              const int4 *__restrict__ face_src, int n_faces,
-                                                              float *__restrict__ centroids, uint32_t *cbounds) {
-    // grid-stride: few workgroups, so the six global atomics per workgroup do not pile up
-    uint32_t tmn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, tmx[3] = {0u, 0u, 0u};
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_faces; i += gridDim.x * blockDim.x) {
-        const int4 f = face_src[i];
-        for (int k = 0; k < 3; ++k) {
-            // (a + b + c) * (1/3), the reference's centroid (mesh.cuh:425)
-            const float c = (verts[f.x * 3 + k] + verts[f.y * 3 + k] + verts[f.z * 3 + k]) * (1.0f / 3.0f);
-            centroids[(size_t)i * 3 + k] = c;
-            const uint32_t o = ordered_bits(c);
-            tmn[k] = o < tmn[k] ? o : tmn[k];
-            tmx[k] = o > tmx[k] ? o : tmx[k];
-        }
-    }
+// a workgroup's per-thread bounds (ordered bits) into cbounds: wave shuffles, LDS atomics of one lane per wave, then six
+// global atomics per workgroup.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void block_bounds_to_global(const uint32_t tmn[3], const uint32_t tmx[3], uint32_t *cbounds) {
     __shared__ uint32_t lo[3], hi[3];
     if (threadIdx.x < 3) {
         lo[threadIdx.x] = 0xffffffffu;
@@ -82,6 +68,26 @@ __global__ __launch_bounds__(256) void centroid_bounds_kernel(const float *__res
     }
 }
 
+// cbounds[0..2] = min, [3..5] = max of the centroids, as ordered bits (memset to ff.. / 00.. before)
+__global__ __launch_bounds__(256) void centroid_bounds_kernel(const float *__restrict__ verts,
+                                                              const int4 *__restrict__ face_src, int n_faces,
+                                                              float *__restrict__ centroids, uint32_t *cbounds) {
+    // grid-stride: few workgroups, so the six global atomics per workgroup do not pile up
+    uint32_t tmn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, tmx[3] = {0u, 0u, 0u};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_faces; i += gridDim.x * blockDim.x) {
+        const int4 f = face_src[i];
+        for (int k = 0; k < 3; ++k) {
+            // (a + b + c) * (1/3), the reference's centroid (mesh.cuh:425)
+            const float c = (verts[f.x * 3 + k] + verts[f.y * 3 + k] + verts[f.z * 3 + k]) * (1.0f / 3.0f);
+            centroids[(size_t)i * 3 + k] = c;
+            const uint32_t o = ordered_bits(c);
+            tmn[k] = o < tmn[k] ? o : tmn[k];
+            tmx[k] = o > tmx[k] ? o : tmx[k];
+        }
+    }
+    block_bounds_to_global(tmn, tmx, cbounds);
+}
+
 __device__ __forceinline__ uint32_t spread10(uint32_t v) { // 10 bits -> every third bit
     v = (v | (v << 16)) & 0x030000ffu;
     v = (v | (v << 8)) & 0x0300f00fu;
@@ -90,27 +96,40 @@ __device__ __forceinline__ uint32_t spread10(uint32_t v) { // 10 bits -> every t
     return v;
 }
 
+// one scale for the three axes (the largest extent): a flat mesh such as a water surface then
+// spends its code bits on the two axes it spans instead of on the noise of the third
+__device__ __forceinline__ float bounds_scale(const uint32_t *cbounds, float lo[3]) {
+    float ext = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = from_ordered_bits(cbounds[k]);
+        const float e = from_ordered_bits(cbounds[3 + k]) - lo[k];
+        ext = e > ext ? e : ext;
+    }
+    return ext;
+}
+
+// 30-bit Morton code of point p: 10 bits per axis of (p - lo) / ext clamped to [0, 1], x in the high bit; ext == 0: code 0.
+// Shared by the BLAS rebuild (morton_kernel) and the TLAS re-order (pt_tlas.hip.h).  Scene::mortonOrderTLAS
+// (host/ptrt/scene.hpp) restates it and spread10 for the host twin of the re-order: change both or neither.
+__device__ __forceinline__ uint32_t morton30(const float *p, const float lo[3], float ext) {
+    uint32_t q[3];
+    for (int k = 0; k < 3; ++k) {
+        float t = ext > 0.0f ? (p[k] - lo[k]) / ext : 0.0f;
+        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+        int v = (int)(t * 1024.0f);
+        q[k] = (uint32_t)(v > 1023 ? 1023 : v);
+    }
+    return (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
+}
+
 __global__ __launch_bounds__(256) void morton_kernel(const float *__restrict__ centroids, const uint32_t *__restrict__ cbounds,
                                                      int n_faces, uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_faces)
         return;
-    // one scale for the three axes (the largest extent): a flat mesh such as a water surface then
-    // spends its code bits on the two axes it spans instead of on the noise of the third
-    float ext = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-        const float e = from_ordered_bits(cbounds[3 + k]) - from_ordered_bits(cbounds[k]);
-        ext = e > ext ? e : ext;
-    }
-    uint32_t q[3];
-    for (int k = 0; k < 3; ++k) {
-        const float lo = from_ordered_bits(cbounds[k]);
-        float t = ext > 0.0f ? (centroids[(size_t)i * 3 + k] - lo) / ext : 0.0f;
-        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-        int v = (int)(t * 1024.0f);
-        q[k] = (uint32_t)(v > 1023 ? 1023 : v);
-    }
-    keys[i] = (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
+    float lo[3];
+    const float ext = bounds_scale(cbounds, lo);
+    keys[i] = morton30(centroids + (size_t)i * 3, lo, ext);
     vals[i] = (uint32_t)i;
 }
 

@@ -15,27 +15,56 @@
 //      A TLAS has at most mesh-count nodes; every phase strides over its items, so any mesh count is
 //      covered.  Beyond TLAS_WIDE meshes phase a runs as a launch of its own over the whole device.
 // min / max are exact, so the boxes equal a host refit of the same topology bit for bit (Scene::refitTLAS).
+//
+// Re-order (ptrt_reorder_tlas), in front of the refit.  The reference's TLAS builder splits n > leafMax entries into
+// n/2 | n - n/2 whatever the boxes are (scene.cuh:497-548), so a TLAS of a given mesh count has ONE shape; what a rebuild
+// changes is which mesh sits at which TLAS index.  As ptrt_build_bvh does for the faces of a mesh (pt_build.hip.h), the
+// meshes are re-dealt to the indices in Morton order of their world boxes' centres:
+//   3. reorder_tlas_kernel    ONE workgroup, up to TLAS_WIDE meshes; item i is MESH i, so the result does not depend on the
+//                             order it replaces:
+//        a. centre of the mesh's world box (mesh_world_box; AABB::center(), transform.cuh:97: (bmin + bmax) * 0.5f)
+//        b. min / max of the centres: wave shuffles, then one LDS slot per wave (no atomics)
+//        c. 30-bit Morton code (morton30 of pt_build.hip.h), key = code << 32 | mesh
+//        d. bitonic sort of the keys in LDS, padded to a power of two with all-ones keys (32 KB at most)
+//        e. tlas_mesh_ids[j] = the mesh ranked j
+//      Beyond TLAS_WIDE meshes: tlas_centres_kernel (ordered-int atomics, as centroid_bounds_kernel), morton_kernel and the
+//      radix passes of pt_build.hip.h over (code, mesh) seeded in ascending mesh order -- the sort is stable, so equal codes
+//      keep that order, which is what the mesh in the key's low half gives -- and tlas_take_order_kernel.
+// The builder emits its leaves depth first and each appends its members to the index array (build_bvh_range: prims.push_back;
+// upload_tlas keeps those ranges in tlas_leaves), so the leaves' index ranges are consecutive and in tree order, left subtree
+// before right: rank j -> index j puts the lower half of the curve under every node's left child, i.e. an object-median split
+// along the Z-order curve.  (A TLAS uploaded through the C ABI with other ranges is still re-ordered validly -- any
+// permutation is a valid TLAS under the refit that follows -- only without that reading.)
 #pragma once
+#include "pt_build.hip.h"
 #include "pt_refit.hip.h"
 
 namespace pt {
 
 constexpr int XFORM_F = 40;       // floats per staged record: {flag, -, -, -}, inverse rows, world rows, normal rows
+// where scatter_xforms_kernel finds a record's fields, in floats: the staged records above, or a caller's ptrt_instance_xform
+// array read in place (ptrt_set_instance_transforms_device).  `flag`: a word that is non-zero for has_transform.
+struct XformLayout {
+    int stride, flag, inverse, world, normal;
+};
+constexpr XformLayout XFORM_STAGED{XFORM_F, 0, 4, 16, 28};
 constexpr int TLAS_BLOCK = 256;   // threads of the one workgroup (the fp64 first-pass bound wants registers, not lanes)
 constexpr int TLAS_WIDE = 4096;   // more TLAS indices than this: world boxes in a launch of their own
 
-__global__ void scatter_xforms_kernel(const float *__restrict__ stage, float4 *mesh_recs, int first, int count) {
+__global__ void scatter_xforms_kernel(const float *__restrict__ xf, XformLayout L, float4 *mesh_recs, int first, int count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count * 37)
         return;
     const int r = i / 37, k = i - r * 37; // k == 0: the flags word, k >= 1: float k - 1 of the nine rows
     float *rec = reinterpret_cast<float *>(mesh_recs + (size_t)(first + r) * MESH_REC_F4);
-    const float *src = stage + (size_t)r * XFORM_F;
+    const float *src = xf + (size_t)r * L.stride;
     if (k == 0) {
-        const int flags = (__float_as_int(rec[7]) & ~1) | (__float_as_int(src[0]) & 1); // (bit 1 belongs to the materials)
+        const int flags = (__float_as_int(rec[7]) & ~1) | (__float_as_int(src[L.flag]) != 0 ? 1 : 0); // (bit 1 belongs to the materials)
         rec[7] = __int_as_float(flags);
     } else {
-        rec[8 + k - 1] = src[4 + k - 1];
+        const int b = (k - 1) / 12, j = (k - 1) - b * 12; // matrix b (inverse, world, normal), float j of its first three rows
+        const int off = b == 0 ? L.inverse : (b == 1 ? L.world : L.normal);
+        rec[8 + k - 1] = (b == 2 && (j & 3) == 3) ? 0.0f : src[off + j]; // (a normal row's fourth word is 0 in the records)
     }
 }
 
@@ -114,13 +143,11 @@ __device__ inline void instance_pretest(const float4 *rec, double c2_cap, float4
     pre[1] = p1;
 }
 
-// phase a for TLAS index j: world box of its mesh into world[2j..2j+1], first-pass box into pre[2m..2m+1]
-__device__ inline void tlas_world_box(const float4 *mesh_recs, const int *tlas_mesh_ids, int j, double c2_cap, float4 *world,
-                                      float4 *pre) {
-    const int m = tlas_mesh_ids[j];
-    const float4 *rec = mesh_recs + (size_t)m * MESH_REC_F4;
+// world box of the mesh behind `rec`: its root box as the device holds it through its world rows
+__device__ inline void mesh_world_box(const float4 *rec, float3 &lo, float3 &hi) {
     const float4 b0 = rec[0], b1 = rec[1], w0 = rec[5], w1 = rec[6], w2 = rec[7];
-    float3 lo = make_float3(1e30f, 1e30f, 1e30f), hi = make_float3(-1e30f, -1e30f, -1e30f);
+    lo = make_float3(1e30f, 1e30f, 1e30f);
+    hi = make_float3(-1e30f, -1e30f, -1e30f);
     for (int k = 0; k < 8; ++k) { // the 8 corners through the world matrix, as tlas_root_box and the host do
         const float x = (k & 1) ? b1.x : b0.x, y = (k & 2) ? b1.y : b0.y, z = (k & 4) ? b1.z : b0.z;
         const float px = w0.x * x + w0.y * y + w0.z * z + w0.w;
@@ -129,6 +156,15 @@ __device__ inline void tlas_world_box(const float4 *mesh_recs, const int *tlas_m
         lo.x = fminf(lo.x, px); lo.y = fminf(lo.y, py); lo.z = fminf(lo.z, pz);
         hi.x = fmaxf(hi.x, px); hi.y = fmaxf(hi.y, py); hi.z = fmaxf(hi.z, pz);
     }
+}
+
+// phase a for TLAS index j: world box of its mesh into world[2j..2j+1], first-pass box into pre[2m..2m+1]
+__device__ inline void tlas_world_box(const float4 *mesh_recs, const int *tlas_mesh_ids, int j, double c2_cap, float4 *world,
+                                      float4 *pre) {
+    const int m = tlas_mesh_ids[j];
+    const float4 *rec = mesh_recs + (size_t)m * MESH_REC_F4;
+    float3 lo, hi;
+    mesh_world_box(rec, lo, hi);
     world[2 * j] = make_float4(lo.x, lo.y, lo.z, 0.0f);
     world[2 * j + 1] = make_float4(hi.x, hi.y, hi.z, 0.0f);
     instance_pretest(rec, c2_cap, pre + 2 * (size_t)m);
@@ -179,6 +215,97 @@ __global__ __launch_bounds__(TLAS_BLOCK) void refit_tlas_kernel(const float4 *__
             store_tlas_box(tlas_nodes, root_box, node_dst[n], lo, hi);
         }
     }
+}
+
+// ---- re-order (see the head of the file) -------------------------------------------------------------------------------
+// centre of mesh m's world box into centres[3m..3m+2], folded into the caller's running bounds (ordered bits)
+__device__ inline void tlas_mesh_centre(const float4 *mesh_recs, int m, float *centres, uint32_t tmn[3], uint32_t tmx[3]) {
+    float3 lo, hi;
+    mesh_world_box(mesh_recs + (size_t)m * MESH_REC_F4, lo, hi);
+    const float c[3] = {(lo.x + hi.x) * 0.5f, (lo.y + hi.y) * 0.5f, (lo.z + hi.z) * 0.5f};
+    for (int k = 0; k < 3; ++k) {
+        centres[(size_t)m * 3 + k] = c[k];
+        const uint32_t o = ordered_bits(c[k]);
+        tmn[k] = o < tmn[k] ? o : tmn[k];
+        tmx[k] = o > tmx[k] ? o : tmx[k];
+    }
+}
+
+// n_meshes <= TLAS_WIDE (the host launches it for nothing else; a larger count returns at once: `keys` holds TLAS_WIDE).
+// `centres` (3 floats per mesh) is written in phase a and read in phase c by the same thread.
+__global__ __launch_bounds__(TLAS_BLOCK) void reorder_tlas_kernel(const float4 *__restrict__ mesh_recs, int n_meshes,
+                                                                  float *centres, int *__restrict__ tlas_mesh_ids) {
+    __shared__ unsigned long long keys[TLAS_WIDE];
+    __shared__ uint32_t wave_bounds[TLAS_BLOCK / 64][6];
+    if (n_meshes > TLAS_WIDE)
+        return;
+    uint32_t tmn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, tmx[3] = {0u, 0u, 0u};
+    for (int m = threadIdx.x; m < n_meshes; m += TLAS_BLOCK)
+        tlas_mesh_centre(mesh_recs, m, centres, tmn, tmx);
+    for (int k = 0; k < 3; ++k) {
+        uint32_t mn = tmn[k], mx = tmx[k];
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t a = __shfl_xor(mn, off), b = __shfl_xor(mx, off);
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+        }
+        if ((threadIdx.x & 63) == 0) {
+            wave_bounds[threadIdx.x >> 6][k] = mn;
+            wave_bounds[threadIdx.x >> 6][3 + k] = mx;
+        }
+    }
+    __syncthreads();
+    uint32_t cb[6];
+    for (int k = 0; k < 3; ++k) {
+        uint32_t mn = wave_bounds[0][k], mx = wave_bounds[0][3 + k];
+        for (int w = 1; w < TLAS_BLOCK / 64; ++w) {
+            mn = wave_bounds[w][k] < mn ? wave_bounds[w][k] : mn;
+            mx = wave_bounds[w][3 + k] > mx ? wave_bounds[w][3 + k] : mx;
+        }
+        cb[k] = mn;
+        cb[3 + k] = mx;
+    }
+    float lo[3];
+    const float ext = bounds_scale(cb, lo);
+    int padded = 1;
+    while (padded < n_meshes)
+        padded <<= 1;
+    for (int i = threadIdx.x; i < padded; i += TLAS_BLOCK)
+        keys[i] = i < n_meshes ? ((unsigned long long)morton30(centres + (size_t)i * 3, lo, ext) << 32) | (unsigned)i : ~0ull;
+    for (int k = 2; k <= padded; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int t = threadIdx.x; t < (padded >> 1); t += TLAS_BLOCK) { // pair t of this step: (i, i | j), bit j of i clear
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long a = keys[i], b = keys[l];
+                if ((a > b) == ((i & k) == 0)) {
+                    keys[i] = b;
+                    keys[l] = a;
+                }
+            }
+        }
+    __syncthreads();
+    for (int j = threadIdx.x; j < n_meshes; j += TLAS_BLOCK)
+        tlas_mesh_ids[j] = (int)(uint32_t)keys[j];
+}
+
+// beyond TLAS_WIDE meshes: phases a and b as a launch of their own over few workgroups (cbounds as centroid_bounds_kernel's)
+__global__ __launch_bounds__(256) void tlas_centres_kernel(const float4 *__restrict__ mesh_recs, int n_meshes,
+                                                           float *__restrict__ centres, uint32_t *cbounds) {
+    uint32_t tmn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, tmx[3] = {0u, 0u, 0u};
+    for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < n_meshes; m += gridDim.x * blockDim.x)
+        tlas_mesh_centre(mesh_recs, m, centres, tmn, tmx);
+    block_bounds_to_global(tmn, tmx, cbounds);
+}
+
+// ... and phase e: TLAS index j <- the mesh ranked j by the radix sort; cbounds made ready for the next re-order
+__global__ __launch_bounds__(256) void tlas_take_order_kernel(const uint32_t *__restrict__ order, int n_meshes,
+                                                              int *__restrict__ tlas_mesh_ids, uint32_t *cbounds) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < 6)
+        cbounds[j] = j < 3 ? 0xffffffffu : 0u;
+    if (j < n_meshes)
+        tlas_mesh_ids[j] = (int)order[j];
 }
 
 } // namespace pt

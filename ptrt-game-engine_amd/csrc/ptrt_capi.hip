@@ -102,6 +102,12 @@ struct ptrt_ctx {
     std::vector<ptrt_bvh_node> h_tlas_in; // the TLAS as it was uploaded ...
     std::vector<int> h_tlas_in_dst;       // ... and where the device keeps each of its nodes' boxes (INT32_MIN: nowhere)
     int tlas_refits = 0;                // ptrt_refit_tlas calls since the last geometry upload
+    // TLAS re-order support (ptrt_reorder_tlas, pt_tlas.hip.h)
+    uint32_t *d_tlas_sort = nullptr;    // scratch: {cbounds 8 | centres 3n | keys n, n | meshes n, n | radix counts, positions}
+    int tlas_sort_cap = 0;              // (the cbounds, key and radix parts are used only beyond pt::TLAS_WIDE meshes)
+    bool tlas_is_perm = false;          // the uploaded TLAS index array is a permutation of 0 .. mesh count - 1
+    int tlas_reorders = 0;              // ptrt_reorder_tlas calls since the last geometry upload
+    bool xf_host_stale = false;         // ptrt_set_instance_transforms_device wrote flag bits and matrices h_mesh_recs has not seen
     bool inst_c2_all = false;           // inst_c2 covers every instance's matrices (host_inst_c2), not only the upload's finite boxes
     // staged instance transforms: two halves of pinned host / device memory, each waited for when it comes round again
     float *h_xf = nullptr, *d_xf = nullptr;
@@ -469,6 +475,12 @@ int convert_tree(const ptrt_bvh_node *in, int n_in, std::vector<float4> &out_nod
     return root;
 }
 
+// words of ptrt_ctx::d_tlas_sort for n meshes (layout there)
+size_t tlas_sort_words(int n) {
+    const size_t n_waves = ((size_t)n + pt::RS_WAVE_KEYS - 1) / pt::RS_WAVE_KEYS;
+    return 8 + (size_t)n * 3 + (n > pt::TLAS_WIDE ? (size_t)n * 4 + n_waves * 256 * 2 : 0);
+}
+
 // TLAS part of an upload: converts the reference-shaped TLAS, uploads it and derives what the launch needs of it
 int upload_tlas(ptrt_ctx *c, int mesh_count, const ptrt_bvh_node *tlas_nodes, int tlas_node_count,
                 const int32_t *tlas_mesh_indices, int tlas_index_count, bool dry_run) {
@@ -535,6 +547,22 @@ int upload_tlas(ptrt_ctx *c, int mesh_count, const ptrt_bvh_node *tlas_nodes, in
         HIP_TRY(c, hipMalloc((void **)&c->d_tlas_world, (size_t)tlas_index_count * 2 * sizeof(float4)));
         c->tlas_world_cap = tlas_index_count;
     }
+    // a re-order (ptrt_reorder_tlas) deals MESHES to the indices: it needs every mesh exactly once
+    std::vector<char> seen((size_t)mesh_count, 0);
+    bool perm = tlas_index_count == mesh_count;
+    for (int id : tids) {
+        perm = perm && !seen[(size_t)id];
+        seen[(size_t)id] = 1;
+    }
+    c->tlas_is_perm = perm;
+    if (perm && troot >= 0 && mesh_count > c->tlas_sort_cap) {
+        dfree(c->d_tlas_sort);
+        c->tlas_sort_cap = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_tlas_sort, tlas_sort_words(mesh_count) * sizeof(uint32_t)));
+        c->tlas_sort_cap = mesh_count;
+        const uint32_t cb[8] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, 0u}; // min words all-ones, max words zero; every re-order leaves them so
+        HIP_TRY(c, hipMemcpy(c->d_tlas_sort, cb, sizeof cb, hipMemcpyHostToDevice));
+    }
     c->n_tlas_leaves = (int)leaf_dst.size();
     c->n_tlas_inner = n_inner;
     c->h_tlas_in.assign(tlas_nodes, tlas_nodes + tlas_node_count);
@@ -569,6 +597,8 @@ void free_scene(ptrt_ctx *c) {
     dfree(c->d_tlas_refit);
     dfree(c->d_tlas_world);
     c->tlas_world_cap = 0;
+    dfree(c->d_tlas_sort);
+    c->tlas_sort_cap = 0;
     dfree(c->d_verts);
     dfree(c->d_slot_face);
     dfree(c->d_leaf_dst);
@@ -586,10 +616,39 @@ void free_scene(ptrt_ctx *c) {
     c->sort_capacity = 0;
 }
 
+// After ptrt_set_instance_transforms_device the has_transform bits and matrices of h_mesh_recs lag the device's.  The paths
+// that write host flag words back (push_mesh_recs) fetch them first; they synchronise anyway.  Until then the host copy is
+// only used conservatively: any_transform is held true, and host_inst_c2 over old matrices gives a cap under which
+// pt::instance_pretest hands an instance it does not cover the infinite box.
+int sync_host_xforms(ptrt_ctx *c) {
+    if (!c->xf_host_stale)
+        return PTRT_OK;
+    std::vector<float4> dev((size_t)c->n_meshes * pt::MESH_REC_F4);
+    HIP_TRY(c, hipMemcpyAsync(dev.data(), c->d_mesh_recs, dev.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->any_transform = false;
+    for (int m = 0; m < c->n_meshes; ++m) {
+        float4 *rec = &c->h_mesh_recs[(size_t)m * pt::MESH_REC_F4];
+        const float4 *d = &dev[(size_t)m * pt::MESH_REC_F4];
+        int hf, df;
+        std::memcpy(&hf, &rec[1].w, 4);
+        std::memcpy(&df, &d[1].w, 4);
+        hf = (hf & ~1) | (df & 1);
+        std::memcpy(&rec[1].w, &hf, 4);
+        std::memcpy(&rec[2], &d[2], 9 * sizeof(float4));
+        c->any_transform = c->any_transform || (hf & 1) != 0;
+    }
+    c->xf_host_stale = false;
+    return PTRT_OK;
+}
+
 // flags bit1 (skipped by shadow rays) comes from the materials; re-applied on either upload.
 // `full` re-sends the whole records (geometry upload); otherwise only the flag words are patched
 // so that boxes moved by ptrt_refit on the device are not overwritten with stale host copies.
 int push_mesh_recs(ptrt_ctx *c, bool full) {
+    if (!full)
+        if (int rc = sync_host_xforms(c))
+            return rc;
     for (int m = 0; m < c->n_meshes; ++m) {
         int flags;
         std::memcpy(&flags, &c->h_mesh_recs[(size_t)m * pt::MESH_REC_F4 + 1].w, 4);
@@ -1019,27 +1078,32 @@ int enqueue_refit(ptrt_ctx *c, hipStream_t st) {
     return PTRT_OK;
 }
 
+// stable sort of n (30-bit Morton code, value) pairs in keys[0] / vals[0]; `hist`: n_waves * 256 counts, then as many
+// positions.  Returns which of the two buffers holds the result.
+int enqueue_radix_sort(hipStream_t st, uint32_t *const keys[2], uint32_t *const vals[2], uint32_t *hist, int n) {
+    const int n_waves = (n + pt::RS_WAVE_KEYS - 1) / pt::RS_WAVE_KEYS;
+    const int wg = (n_waves + pt::RS_BLOCK / 64 - 1) / (pt::RS_BLOCK / 64);
+    int cur = 0;
+    for (int shift = 0; shift < 32; shift += 8) { // the top pass only sees bits 24..29 of the 30-bit code
+        hipLaunchKernelGGL(pt::rs_hist_kernel, dim3(wg), dim3(pt::RS_BLOCK), 0, st, keys[cur], n, shift, hist, n_waves);
+        uint32_t *positions = hist + (size_t)n_waves * 256;
+        hipLaunchKernelGGL(pt::rs_scan_kernel, dim3(1), dim3(1024), 0, st, hist, positions, n_waves);
+        hipLaunchKernelGGL(pt::rs_scatter_kernel, dim3(wg), dim3(pt::RS_BLOCK), 0, st, keys[cur], vals[cur], n, shift, positions,
+                           n_waves, keys[cur ^ 1], vals[cur ^ 1]);
+        cur ^= 1;
+    }
+    return cur;
+}
+
 int enqueue_build(ptrt_ctx *c, int mesh, hipStream_t st) {
     const int n = c->mesh_face_count[mesh];
-    const int n_waves = (n + pt::RS_WAVE_KEYS - 1) / pt::RS_WAVE_KEYS;
     const int B = 256, G = (n + B - 1) / B;
     const int4 *faces = c->d_face_src + c->mesh_face_base[mesh];
     hipLaunchKernelGGL(pt::centroid_bounds_kernel, dim3(G < 128 ? G : 128), dim3(B), 0, st, c->d_verts, faces, n,
                        c->d_centroids, c->d_cbounds);
     hipLaunchKernelGGL(pt::morton_kernel, dim3(G), dim3(B), 0, st, c->d_centroids, c->d_cbounds, n, c->d_sort_keys[0],
                        c->d_sort_vals[0]);
-    const int wg = (n_waves + pt::RS_BLOCK / 64 - 1) / (pt::RS_BLOCK / 64);
-    int cur = 0;
-    for (int shift = 0; shift < 32; shift += 8) { // the top pass only sees bits 24..29 of the 30-bit code
-        hipLaunchKernelGGL(pt::rs_hist_kernel, dim3(wg), dim3(pt::RS_BLOCK), 0, st, c->d_sort_keys[cur], n, shift,
-                           c->d_sort_hist, n_waves);
-        uint32_t *positions = c->d_sort_hist + (size_t)n_waves * 256;
-        hipLaunchKernelGGL(pt::rs_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_sort_hist, positions, n_waves);
-        hipLaunchKernelGGL(pt::rs_scatter_kernel, dim3(wg), dim3(pt::RS_BLOCK), 0, st, c->d_sort_keys[cur],
-                           c->d_sort_vals[cur], n, shift, positions, n_waves, c->d_sort_keys[cur ^ 1],
-                           c->d_sort_vals[cur ^ 1]);
-        cur ^= 1;
-    }
+    const int cur = enqueue_radix_sort(st, c->d_sort_keys, c->d_sort_vals, c->d_sort_hist, n);
     hipLaunchKernelGGL(pt::apply_order_kernel, dim3(G), dim3(B), 0, st, c->d_sort_vals[cur], c->d_slot_pos, faces,
                        c->d_slot_face, c->mesh_slot_base[mesh], n, c->d_cbounds);
     HIP_TRY(c, hipGetLastError());
@@ -1571,6 +1635,7 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
     c->n_slots = c->n_leaves = 0;
     c->n_meshes = mesh_count;
     c->h_mesh_recs = recs;
+    c->xf_host_stale = false;
     if (int rc = push_mesh_recs(c, true))
         return rc;
     {
@@ -1643,6 +1708,7 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
         return rc;
     c->n_geometry_uploads++;
     c->tlas_refits = 0;
+    c->tlas_reorders = 0;
     c->all_single_leaf = all_leaf;
     c->any_transform = false;
     for (int m = 0; m < mesh_count; ++m)
@@ -1774,6 +1840,7 @@ int ptrt_update_instances(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_co
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // frames in flight still read the old records
     c->any_transform = false;
+    c->xf_host_stale = false; // (every mesh's flag bit and matrices are rewritten below, on both sides)
     for (int m = 0; m < mesh_count; ++m) {
         const ptrt_mesh_desc &M = meshes[m];
         float4 *rec = &c->h_mesh_recs[(size_t)m * pt::MESH_REC_F4];
@@ -1843,13 +1910,14 @@ float host_inst_c2(const ptrt_ctx *c) {
 
 // inst_c2 is an argument of the TLAS refit: a captured launch sequence holds the old value
 void set_inst_c2(ptrt_ctx *c, float v) {
-    if (v != c->inst_c2 || !c->inst_c2_all) {
-        auto it = c->graphs.find(-2);
-        if (it != c->graphs.end()) {
-            (void)hipGraphExecDestroy(it->second);
-            c->graphs.erase(it);
+    if (v != c->inst_c2 || !c->inst_c2_all)
+        for (int key : {-2, -3}) { // (the refit alone, the re-order with its refit)
+            auto it = c->graphs.find(key);
+            if (it != c->graphs.end()) {
+                (void)hipGraphExecDestroy(it->second);
+                c->graphs.erase(it);
+            }
         }
-    }
     c->inst_c2 = v;
     c->inst_c2_all = true;
 }
@@ -1913,11 +1981,11 @@ int ptrt_set_instance_transforms(ptrt_ctx *c, int first_mesh, int count, const p
             rec[8 + r] = f4(X.normal[r * 4], X.normal[r * 4 + 1], X.normal[r * 4 + 2], 0.0f);
         }
         float *o = hs + (size_t)i * pt::XFORM_F;
-        o[0] = rec[1].w;
+        o[0] = as_f(flags & 1);
         o[1] = o[2] = o[3] = 0.0f;
         std::memcpy(o + 4, &rec[2], 9 * sizeof(float4));
     }
-    c->any_transform = false;
+    c->any_transform = c->xf_host_stale; // (flags only the device knows: held true, see sync_host_xforms)
     for (int m = 0; m < c->n_meshes && !c->any_transform; ++m) {
         int flags;
         std::memcpy(&flags, &c->h_mesh_recs[(size_t)m * pt::MESH_REC_F4 + 1].w, 4);
@@ -1927,11 +1995,38 @@ int ptrt_set_instance_transforms(ptrt_ctx *c, int first_mesh, int count, const p
     c->inst_pre_ok = false; // the first-pass boxes follow with the next ptrt_refit_tlas
     HIP_TRY(c, hipMemcpyAsync(c->d_xf + at, hs, (size_t)count * pt::XFORM_F * sizeof(float), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(pt::scatter_xforms_kernel, dim3((count * 37 + 255) / 256), dim3(256), 0, c->stream, c->d_xf + at,
-                       c->d_mesh_recs, first_mesh, count);
+                       pt::XFORM_STAGED, c->d_mesh_recs, first_mesh, count);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->xf_ev[half], c->stream)); // (this half's records are free again behind this)
     c->xf_pending[half] = true;
     c->xf_used[half] += (size_t)count;
+    return PTRT_OK;
+}
+
+// The same records from DEVICE memory ordered on the context's stream: one scatter launch that reads them in place.  The host
+// copy of the flag bits and matrices lags from here on (sync_host_xforms).
+int ptrt_set_instance_transforms_device(ptrt_ctx *c, int first_mesh, int count, const ptrt_instance_xform *d_xf) {
+    static_assert(sizeof(ptrt_instance_xform) == 49 * sizeof(float), "ptrt_instance_xform is read as 49 words");
+    constexpr int W = (int)sizeof(float);
+    constexpr pt::XformLayout abi{49, (int)offsetof(ptrt_instance_xform, has_transform) / W, (int)offsetof(ptrt_instance_xform, inverse) / W,
+                                  (int)offsetof(ptrt_instance_xform, world) / W, (int)offsetof(ptrt_instance_xform, normal) / W};
+    if (!ctx_live(c))
+        return fail(c, PTRT_E_INVALID, "ptrt_set_instance_transforms_device: bad context");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_set_instance_transforms_device: geometry not uploaded");
+    if (!d_xf || count < 0 || first_mesh < 0 || first_mesh > c->n_meshes || count > c->n_meshes - first_mesh)
+        return fail(c, PTRT_E_INVALID, "ptrt_set_instance_transforms_device: meshes [%d, %d + %d) of %d%s", first_mesh, first_mesh,
+                    count, c->n_meshes, d_xf ? "" : ", NULL transforms");
+    if (count == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    c->xf_host_stale = true;
+    c->any_transform = true;
+    c->inst_pre_ok = false; // the first-pass boxes follow with the next ptrt_refit_tlas / ptrt_reorder_tlas
+    hipLaunchKernelGGL(pt::scatter_xforms_kernel, dim3((count * 37 + 255) / 256), dim3(256), 0, c->stream,
+                       reinterpret_cast<const float *>(d_xf), abi, c->d_mesh_recs, first_mesh, count);
+    HIP_TRY(c, hipGetLastError());
     return PTRT_OK;
 }
 
@@ -1949,19 +2044,68 @@ int enqueue_refit_tlas(ptrt_ctx *c, hipStream_t st) {
     return PTRT_OK;
 }
 
-int ptrt_refit_tlas(ptrt_ctx *c) {
+// the meshes re-dealt to the TLAS indices in Morton order of their world boxes' centres (pt_tlas.hip.h), then the refit.
+// Invariant of the wide path: cbounds hold {all-ones x 3, zero x 3} between calls -- upload_tlas seeds them with the
+// allocation and tlas_take_order_kernel, the last launch of every sequence, restores them (as apply_order_kernel does for a
+// BLAS build).  The launches are enqueued or captured as one sequence, so a sequence that starts also ends.
+int enqueue_reorder_tlas(ptrt_ctx *c, hipStream_t st) {
+    const int n = c->n_meshes;
+    uint32_t *cbounds = c->d_tlas_sort, *rest = cbounds + 8;
+    float *centres = reinterpret_cast<float *>(rest);
+    if (n <= pt::TLAS_WIDE) {
+        hipLaunchKernelGGL(pt::reorder_tlas_kernel, dim3(1), dim3(pt::TLAS_BLOCK), 0, st, c->d_mesh_recs, n, centres,
+                           c->d_tlas_mesh_ids);
+    } else {
+        uint32_t *keys[2] = {rest + (size_t)n * 3, rest + (size_t)n * 4}, *vals[2] = {rest + (size_t)n * 5, rest + (size_t)n * 6};
+        uint32_t *hist = rest + (size_t)n * 7;
+        const int B = 256, G = (n + B - 1) / B;
+        hipLaunchKernelGGL(pt::tlas_centres_kernel, dim3(G < 128 ? G : 128), dim3(B), 0, st, c->d_mesh_recs, n, centres, cbounds);
+        hipLaunchKernelGGL(pt::morton_kernel, dim3(G), dim3(B), 0, st, centres, cbounds, n, keys[0], vals[0]);
+        const int cur = enqueue_radix_sort(st, keys, vals, hist, n);
+        hipLaunchKernelGGL(pt::tlas_take_order_kernel, dim3(G), dim3(B), 0, st, vals[cur], n, c->d_tlas_mesh_ids, cbounds);
+    }
+    return enqueue_refit_tlas(c, st);
+}
+
+// What ptrt_refit_tlas and ptrt_reorder_tlas share: ctx_live orders the next frame (pipelined or split) behind the stream and
+// has the TLAS-leaf-order heads gathered again; the launches go out on the stream, replayed as a hipGraph under use_graphs;
+// the instances' first-pass boxes are fresh behind them.  A single-leaf TLAS has nothing to re-deal (and its kernels' mesh
+// order must stay): the re-order is the refit there.
+int refit_tlas_entry(ptrt_ctx *c, const char *who, bool reorder) {
     if (!ctx_live(c))
-        return fail(c, PTRT_E_INVALID, "ptrt_refit_tlas: bad context");
+        return fail(c, PTRT_E_INVALID, "%s: bad context", who);
     if (!c->have_geometry)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_refit_tlas: geometry not uploaded");
+        return fail(c, PTRT_E_NOT_READY, "%s: geometry not uploaded", who);
+    const bool deal = reorder && !c->tlas_single_leaf;
+    if (deal && !c->tlas_is_perm)
+        return fail(c, PTRT_E_INVALID, "%s: the uploaded TLAS indices are not a permutation of the %d meshes", who, c->n_meshes);
     if (int rc = set_device(c))
         return rc;
     if (!c->inst_c2_all)
         set_inst_c2(c, host_inst_c2(c));
-    if (int rc = run_graphed(c, -2, [c](hipStream_t st) { return enqueue_refit_tlas(c, st); }))
+    if (int rc = deal ? run_graphed(c, -3, [c](hipStream_t st) { return enqueue_reorder_tlas(c, st); })
+                      : run_graphed(c, -2, [c](hipStream_t st) { return enqueue_refit_tlas(c, st); }))
         return rc;
     c->inst_pre_ok = true;
-    c->tlas_refits++;
+    ++(reorder ? c->tlas_reorders : c->tlas_refits);
+    return PTRT_OK;
+}
+
+int ptrt_refit_tlas(ptrt_ctx *c) { return refit_tlas_entry(c, "ptrt_refit_tlas", false); }
+
+int ptrt_reorder_tlas(ptrt_ctx *c) { return refit_tlas_entry(c, "ptrt_reorder_tlas", true); }
+
+int ptrt_read_tlas_order(ptrt_ctx *c, int32_t *mesh_indices_out, int count) {
+    if (!ctx_live(c) || !mesh_indices_out)
+        return fail(c, PTRT_E_INVALID, "ptrt_read_tlas_order: bad argument");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_read_tlas_order: geometry not uploaded");
+    if (count != c->n_tlas_index)
+        return fail(c, PTRT_E_INVALID, "ptrt_read_tlas_order: the uploaded TLAS has %d indices, asked for %d", c->n_tlas_index, count);
+    if (int rc = set_device(c))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(mesh_indices_out, c->d_tlas_mesh_ids, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PTRT_OK;
 }
 

@@ -315,6 +315,11 @@ int hs_refit_instance_changes(void *s, int host_only) {
     return 0;
 }
 int hs_reseat_tlas(void *s) { HS_TRY(static_cast<Scene *>(s)->reseatTLAS()); return 0; }
+// hs_reorder_tlas: as hs_refit_instance_changes, with the meshes re-dealt to the TLAS indices in Morton order first
+int hs_reorder_tlas(void *s, int host_only) {
+    HS_TRY(host_only ? static_cast<Scene *>(s)->reorderTLASOnHost() : static_cast<Scene *>(s)->reorderTLAS());
+    return 0;
+}
 int hs_refit_from_device(void *s, int mesh, const void *device_xyz) {
     HS_TRY(static_cast<Scene *>(s)->refitFromDevice((size_t)mesh, static_cast<const float *>(device_xyz)));
     return 0;

@@ -96,6 +96,7 @@ const Option OPTIONS[] = {
     // the instances' first-pass boxes (PMODE 3) match the device's root boxes and matrices
     {"inst_pre_ok", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->inst_pre_ok ? 1 : 0; }},
     {"tlas_refits", &ptrt_ctx::tlas_refits, OPT_READ_ONLY}, // ptrt_refit_tlas calls since the last geometry upload
+    {"tlas_reorders", &ptrt_ctx::tlas_reorders, OPT_READ_ONLY}, // ptrt_reorder_tlas calls since the last geometry upload
     // the hipStream_t the context enqueues on (stream-ordering its device results)
     {"stream", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) { return (long long)(intptr_t)c->stream; }},
 };

@@ -578,7 +578,7 @@ class Scene {
     // rebuilds it as the reference's commit does)
     void syncTLAS() {
         buildTLAS();
-        hostTlasStale = false;
+        hostTlasStale = hostTlasOrderStale = false;
         flat.tlas_nodes = h_tlasNodes.data();
         flat.tlas_node_count = (int)h_tlasNodes.size();
         flat.tlas_mesh_indices = h_tlasMeshIndices.data();
@@ -690,7 +690,19 @@ class Scene {
         refitMovedInstances();
         resetAccumulation();
     }
-    void refitMovedInstances() { // (the work of refitInstanceChanges; a commit under GpuRefitAll comes here as well)
+    // refitInstanceChanges() with a fresh ORDER first: moved instances' matrices go over, then ptrt_reorder_tlas re-deals the
+    // meshes to the TLAS indices in Morton order of their world boxes' centres and refits (pt_tlas.hip.h) -- no upload, no
+    // synchronisation.  The host TLAS follows through the same arithmetic (reorderTLASOnHost's), so flatten() describes what
+    // the GPU traverses; where host root boxes lag the device's it follows by read-back when something reads it.
+    void reorderTLAS() {
+        needBackend();
+        if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
+            throw std::runtime_error("reorderTLAS: call uploadToGPU() first (the TLAS topology must already be on the GPU)");
+        refitMovedInstances(true);
+        resetAccumulation();
+    }
+    // (the work of refitInstanceChanges and reorderTLAS; a commit under GpuRefitAll comes here as well)
+    void refitMovedInstances(bool reorder = false) {
         std::vector<ptrt_instance_xform> run;
         int first = 0;
         auto flush = [&] {
@@ -714,14 +726,22 @@ class Scene {
             run.push_back(x);
         }
         flush();
-        check(ptrt_refit_tlas(ctx), "Failed to refit the TLAS");
+        if (reorder)
+            check(ptrt_reorder_tlas(ctx), "Failed to re-order the TLAS");
+        else
+            check(ptrt_refit_tlas(ctx), "Failed to refit the TLAS");
         bool roots_lag = hostTlasStale; // (host root boxes that lag the device's: the host TLAS follows by read-back, lazily)
         for (unsigned char st : hostTreeStale)
             roots_lag = roots_lag || st != 0;
-        if (roots_lag)
+        if (roots_lag) {
             hostTlasStale = true;
-        else
-            refitTLAS();
+            hostTlasOrderStale = hostTlasOrderStale || (reorder && h_tlasNodes.size() > 1);
+        } else {
+            const std::vector<AABB> world = meshWorldBoxes();
+            if (reorder)
+                mortonOrderTLAS(world);
+            refitTLASNode(0, world, 0);
+        }
     }
     // the host half alone, for a Scene without a back end (tests, tools that only flatten())
     void refitInstanceChangesOnHost() {
@@ -734,10 +754,25 @@ class Scene {
         refitTLAS();
         resetAccumulation();
     }
+    // Host twin of ptrt_reorder_tlas, for a Scene without a back end as well: h_tlasMeshIndices in Morton order of the meshes'
+    // world-box centres (mortonOrderTLAS), then refitTLAS() over the kept topology.
+    void reorderTLASOnHost() {
+        if (geometryDirty && ctx)
+            throw std::runtime_error("reorderTLASOnHost: geometry is dirty");
+        if (flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
+            prepareHostStructures();
+        for (size_t i = 0; i < meshes.size(); ++i)
+            takeInstanceMove(i);
+        const std::vector<AABB> world = meshWorldBoxes();
+        mortonOrderTLAS(world);
+        refitTLASNode(0, world, 0);
+        resetAccumulation();
+    }
     // Host twin of ptrt_refit_tlas: the boxes of h_tlasNodes over the topology they have -- every mesh's world box from its
     // root box through Transform3D::transformAABB (as buildTLAS takes it), every leaf the union of its members, every inner
     // node the union of its children.  min / max are exact: the device's refit gives the same bits.
-    void refitTLAS() {
+    void refitTLAS() { refitTLASNode(0, meshWorldBoxes(), 0); }
+    std::vector<AABB> meshWorldBoxes() const {
         if (h_tlasNodes.empty())
             throw std::runtime_error("refitTLAS: no TLAS built yet");
         std::vector<AABB> world(meshes.size());
@@ -748,7 +783,54 @@ class Scene {
             const DeviceBVHNode &root = m->bvhNodes[0];
             world[i] = m->transform.transformAABB(AABB{vec3(root.bmin.x, root.bmin.y, root.bmin.z), vec3(root.bmax.x, root.bmax.y, root.bmax.z)});
         }
-        refitTLASNode(0, world, 0);
+        return world;
+    }
+    // pt::reorder_tlas_kernel on the host (morton30 / spread10 of csrc/pt_build.hip.h restated: change both or neither), operation by operation (-ffp-contract=off on both sides): mesh i's key is the
+    // 30-bit Morton code of its world box's centre, (bmin + bmax) * 0.5f, within the bounds of all centres -- one scale, the
+    // largest extent; t = (c - lo) / ext clamped to [0, 1]; min((int)(t * 1024), 1023) per axis, x in the high bit; ext == 0:
+    // code 0 -- above the mesh index; TLAS index j gets the mesh ranked j.  The node array keeps its shape (the builder gives
+    // a mesh count one shape); the caller refits its boxes.  A single-leaf TLAS keeps its order, as on the device.
+    void mortonOrderTLAS(const std::vector<AABB> &world) {
+        if (h_tlasNodes.size() <= 1)
+            return;
+        const size_t n = meshes.size();
+        if (h_tlasMeshIndices.size() != n)
+            throw std::runtime_error("reorderTLAS: the TLAS does not index every mesh once");
+        std::vector<vec3> c(n);
+        vec3 lo(1e30f), hi(-1e30f);
+        for (size_t i = 0; i < n; ++i) {
+            c[i] = world[i].center();
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = c[i][k] < lo[k] ? c[i][k] : lo[k];
+                hi[k] = c[i][k] > hi[k] ? c[i][k] : hi[k];
+            }
+        }
+        float ext = 0.0f;
+        for (int k = 0; k < 3; ++k) {
+            const float e = hi[k] - lo[k];
+            ext = e > ext ? e : ext;
+        }
+        auto spread10 = [](uint32_t v) { // 10 bits -> every third bit
+            v = (v | (v << 16)) & 0x030000ffu;
+            v = (v | (v << 8)) & 0x0300f00fu;
+            v = (v | (v << 4)) & 0x030c30c3u;
+            v = (v | (v << 2)) & 0x09249249u;
+            return v;
+        };
+        std::vector<uint64_t> keys(n);
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t q[3];
+            for (int k = 0; k < 3; ++k) {
+                float t = ext > 0.0f ? (c[i][k] - lo[k]) / ext : 0.0f;
+                t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+                const int v = (int)(t * 1024.0f);
+                q[k] = (uint32_t)(v > 1023 ? 1023 : v);
+            }
+            keys[i] = ((uint64_t)((spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2])) << 32) | (uint32_t)i;
+        }
+        std::sort(keys.begin(), keys.end());
+        for (size_t j = 0; j < n; ++j)
+            h_tlasMeshIndices[j] = (int)(uint32_t)keys[j];
     }
     // A refitted TLAS degrades as instances travel: the topology is the upload's, and the boxes of far-apart members of a leaf
     // overlap their neighbours'.  reseatTLAS() is the reference's way for the TLAS alone -- rebuilt on the host over the meshes'
@@ -758,7 +840,7 @@ class Scene {
         needBackend();
         if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size())
             throw std::runtime_error("reseatTLAS: call uploadToGPU() first");
-        hostTlasStale = false; // (rebuilt below; only the meshes' own trees have to follow the device first)
+        hostTlasStale = hostTlasOrderStale = false; // (rebuilt below; only the meshes' own trees have to follow the device first)
         syncHostTrees();
         for (size_t i = 0; i < meshes.size(); ++i)
             takeInstanceMove(i);
@@ -1081,6 +1163,7 @@ class Scene {
     std::vector<size_t> uploadedVerts;
     std::vector<unsigned char> hostTreeStale, uploadedSoup;
     bool hostTlasStale = false; // the device refitted its TLAS (ptrt_refit_tlas) over root boxes the host has not followed yet
+    bool hostTlasOrderStale = false; // ... and re-ordered it (ptrt_reorder_tlas): the index array is read back with the boxes
     size_t gpuDynamicCommits = 0, geometryUploads = 0;
     double commitMicros = 0.0, compareMicros = 0.0;
 
@@ -1376,8 +1459,10 @@ class Scene {
             any = true;
         }
         if (hostTlasStale && ctx && !h_tlasNodes.empty()) { // the TLAS as the device refitted it (ptrt_read_tlas synchronises)
+            if (hostTlasOrderStale)
+                check(ptrt_read_tlas_order(ctx, h_tlasMeshIndices.data(), (int)h_tlasMeshIndices.size()), "Failed to read the TLAS order");
             check(ptrt_read_tlas(ctx, h_tlasNodes.data(), (int)h_tlasNodes.size()), "Failed to read the TLAS");
-            hostTlasStale = false;
+            hostTlasStale = hostTlasOrderStale = false;
         }
         return any;
     }
@@ -1401,7 +1486,7 @@ class Scene {
                                        flat.tlas_mesh_indices, flat.tlas_index_count),
                   "Failed to upload geometry");
             geometryDirty = instancesDirty = false;
-            hostTlasStale = false;
+            hostTlasStale = hostTlasOrderStale = false;
             ++geometryUploads;
             // what the device now holds, for the dynamic-geometry policy
             uploadedFaces.resize(meshes.size());
@@ -1426,7 +1511,7 @@ class Scene {
                                         flat.tlas_mesh_indices, flat.tlas_index_count),
                   "Failed to update instances");
             instancesDirty = false;
-            hostTlasStale = false;
+            hostTlasStale = hostTlasOrderStale = false;
         }
         if (materialsDirty) {
             check(ptrt_upload_materials(ctx, &flat.materials), "Failed to upload materials");

@@ -255,10 +255,14 @@ _sig("ptrt_build_bvh", C.c_int, _vp, C.c_int)
 _sig("ptrt_read_prim_order", C.c_int, _vp, C.c_int, C.POINTER(C.c_int), C.c_int)
 _sig("ptrt_update_triangles", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
 _sig("ptrt_set_instance_transforms", C.c_int, _vp, C.c_int, C.c_int, C.POINTER(InstanceXform))
+_sig("ptrt_set_instance_transforms_device", C.c_int, _vp, C.c_int, C.c_int, _vp)
 _sig("ptrt_refit_tlas", C.c_int, _vp)
 _sig("ptrt_read_tlas", C.c_int, _vp, C.POINTER(BvhNode), C.c_int)
 _sig("hs_refit_instance_changes", C.c_int, _vp, C.c_int)
+_sig("ptrt_reorder_tlas", C.c_int, _vp)
+_sig("ptrt_read_tlas_order", C.c_int, _vp, C.POINTER(C.c_int32), C.c_int)
 _sig("hs_reseat_tlas", C.c_int, _vp)
+_sig("hs_reorder_tlas", C.c_int, _vp, C.c_int)
 _sig("hs_rebuild_object_changes", C.c_int, _vp, C.c_int)
 _sig("hs_rebuild_from_device", C.c_int, _vp, C.c_int, _vp)
 _sig("hs_update_triangles", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
@@ -548,6 +552,41 @@ class Scene:
     def reseatTLAS(self):
         """A fresh TLAS topology: rebuilt on the host over the meshes' current boxes and uploaded (ptrt_update_instances)."""
         self._chk(lib.hs_reseat_tlas(self._h))
+
+    def reorderTLAS(self, host_only=False):
+        """refitInstanceChanges with a fresh order: moved instances' matrices go over, the meshes are re-dealt to the TLAS indices
+        in Morton order of their world boxes' centres on the device and the TLAS is refitted there (ptrt_reorder_tlas): no
+        upload, no host synchronisation; the host TLAS follows through the same arithmetic.
+        `host_only`: the host half alone, for a device=-1 scene."""
+        self._chk(lib.hs_reorder_tlas(self._h, int(bool(host_only))))
+
+    def set_instance_transforms_device(self, first, tensor):
+        """`ptrt_set_instance_transforms_device`: meshes first .. first + count - 1 take their has_transform bit and matrices from
+        `tensor`, a contiguous torch tensor on this scene's device whose rows are `ptrt_instance_xform` records (196 bytes:
+        world[16], inverse[16], normal[16] as float32 and has_transform as int32 -- shape (count, 49) of a 4-byte dtype or
+        (count, 196) of uint8), read in place by one launch on the context's stream: no copy, no synchronisation.  The
+        context's stream is ordered behind torch's current stream.  Follow with reorderTLAS / ptrt_reorder_tlas / ptrt_refit_tlas."""
+        if not _is_tensor(tensor):
+            raise ValueError("set_instance_transforms_device: needs a torch tensor on the scene's device")
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError(f"set_instance_transforms_device: tensor on {tensor.device}, this scene renders on cuda:{self.device}")
+        rec = C.sizeof(InstanceXform)
+        if not tensor.is_contiguous() or tensor.dim() != 2 or tensor.shape[1] * tensor.element_size() != rec:
+            raise ValueError(f"set_instance_transforms_device: needs a contiguous (count, {rec} bytes) tensor, got "
+                             f"{tuple(tensor.shape)} of {tensor.dtype}")
+        import torch
+        cur = torch.cuda.current_stream(tensor.device)
+        ctx_stream = torch.cuda.ExternalStream(self.get_option("stream"), device=tensor.device)
+        if ctx_stream.cuda_stream != cur.cuda_stream:
+            ctx_stream.wait_stream(cur)
+        self._cchk(lib.ptrt_set_instance_transforms_device(self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr())))
+
+    def read_tlas_order(self):
+        """The TLAS index array as the device holds it (ptrt_read_tlas_order; synchronises): int32 mesh indices."""
+        n = self.flatten().contents.tlas_index_count
+        out = np.zeros(n, dtype=np.int32)
+        self._cchk(lib.ptrt_read_tlas_order(self.ctx, out.ctypes.data_as(C.POINTER(C.c_int32)), n))
+        return out
 
     def read_tlas(self):
         """The TLAS as the device holds it (ptrt_read_tlas; synchronises): structured array bmin, bmax, left, right, start, count."""

@@ -7,6 +7,13 @@ Per frame: host microseconds inside the commit call (perf_counter around it) and
 stream around the whole run of commit + render_to_device, divided by the frames, so a stall of the host shows as a gap.  The two
 paths alternate, window by window, in one process; medians over the windows are reported with their range.
 
+And while the instances random-walk away from where the TLAS was built (--walk-frames of cumulative steps), every
+--reorder-every-th frame is committed
+  (c) by reorderTLAS(): ptrt_reorder_tlas re-deals the meshes over the kept TLAS shape on the stream, then refits;
+beside refitInstanceChanges() on every frame and reseatTLAS() (host rebuild, synchronises) on those frames.  Reported: the
+frame time of the frames AFTER such a frame (events around the refit-only frames up to the next one), i.e. what the fresher
+tree is worth, and the host microseconds of the call itself.
+
 Also: the PMODE 3 frame time after a vertex refit of one mesh, with the instances' first-pass boxes left invalid (ptrt_refit
 alone: inst_pre_ok 0) and recomputed on the device (ptrt_refit + ptrt_refit_tlas: inst_pre_ok 1), same frames otherwise.
 
@@ -97,6 +104,59 @@ def measure_moves(a):
     return rows
 
 
+def measure_walk(a):
+    """instances random-walk; every `reorder_every`-th frame goes through refit / reorderTLAS / reseatTLAS, the others through
+    refitInstanceChanges; timed: the frames between those frames"""
+    inst = [BASE + j for j in range(0, N_EXTRA, 3)]
+    names = ("refit", "reorder", "reseat")
+    scenes = {name: build(a.width, a.height, a.spp, a.depth) for name in names}
+    special = {"refit": scenes["refit"].refitInstanceChanges, "reorder": scenes["reorder"].reorderTLAS, "reseat": scenes["reseat"].reseatTLAS}
+    stream = torch.cuda.Stream()
+    out = torch.empty(a.width * a.height * 3, dtype=torch.uint8, device="cuda")
+    for s in scenes.values():
+        s.set_stream(stream.cuda_stream)
+    d0 = scenes["refit"].flatten().contents
+    pos = {name: np.array([[d0.meshes[m].world[3], d0.meshes[m].world[7], d0.meshes[m].world[11]] for m in inst]) for name in names}
+    rs = {name: np.random.RandomState(1) for name in names}  # the same walk in every scene
+    res = {name: {"host_us": [], "frame_ms": []} for name in names}
+
+    def step(name):
+        pos[name] += rs[name].uniform(-a.walk_step, a.walk_step, pos[name].shape)
+        for m, p in zip(inst, pos[name]):
+            scenes[name].setPosition(m, tuple(float(x) for x in p))
+
+    with torch.cuda.stream(stream):
+        for seg in range(a.walk_frames // a.reorder_every):
+            for name, s in scenes.items():
+                step(name)
+                t0 = time.perf_counter()
+                special[name]()
+                host = 1e6 * (time.perf_counter() - t0)
+                s.render_to_device(out.data_ptr())
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reorder_every - 1):
+                    step(name)
+                    s.refitInstanceChanges()
+                    s.render_to_device(out.data_ptr())
+                e1.record(stream)
+                e1.synchronize()
+                if seg:  # (segment 0 warms every path up)
+                    res[name]["host_us"].append(host)
+                    res[name]["frame_ms"].append(e0.elapsed_time(e1) / (a.reorder_every - 1))
+    row = {"case": "random_walk", "meshes": BASE + N_EXTRA, "walking": len(inst), "step": a.walk_step, "frames": a.walk_frames,
+           "every": a.reorder_every, "size": [a.width, a.height], "spp": a.spp, "depth": a.depth,
+           "tlas_reorders": scenes["reorder"].get_option("tlas_reorders"), "library": P.library_info()["sha16"]}
+    for name in names:
+        row[f"{name}_call_host_us"] = summary(res[name]["host_us"])
+        row[f"{name}_frames_after_ms"] = summary(res[name]["frame_ms"])
+    print(json.dumps(row), flush=True)
+    for s in scenes.values():
+        s.sync()
+        s.close()
+    return [row]
+
+
 def measure_pretest(a):
     """frames after a vertex refit of one mesh, first-pass boxes invalid vs recomputed on the device"""
     s = build(a.width, a.height, a.spp, a.depth)
@@ -144,9 +204,12 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=1)
     ap.add_argument("--depth", type=int, default=4)
+    ap.add_argument("--walk-frames", type=int, default=600, help="frames of the random walk (0: skip it)")
+    ap.add_argument("--walk-step", type=float, default=0.05, help="largest step per axis and frame")
+    ap.add_argument("--reorder-every", type=int, default=20, help="every k-th frame of the walk takes the path under test")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    rows = measure_moves(a) + measure_pretest(a)
+    rows = measure_moves(a) + (measure_walk(a) if a.walk_frames >= 2 * a.reorder_every else []) + measure_pretest(a)
     if a.out:
         with open(a.out, "w") as f:
             json.dump({"command": f"python3 tools/tlas_refit_time.py --moved {a.moved} --frames {a.frames} --windows {a.windows} "
