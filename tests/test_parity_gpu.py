@@ -240,7 +240,7 @@ def test_real_tlas_many_meshes(P, O, blue_noise, pair_trace, leaf):
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_real_tlas_of_hostile_instances(P, O, blue_noise, seed):
-    """PMODE 3's conservative world-space pre-test of instance root boxes (ptrt_capi.hip upload_instance_pretests) must
+    """PMODE 3's conservative world-space pre-test of instance root boxes (ptrt_accel.hip.h upload_instance_pretests) must
     never reject a ray the reference's local-space test accepts.  56 instances only -- thin slabs, needles, large and tiny
     scales, every rotation, translations that hit the reference's wrong mat4::inverse (rotation + x translation), some far
     from the origin, boxes that touch and overlap -- and a camera INSIDE the cloud, so rays start in and next to the boxes;
