@@ -628,6 +628,11 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         longest path.  Same bits.  -1 (default): on where it was measured to pay -- at most 4 bounces (Cornell
  *                         1.76 -> 1.64 ms, 136 meshes 15.9 -> 14.8, the fluid frame -3 %, scenes of short paths even; 5 bounces and more lose).
  *                         ptrt_get_option "sample_sync_eff" says what the last frame did.
+ *   pm1_dense_roots -1|0|1   PMODE 1: a trace whose live rays fill at most half the wave deals its root-box tests over all 64
+ *                         lanes -- 2 or 4 meshes per slab round instead of one.  Same pair list, same bits.
+ *                         -1 (default): on with at least four meshes in the leaf, decided on the host from the scene (Cornell 1080p
+ *                         1.455 -> 1.421 ms, 8 bounces 1.856 -> 1.819); 0: never;
+ *                         1: always.  ptrt_get_option "pm1_dense_roots_eff" says what the last frame did.
  *   tile_run 0..64        the one-tile-per-workgroup kernels' workgroup -> tile map.  Consecutive workgroups go to the eight XCDs in
  *                         turn; with n > 0, of every 8 n consecutive tiles XCD x renders tiles [x n, (x + 1) n) -- neighbours,
  *                         whose rays walk the same part of the trees, share an L2 -- instead of every eighth tile.  8 (default):

@@ -79,6 +79,7 @@ struct KParams {
     int tlas_depth;     // PMODE 3: TLAS stack entries per lane
     int tlas_any_rounds; // PMODE 3 shadow rays: 1 = one TLAS leaf per ray and fill (more than 1024 meshes, or option tlas_rounds)
     int pair_split;     // PMODE 1: a batch that does not fill the wave may give each pair several lanes
+    int pm1_dense;      // PMODE 1: a call with at most 32 live rays deals its root-box tests over all lanes (build_pairs_dense)
     int steal;          // PMODE 2 any-hit: 0 off; n > 0: idle lanes steal subtrees, node loop yields every n steps
     int csteal;         // PMODE 2 closest hit: 0 off; n > 0: verified subtree stealing (run_closest_queue), node loop yields every n steps
     int csteal_min;     // ... node steps a walk must have taken before its stack may be stolen from

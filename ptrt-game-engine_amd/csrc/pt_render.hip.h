@@ -183,6 +183,7 @@ PT_DEV PairLds carve_pair_lds_wg(void *base, int wave, int meshes, int stack_ent
 // calls, pairs, node wave-iterations, node lane-steps, leaf phases, triangle wave-iterations,
 // triangle lane-tests, outer iterations; [16] persistent-loop iterations, [17] live lanes in them.
 __device__ unsigned long long g_trav_bounce[64]; // the traversal counters [0..15] once more, split by the rays' bounce: [bounce 0..3][16]
+__device__ unsigned long long g_trav_rhist[8]; // build_pairs calls by live rays (TS_RHIST)
 __device__ unsigned long long g_trav_stats[32]; // [0..7] closest, [8..15] any-hit, [16..17] loop, [18..23] lanes per phase (TS_LANES), [24..31] cycles (CycleAcc)
 // -DPT_MARKS: "; MARK x" comments in the ISA at the phase boundaries of path_trace_kernel (tools/asm_phases.py counts the
 // instructions between them)
@@ -243,6 +244,13 @@ struct CycleAcc {
         if (lane == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))                                                   \
             atomicAdd(&g_trav_stats[slot], (unsigned long long)__builtin_popcountll(ts_m));                                 \
     } while (0)
+// calls of build_pairs by the rays they carry behind the TLAS root test: [0..3] closest hit with 0, 1..16, 17..32, 33..64, [4..7] any hit
+#define TS_RHIST(any, cond)                                                                                              \
+    do {                                                                                                                 \
+        const int ts_r = __builtin_popcountll(__builtin_amdgcn_ballot_w64(cond));                                        \
+        if (lane == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))                                                   \
+            atomicAdd(&g_trav_rhist[((any) ? 4 : 0) + (ts_r == 0 ? 0 : ts_r <= 16 ? 1 : ts_r <= 32 ? 2 : 3)], 1ull);       \
+    } while (0)
 #define TS_NOW() __builtin_readcyclecounter()
 #define TS_ADD(slot, t) (cyc.c[(slot) - 8] += __builtin_readcyclecounter() - (t))
 #define TS_ADDL(slot, t) (L.cyc->c[(slot) - 8] += __builtin_readcyclecounter() - (t))
@@ -270,6 +278,7 @@ struct CycleAcc {
     PT_DEV void flush(int) {}
 };
 #define TS_LANES(slot, cond)
+#define TS_RHIST(any, cond)
 #define TS_NOW() 0ull
 #define TS_ADD(slot, t) (void)(t)
 #define TS_ADDL(slot, t) (void)(t)
@@ -323,16 +332,97 @@ PT_DEV void leaf_prefix(int cnt, int &start, int &total) {
     total = tot;
 }
 
-// step 1: root-box tests + ballot/prefix-sum compaction into the LDS pair list
+// PMODE 1, option "pm1_dense_roots": the root-box tests of a call whose R live rays fill at most half the wave, dealt over all
+// 64 lanes.  The lock-step loop below spends one slab round per mesh whatever R is; with the samples in step a shadow call
+// carries ~27 rays and a deep-bounce extension call fewer.  Here the wave splits into G = 2 (R <= 32) or 4 (R <= 16) groups
+// of 64 / G lanes; lane l takes the ray of ballot rank l mod (64 / G) and, in round j, mesh G * j + l / (64 / G): ceil(M / G)
+// rounds instead of M.  A ray's origin, 1 / d and limit come from its owner lane's registers by ds_bpermute, once per call
+// (the slab test reads nothing else; 1 / d is the owner's make_ray result, so nothing is computed twice); the mesh head is a
+// per-lane read of the staged copy, G distinct addresses per instruction.  Each (ray, mesh) item runs the slab test the
+// lock-step loop runs for it, and a round appends its hits in lane order = mesh order, then owner lane: the pair list is the
+// lock-step loop's list entry for entry, so everything behind it is untouched.
+// The rank -> owner table sits in the upper half of the pair list: R <= 32 rays make at most 32 * M entries of the 64 * M.
 template <bool ANY>
+PT_DEV int build_pairs_dense(const KParams &K, const PairLds &L, int lane, bool alive, unsigned long long lm, int R, const RayO &w,
+                             float tMax) {
+    const int M = K.pair_meshes;
+    unsigned char *own = (unsigned char *)L.pairs + 64 * M;
+    if (alive)
+        own[lane_prefix(lm)] = (unsigned char)lane;
+    wave_sync();
+    const int wsh = R <= 16 ? 4 : 5; // log2 of the lanes per group
+    const int rk = lane & ((1 << wsh) - 1), G = 64 >> wsh;
+    const bool has = rk < R;
+    // the entry this lane may append in the current round: {owner lane, mesh order << 6}
+    uint32_t e = (uint32_t)(has ? (int)own[rk] : lane) | ((uint32_t)(lane >> wsh) << 6);
+    // (every lane executes the shuffles: a source lane must be active for ds_bpermute)
+    RayO q;
+    q.o = mk3(__shfl(w.o.x, (int)(e & 63u)), __shfl(w.o.y, (int)(e & 63u)), __shfl(w.o.z, (int)(e & 63u)));
+    q.inv = mk3(__shfl(w.inv.x, (int)(e & 63u)), __shfl(w.inv.y, (int)(e & 63u)), __shfl(w.inv.z, (int)(e & 63u)));
+    q.d = q.inv; // (not read by the slab test; an instance's round fetches the direction)
+    q.sx = q.inv.x < 0;
+    q.sy = q.inv.y < 0;
+    q.sz = q.inv.z < 0;
+    const float tm = ANY ? __shfl(tMax, (int)(e & 63u)) : T_FAR;
+    int base = 0;
+    for (int i0 = 0; i0 < M; i0 += G, e += (uint32_t)G << 6) {
+        const int i = (int)(e >> 6);
+        const float *hp = (const float *)L.meshbox + 8 * (i < M ? i : 0);
+        const int fm = __float_as_int(lds_ld1(hp, 7)); // (staged as flags | mesh id << 8)
+        const bool cand = has && i < M && !(ANY && (fm & 2));
+        const bool xf = cand && (fm & 1);
+        float tE;
+        bool hb = cand && !xf &&
+                  slab(mk3(lds_ld1(hp, 0), lds_ld1(hp, 1), lds_ld1(hp, 2)), mk3(lds_ld1(hp, 4), lds_ld1(hp, 5), lds_ld1(hp, 6)), q, tm, tE);
+        if (__builtin_amdgcn_ballot_w64(xf)) { // (wave-uniform: the shuffles run with every lane)
+            RayO wr = q;
+            wr.d = mk3(__shfl(w.d.x, (int)(e & 63u)), __shfl(w.d.y, (int)(e & 63u)), __shfl(w.d.z, (int)(e & 63u)));
+            if (xf) {
+                float ds;
+                const RayO lr = local_ray(K, fm >> 8, wr, ds);
+                wave_lds_order(); // (the box is read again here instead of kept across the transform)
+                hb = slab(mk3(lds_ld1(hp, 0), lds_ld1(hp, 1), lds_ld1(hp, 2)), mk3(lds_ld1(hp, 4), lds_ld1(hp, 5), lds_ld1(hp, 6)), lr,
+                          ANY ? tm * ds : T_FAR, tE);
+            }
+        }
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(hb);
+        if (hb) {
+            ((uint16_t *)L.pairs)[base + lane_prefix(bal)] = (uint16_t)e;
+        }
+        base += __builtin_popcountll(bal);
+    }
+    return base;
+}
+
+// The lane index as the shadow trace of PMODE 1 uses it for its own words of the flag and limit planes: opaque, so that the
+// address is made where it is used.  Hoisted out of the persistent loop it was one register held through every phase of
+// the frame -- the one the lane-refill kernel had to keep in scratch once build_pairs_dense was in the loop.
+PT_DEV int lane_here(int lane) {
+    int z = 0;
+    asm volatile("" : "+s"(z));
+    return lane + z;
+}
+
+// step 1: root-box tests + ballot/prefix-sum compaction into the LDS pair list
+// (DENSE: the caller is PMODE 1, where K.pm1_dense may hand a half-empty wave's call to build_pairs_dense)
+template <bool ANY, bool DENSE = false>
 PT_DEV int build_pairs(const KParams &K, const PairLds &L, int lane, bool alive, f3 o, f3 d, float tMax) {
     const RayO w = make_ray(o, d);
     float tE;
     alive = alive && slab(tlas_bmin(K), tlas_bmax(K), w, ANY ? tMax : T_FAR, tE);
     if (ANY)
-        L.occ[lane] = 0u;
+        L.occ[DENSE ? lane_here(lane) : lane] = 0u;
     else
         L.best[lane] = ~0ull;
+    TS_RHIST(ANY, alive);
+    if (DENSE && K.pm1_dense) {
+        const unsigned long long lm = __builtin_amdgcn_ballot_w64(alive);
+        const int R = __builtin_popcountll(lm);
+        if (R == 0)
+            return 0;
+        if (R <= 32)
+            return build_pairs_dense<ANY>(K, L, lane, alive, lm, R, w, tMax);
+    }
     // (the mesh heads come out of LDS, staged at kernel start: read from memory here -- mesh id, then its record, one
     // dependent round trip each -- the loop took ~0.7 us per mesh and ~25 % of a showcase wave's time.  Reading head i + 1
     // while mesh i's box is tested was measured in round 3: Cornell 1.81 -> 1.85 ms, the registers cost more than the round trip)
@@ -373,8 +463,9 @@ template <int GEN = 0> PT_DEV void pair_ray_from(const KParams &K, const int4 mt
     }
 }
 
+template <bool DENSE = false>
 PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool alive, f3 o, f3 d, int &order) {
-    const int P = build_pairs<false>(K, L, lane, alive, o, d, T_FAR);
+    const int P = build_pairs<false, DENSE>(K, L, lane, alive, o, d, T_FAR);
     wave_sync();
     for (int c = 0; c < P; c += 64) {
         // a batch that does not fill the wave (the last one) gives every pair 2^sh lanes, each testing every
@@ -457,11 +548,12 @@ PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool 
     return h;
 }
 
+template <bool DENSE = false>
 PT_DEV bool any_hit_pairs(const KParams &K, const PairLds &L, int lane, bool alive, f3 o, f3 d, float tMax) {
-    const int P = build_pairs<true>(K, L, lane, alive, o, d, tMax);
-    // per-lane tMax travels with the ray: reuse the `best` words as a float plane
+    // per-lane tMax travels with the ray: reuse the `best` words as a float plane (the builder writes the flags behind it)
     float *tmaxv = (float *)L.best;
-    tmaxv[lane] = tMax;
+    tmaxv[DENSE ? lane_here(lane) : lane] = tMax;
+    const int P = build_pairs<true, DENSE>(K, L, lane, alive, o, d, tMax);
     wave_sync();
     for (int c = 0; c < P; c += 64) {
         const int n = (P - c) < 64 ? (P - c) : 64; // 2^sh lanes per pair in a batch that does not fill the wave
@@ -500,7 +592,7 @@ PT_DEV bool any_hit_pairs(const KParams &K, const PairLds &L, int lane, bool ali
             L.occ[r] = 1u;
     }
     wave_sync();
-    const bool occluded = alive && (L.occ[lane] != 0u);
+    const bool occluded = alive && (L.occ[DENSE ? lane_here(lane) : lane] != 0u);
     wave_sync();
     return occluded;
 }
@@ -2113,7 +2205,7 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
             }
         } else {
             const unsigned long long t_tr = TS_NOW();
-            h = (PMODE == 1)   ? closest_hit_pairs(KB, PL, lane, act, ro, rd, h_order)
+            h = (PMODE == 1)   ? closest_hit_pairs<true>(KB, PL, lane, act, ro, rd, h_order)
                 : (PMODE == 2) ? closest_hit_pairs_dyn(KB, PL, lane, act, ro, rd)
                 : (PMODE == 3) ? closest_hit_pairs_tlas(KB, PL, lane, act, ro, rd, cyc)
                                : closest_hit<GEOM>(KB, act, ro, rd, stk);
@@ -2324,7 +2416,7 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
                 pending = true;
             }
         } else if (__builtin_amdgcn_ballot_w64(lit)) {
-            const bool in_shadow = (PMODE == 1)   ? any_hit_pairs(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
+            const bool in_shadow = (PMODE == 1)   ? any_hit_pairs<true>(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
                                    : (PMODE == 2) ? any_hit_pairs_dyn(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
                                    : (PMODE == 3) ? any_hit_pairs_tlas(KD, PL, lane, lit, shadow_o, L, shadow_tmax, cyc)
                                                   : any_hit<GEOM>(KD, lit, shadow_o, L, shadow_tmax, stk);

@@ -190,6 +190,8 @@ struct ptrt_ctx {
     unsigned int *d_queue = nullptr; // {ticket, waves out} per launch lane: [0] the stream, [1 + i] auxiliary stream i
     int sample_sync = -1;            // option "sample_sync": -1 (default) where it was measured to pay, 0 never, 1 always (ptrt_render)
     int sample_sync_eff = 0;         // ... the last frame
+    int pm1_dense_roots = -1;        // option "pm1_dense_roots": -1 (default) where it pays, 0 never, 1 always (ptrt_render)
+    int pm1_dense_roots_eff = 0;     // ... the last frame (0 as well when another traversal mode rendered it)
     int tile_run = 8;                // option "tile_run": of every 8 * run consecutive tiles XCD x renders a run of neighbours (path_trace_kernel); 0: tile k on workgroup k
     int ticket_tiles = 1;            // option "ticket_tiles": consecutive tiles per ticket of the queue
     int persist = 0, n_cus = 0;      // option "persist": persistent waves per CU (0 = the variant's occupancy)
@@ -1675,6 +1677,12 @@ int ptrt_render(ptrt_ctx *c, int frame_index, int spp, int max_depth, void *out_
     const bool tuning = choose_loop_shape(c, spp, max_depth, geom);
     const int pmode = pair_mode(c, geom, c->merged_eff != 0);
     c->last_pmode = pmode;
+    // Dense root tests (build_pairs_dense): a call with R <= 32 live rays runs ceil(M / G) slab rounds instead of M, G = 2 or 4,
+    // for one ballot, a 32-byte LDS table and seven or eight ds_bpermute -- about what half a slab round issues.  With fewer
+    // than four meshes in the leaf G = 2 saves at most one round: not worth the branch.  Decided here, once per frame, from the
+    // scene alone.
+    K.pm1_dense = (pmode == 1 && (c->pm1_dense_roots >= 0 ? c->pm1_dense_roots : (c->pair_meshes >= 4 ? 1 : 0))) ? 1 : 0;
+    c->pm1_dense_roots_eff = K.pm1_dense;
     // (round 2: the merged loop was at its best WITHOUT shadow-ray subtree stealing, 3.98 vs 4.17 ms on the showcase frame -- its
     // yields served ten shadow pairs at the price of sixty closest-hit walks; with the closest-hit walks stolen from as well the
     // yields pay for both kinds: 3.19 ms with, 3.49 without)

@@ -62,6 +62,7 @@ const Option OPTIONS[] = {
     {"pipeline", &ptrt_ctx::pipeline, OPT_BOOL}, // 1 (default): consecutive frames may overlap on the device when that is safe (ptrt_render); 0: never
     {"persist", &ptrt_ctx::persist, OPT_CLAMP, 0, INT_MAX},
     {"sample_sync", &ptrt_ctx::sample_sync, OPT_TRISTATE},
+    {"pm1_dense_roots", &ptrt_ctx::pm1_dense_roots, OPT_TRISTATE}, // PMODE 1: root-box tests of a half-empty wave dealt over all lanes
     {"tile_run", &ptrt_ctx::tile_run, OPT_REJECT, 0, 64}, // 0 (tile k on workgroup k) or the tiles per XCD and run, 1..64
     {"ticket_tiles", &ptrt_ctx::ticket_tiles, OPT_CLAMP, 1, 16},
     {"refill", &ptrt_ctx::refill, OPT_CLAMP, 0, 2},
@@ -82,6 +83,7 @@ const Option OPTIONS[] = {
     {"use_graphs", &ptrt_ctx::use_graphs, OPT_BOOL}, // 0: issue the refit / rebuild launches one by one instead of replaying a hipGraph
     // read-only facts about the last ptrt_render (so that a measurement can say what ran)
     {"sample_sync_eff", &ptrt_ctx::sample_sync_eff, OPT_READ_ONLY},
+    {"pm1_dense_roots_eff", &ptrt_ctx::pm1_dense_roots_eff, OPT_READ_ONLY},
     {"refilled", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->refill_eff ? 1 : 0; }},
     {"split_eff", &ptrt_ctx::split_eff, OPT_READ_ONLY},
     {"pipelined", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->pipelined_last ? 1 : 0; }},
@@ -180,6 +182,17 @@ int ptrt_debug_trav_bounce(ptrt_ctx *c, unsigned long long *out64) {
 }
 
 #ifdef PT_TRAV_STATS
+// ... and pt::g_trav_rhist (8 words: build_pairs calls by their live rays, TS_RHIST)
+int ptrt_debug_trav_rhist(ptrt_ctx *c, unsigned long long *out8) {
+    if (!ctx_live(c) || !out8)
+        return fail(c, PTRT_E_INVALID, "ptrt_debug_trav_rhist: bad argument");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyFromSymbol(out8, HIP_SYMBOL(pt::g_trav_rhist), 8 * sizeof(unsigned long long)));
+    unsigned long long zero[8] = {};
+    HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(pt::g_trav_rhist), zero, sizeof(zero)));
+    return PTRT_OK;
+}
+
 int ptrt_debug_trav_dbg(ptrt_ctx *c, unsigned long long *out1033) {
     if (!ctx_live(c) || !out1033)
         return fail(c, PTRT_E_INVALID, "ptrt_debug_trav_dbg: bad argument");

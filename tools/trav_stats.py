@@ -59,6 +59,16 @@ for name, b in (("closest", 0), ("any-hit", 8)):
     print(f"   leaf phases/call {lp / calls:.1f}; triangle loop: {tw / calls:.1f} wave-iterations/call, lanes busy "
           f"{100.0 * tl / max(1, tw * 64):.1f} %  ({tl / max(1, pairs):.1f} triangles per pair)")
 vb = list(outb)
+if hasattr(P.lib, "ptrt_debug_trav_rhist"):  # root-test calls by the rays they carry (TS_RHIST)
+    rh = (C.c_ulonglong * 8)()
+    P.lib.ptrt_debug_trav_rhist.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    assert P.lib.ptrt_debug_trav_rhist(s.ctx, rh) == 0
+    for name, o in (("closest", 0), ("any-hit", 4)):
+        n = sum(rh[o:o + 4])
+        if n:
+            print(f"{name} root-test calls {n} by live rays R: " + ", ".join(
+                f"{lab} {100.0 * rh[o + k] / n:.1f} %" for k, lab in enumerate(("0", "1-16", "17-32", "33-64"))) +
+                f"  (dense roots: {s.get_option('pm1_dense_roots_eff')})")
 if hasattr(P.lib, "ptrt_debug_trav_dbg"):
     import struct
     dbg = (C.c_ulonglong * 1033)()
