@@ -633,6 +633,13 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         -1 (default): on with at least four meshes in the leaf, decided on the host from the scene (Cornell 1080p
  *                         1.455 -> 1.421 ms, 8 bounces 1.856 -> 1.819); 0: never;
  *                         1: always.  ptrt_get_option "pm1_dense_roots_eff" says what the last frame did.
+ *   pm1_full_leaf -1|0|1  PMODE 1: when every leaf staged in LDS holds exactly as many triangles as the largest one (a scene of
+ *                         cubes: 12 each), the triangle loops of the closest-hit and shadow traces leave out what only a shorter
+ *                         leaf needs -- the count compare, the clamped slot, the address arithmetic per test -- and step one
+ *                         pointer per pair.  The same tests in the same order: same bits.  -1 (default) and 1:
+ *                         on when the leaves are uniform, decided on the host at upload; 0: never.  The batched ray queries
+ *                         share the loops.  ptrt_get_option "pm1_full_leaf_eff" says what the last frame did (0 as well when
+ *                         the leaves differ or another traversal mode rendered it).
  *   tile_run 0..64        the one-tile-per-workgroup kernels' workgroup -> tile map.  Consecutive workgroups go to the eight XCDs in
  *                         turn; with n > 0, of every 8 n consecutive tiles XCD x renders tiles [x n, (x + 1) n) -- neighbours,
  *                         whose rays walk the same part of the trees, share an L2 -- instead of every eighth tile.  8 (default):

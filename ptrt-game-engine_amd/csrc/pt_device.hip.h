@@ -65,6 +65,20 @@ PT_DEV float rcp_ieee(float y) {
         r = mid ? r : 1.0f / y;
     return r;
 }
+// rcp_ieee for a caller that DISCARDS the result whenever |y| < 2^-60 (tri_test: a determinant that small is rejected before
+// anything made from 1/a is looked at).  That leaves the upper bound of the guarded range, and one compare has it: false for
+// |y| >= 2^60, for an infinity and for NaN, which take the compiler's division as in rcp_ieee.  Equal in bits to `1.0f / y`
+// for every input with |y| >= 2^-60 (tests/test_pm1_full_leaf_gpu.py, all 2^32 patterns); below that the value is whatever
+// the bare Newton core gives.
+PT_DEV float rcp_ieee_above(float y) {
+    const float r0 = __builtin_amdgcn_rcpf(y);
+    const float e = fma_(-y, r0, 1.0f);
+    float r = fma_(e, r0, r0);
+    const bool below = __builtin_fabsf(y) < 0x1p60f;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!below) != 0ull, 0))
+        r = below ? r : 1.0f / y;
+    return r;
+}
 // v / t for a vector: the reference divides component by component (vec3.cuh:54-56), so three IEEE divisions share their
 // divisor -- and hipcc's expansion of each (above) shares nothing, because v_div_scale looks at both operands.  With the
 // correctly rounded reciprocal r = RN(1/t) of rcp_ieee's Newton core, ONE residual step per component is enough

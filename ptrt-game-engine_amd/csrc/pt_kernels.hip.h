@@ -79,6 +79,7 @@ struct KParams {
     int tlas_depth;     // PMODE 3: TLAS stack entries per lane
     int tlas_any_rounds; // PMODE 3 shadow rays: 1 = one TLAS leaf per ray and fill (more than 1024 meshes, or option tlas_rounds)
     int pair_split;     // PMODE 1: a batch that does not fill the wave may give each pair several lanes
+    int pm1_full_leaf;  // PMODE 1: every staged leaf has exactly pair_max_leaf triangles: the triangle loops skip the partial-leaf handling
     int pm1_dense;      // PMODE 1: a call with at most 32 live rays deals its root-box tests over all lanes (build_pairs_dense)
     int steal;          // PMODE 2 any-hit: 0 off; n > 0: idle lanes steal subtrees, node loop yields every n steps
     int csteal;         // PMODE 2 closest hit: 0 off; n > 0: verified subtree stealing (run_closest_queue), node loop yields every n steps
@@ -190,17 +191,21 @@ PT_DEV bool slab(f3 bmin, f3 bmax, const RayO &r, float tMax, float &tEntry) {
 
 // triangle_intersect_fast (intersection.cuh:219-255) on a pre-differenced packet, plus
 // the caller's `t > 1e-5f` acceptance (intersection.cuh:329,379), branch-free.
+// The reference accepts `t > 1e-6f && t < tMax` (intersection.cuh:219-255) and its callers then ask `t > 1e-5f`
+// (intersection.cuh:329,379): the second lower bound implies the first for every float and both are false for NaN, so one
+// compare stands for the two.  1/a comes from rcp_ieee_above: with |a| < 1e-6 (2^-60 is far below) the first conjunct
+// rejects the lane whatever f, u, v and t are, and no caller reads t, u or v of a rejected test.
 PT_DEV bool tri_test(f3 v0, f3 e1, f3 e2, const RayO &r, float tMax, float &t_out, float &u_out, float &v_out) {
     const f3 h = cross(r.d, e2);
     const float a = dot(e1, h);
-    const float f = rcp_ieee(a);
+    const float f = rcp_ieee_above(a);
     const f3 s = r.o - v0;
     const float u = f * dot(s, h);
     const f3 q = cross(s, e1);
     const float v = f * dot(r.d, q);
     const float t = f * dot(e2, q);
     const bool ok = !(__builtin_fabsf(a) < 1e-6f) && !(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) &&
-                    (t > 1e-6f && t < tMax) && (t > 1e-5f);
+                    (t > 1e-5f && t < tMax);
     t_out = t;
     u_out = u;
     v_out = v;
@@ -830,6 +835,25 @@ __global__ void rcp_check_kernel(unsigned int *out) {
         const uint32_t wu = __float_as_uint(want), gu = __float_as_uint(got);
         const bool both_nan = (want != want) && (got != got);
         if (wu != gu && !both_nan) {
+            const unsigned int k = atomicAdd(&out[0], 1u);
+            if (k < 8)
+                out[1 + k] = (uint32_t)b;
+        }
+    }
+}
+
+// the same for rcp_ieee_above, over the inputs its contract covers: |y| >= 2^-60 -- infinities included -- and NaN.
+__global__ void rcp_above_check_kernel(unsigned int *out) {
+    const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long b = tid; b < (1ull << 32); b += stride) {
+        const float y = __uint_as_float((uint32_t)b);
+        const float want = 1.0f / y;
+        const float got = rcp_ieee_above(y);
+        const uint32_t wu = __float_as_uint(want), gu = __float_as_uint(got);
+        const bool both_nan = (want != want) && (got != got);
+        const bool covered = !(__builtin_fabsf(y) < 0x1p-60f); // (true for NaN)
+        if (covered && wu != gu && !both_nan) {
             const unsigned int k = atomicAdd(&out[0], 1u);
             if (k < 8)
                 out[1 + k] = (uint32_t)b;

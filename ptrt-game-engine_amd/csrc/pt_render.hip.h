@@ -463,6 +463,11 @@ template <int GEN = 0> PT_DEV void pair_ray_from(const KParams &K, const int4 mt
     }
 }
 
+// PMODE 1, option "pm1_full_leaf": may this batch's triangle loop leave out the partial-leaf handling?  Wave-uniform.  The
+// host sets K.pm1_full_leaf when every staged leaf has exactly pair_max_leaf triangles; a batch whose 2^sh lanes per pair
+// do not divide that count has a tail behind the leaf's end and keeps the guarded loop (12 triangles: never -- sh <= 2).
+PT_DEV bool pm1_full_batch(const KParams &K, int sh) { return K.pm1_full_leaf && (K.pair_max_leaf & ((1 << sh) - 1)) == 0; }
+
 template <bool DENSE = false>
 PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool alive, f3 o, f3 d, int &order) {
     const int P = build_pairs<false, DENSE>(K, L, lane, alive, o, d, T_FAR);
@@ -495,17 +500,36 @@ PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool 
         // (software-pipelining these LDS reads one packet ahead was measured: 2.82 vs 2.75 ms -- with four
         // waves per SIMD the latency is already covered and the extra live registers cost more)
         const int iters = (K.pair_max_leaf + (1 << sh) - 1) >> sh;
-        for (int it = 0; it < iters; ++it) {
-            const int i = sub + (it << sh);
-            const int slot = mt.x + (i < mt.y ? i : 0);
-            const float4 *tp = L.tris + slot * 3 + oi * PAIR_PAD;
-            const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
-            asm volatile("" ::"v"(p0.w), "v"(p1.w), "v"(p2.w)); // keep the loads ds_read_b128 (b96 is half rate)
-            float t, u, v;
-            const bool ok = tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), pr, tb, t, u, v);
-            if (ok && i < mt.y) {
-                tb = t;
-                bi = i;
+        if (pm1_full_batch(K, sh)) {
+            // every staged leaf holds pair_max_leaf triangles and 2^sh divides that: no test lies behind the end of a leaf,
+            // so the count compare, the clamped slot and the address arithmetic go -- one pointer per pair, one step per
+            // test.  The same tests in the same order as the loop below: same bits.
+            const float4 *tp = L.tris + (mt.x + sub) * 3 + oi * PAIR_PAD;
+            const int step = 3 << sh;
+            int bit = -1;
+            for (int it = 0; it < iters; ++it, tp += step) {
+                const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
+                asm volatile("" ::"v"(p0.w), "v"(p1.w), "v"(p2.w)); // keep the loads ds_read_b128 (b96 is half rate)
+                float t, u, v;
+                if (tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), pr, tb, t, u, v)) {
+                    tb = t;
+                    bit = it;
+                }
+            }
+            bi = bit < 0 ? -1 : sub + (bit << sh);
+        } else {
+            for (int it = 0; it < iters; ++it) {
+                const int i = sub + (it << sh);
+                const int slot = mt.x + (i < mt.y ? i : 0);
+                const float4 *tp = L.tris + slot * 3 + oi * PAIR_PAD;
+                const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
+                asm volatile("" ::"v"(p0.w), "v"(p1.w), "v"(p2.w)); // keep the loads ds_read_b128 (b96 is half rate)
+                float t, u, v;
+                const bool ok = tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), pr, tb, t, u, v);
+                if (ok && i < mt.y) {
+                    tb = t;
+                    bi = i;
+                }
             }
         }
         if (valid && bi >= 0) {
@@ -578,15 +602,26 @@ PT_DEV bool any_hit_pairs(const KParams &K, const PairLds &L, int lane, bool ali
             tm = tm * dirScale;
         bool found = false;
         const int iters = (K.pair_max_leaf + (1 << sh) - 1) >> sh;
-        for (int it = 0; it < iters; ++it) {
-            const int i = sub + (it << sh);
-            const int slot = mt.x + (i < mt.y ? i : 0);
-            const float4 *tp = L.tris + slot * 3 + oi * PAIR_PAD;
-            const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
-            asm volatile("" ::"v"(p0.w), "v"(p1.w), "v"(p2.w)); // keep the loads ds_read_b128 (b96 is half rate)
-            float t, u, v;
-            const bool ok = tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), pr, tm, t, u, v);
-            found |= ok && (i < mt.y);
+        if (pm1_full_batch(K, sh)) { // (as in closest_hit_pairs)
+            const float4 *tp = L.tris + (mt.x + sub) * 3 + oi * PAIR_PAD;
+            const int step = 3 << sh;
+            for (int it = 0; it < iters; ++it, tp += step) {
+                const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
+                asm volatile("" ::"v"(p0.w), "v"(p1.w), "v"(p2.w)); // keep the loads ds_read_b128 (b96 is half rate)
+                float t, u, v;
+                found |= tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), pr, tm, t, u, v);
+            }
+        } else {
+            for (int it = 0; it < iters; ++it) {
+                const int i = sub + (it << sh);
+                const int slot = mt.x + (i < mt.y ? i : 0);
+                const float4 *tp = L.tris + slot * 3 + oi * PAIR_PAD;
+                const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
+                asm volatile("" ::"v"(p0.w), "v"(p1.w), "v"(p2.w)); // keep the loads ds_read_b128 (b96 is half rate)
+                float t, u, v;
+                const bool ok = tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), pr, tm, t, u, v);
+                found |= ok && (i < mt.y);
+            }
         }
         if (valid && found)
             L.occ[r] = 1u;

@@ -863,6 +863,9 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
     for (const int2 &lf : R.leaves)
         if (lf.y > c->pair_max_leaf)
             c->pair_max_leaf = lf.y;
+    c->pair_leaf_uniform = c->pair_max_leaf > 0;
+    for (const int2 &lf : R.leaves)
+        c->pair_leaf_uniform = c->pair_leaf_uniform && lf.y == c->pair_max_leaf;
     if (int rc = upload_instance_pretests(c, meshes, mesh_count))
         return rc;
     c->have_geometry = true;

@@ -132,6 +132,7 @@ struct ptrt_ctx {
     bool tlas_single_leaf = false, all_single_leaf = false, mats_full = false;
     int stack_entries = 1;
     int pair_meshes = 0, pair_tri_slots = 0, pair_max_leaf = 0;
+    bool pair_leaf_uniform = false; // every leaf has exactly pair_max_leaf triangles
     int tlas_max_leaf = 0, tlas_depth = 0;
     bool have_geometry = false, have_materials = false;
 
@@ -192,6 +193,8 @@ struct ptrt_ctx {
     int sample_sync_eff = 0;         // ... the last frame
     int pm1_dense_roots = -1;        // option "pm1_dense_roots": -1 (default) where it pays, 0 never, 1 always (ptrt_render)
     int pm1_dense_roots_eff = 0;     // ... the last frame (0 as well when another traversal mode rendered it)
+    int pm1_full_leaf = -1;          // option "pm1_full_leaf": -1 (default) and 1: on when the leaves are uniform, 0 never (make_params)
+    int pm1_full_leaf_eff = 0;       // ... the last frame (0 as well when another traversal mode rendered it)
     int tile_run = 8;                // option "tile_run": of every 8 * run consecutive tiles XCD x renders a run of neighbours (path_trace_kernel); 0: tile k on workgroup k
     int ticket_tiles = 1;            // option "ticket_tiles": consecutive tiles per ticket of the queue
     int persist = 0, n_cus = 0;      // option "persist": persistent waves per CU (0 = the variant's occupancy)
@@ -407,6 +410,7 @@ pt::KParams make_params(ptrt_ctx *c) {
     K.tlas_depth = c->tlas_depth < 1 ? 1 : c->tlas_depth;
     K.tlas_any_rounds = (c->n_meshes > 1024 || c->tlas_rounds) ? 1 : 0; // (TLAS indices beyond 10 bits do not fit a 16-bit pair entry)
     K.pair_split = (c->pair_split && !c->any_transform) ? 1 : 0;
+    K.pm1_full_leaf = (c->pm1_full_leaf != 0 && c->pair_leaf_uniform) ? 1 : 0;
     K.fetch_min = c->fetch_min > 0 ? c->fetch_min : 64; // 0 = refill only when the whole wave is idle: batches of 64
     K.pair_cap = merged_pair_cap(c);
     K.n_nodes = c->n_nodes;
@@ -1683,6 +1687,7 @@ int ptrt_render(ptrt_ctx *c, int frame_index, int spp, int max_depth, void *out_
     // scene alone.
     K.pm1_dense = (pmode == 1 && (c->pm1_dense_roots >= 0 ? c->pm1_dense_roots : (c->pair_meshes >= 4 ? 1 : 0))) ? 1 : 0;
     c->pm1_dense_roots_eff = K.pm1_dense;
+    c->pm1_full_leaf_eff = pmode == 1 ? K.pm1_full_leaf : 0;
     // (round 2: the merged loop was at its best WITHOUT shadow-ray subtree stealing, 3.98 vs 4.17 ms on the showcase frame -- its
     // yields served ten shadow pairs at the price of sixty closest-hit walks; with the closest-hit walks stolen from as well the
     // yields pay for both kinds: 3.19 ms with, 3.49 without)

@@ -63,6 +63,7 @@ const Option OPTIONS[] = {
     {"persist", &ptrt_ctx::persist, OPT_CLAMP, 0, INT_MAX},
     {"sample_sync", &ptrt_ctx::sample_sync, OPT_TRISTATE},
     {"pm1_dense_roots", &ptrt_ctx::pm1_dense_roots, OPT_TRISTATE}, // PMODE 1: root-box tests of a half-empty wave dealt over all lanes
+    {"pm1_full_leaf", &ptrt_ctx::pm1_full_leaf, OPT_TRISTATE}, // PMODE 1: triangle loops without partial-leaf handling when every leaf is full (0: never)
     {"tile_run", &ptrt_ctx::tile_run, OPT_REJECT, 0, 64}, // 0 (tile k on workgroup k) or the tiles per XCD and run, 1..64
     {"ticket_tiles", &ptrt_ctx::ticket_tiles, OPT_CLAMP, 1, 16},
     {"refill", &ptrt_ctx::refill, OPT_CLAMP, 0, 2},
@@ -84,6 +85,7 @@ const Option OPTIONS[] = {
     // read-only facts about the last ptrt_render (so that a measurement can say what ran)
     {"sample_sync_eff", &ptrt_ctx::sample_sync_eff, OPT_READ_ONLY},
     {"pm1_dense_roots_eff", &ptrt_ctx::pm1_dense_roots_eff, OPT_READ_ONLY},
+    {"pm1_full_leaf_eff", &ptrt_ctx::pm1_full_leaf_eff, OPT_READ_ONLY},
     {"refilled", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->refill_eff ? 1 : 0; }},
     {"split_eff", &ptrt_ctx::split_eff, OPT_READ_ONLY},
     {"pipelined", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->pipelined_last ? 1 : 0; }},
@@ -209,6 +211,14 @@ int ptrt_debug_rcp_check(ptrt_ctx *c, unsigned int *out9) {
     if (!ctx_live(c) || !out9)
         return fail(c, PTRT_E_INVALID, "ptrt_debug_rcp_check: bad argument");
     return run_check(c, out9, [c](unsigned int *d) { hipLaunchKernelGGL(pt::rcp_check_kernel, dim3(4096), dim3(256), 0, c->stream, d); });
+}
+
+// test hook: exhaustive rcp_ieee_above check over the inputs of its contract (|y| >= 2^-60, infinities and NaN included);
+// out9 as above
+int ptrt_debug_rcp_above_check(ptrt_ctx *c, unsigned int *out9) {
+    if (!ctx_live(c) || !out9)
+        return fail(c, PTRT_E_INVALID, "ptrt_debug_rcp_above_check: bad argument");
+    return run_check(c, out9, [c](unsigned int *d) { hipLaunchKernelGGL(pt::rcp_above_check_kernel, dim3(4096), dim3(256), 0, c->stream, d); });
 }
 
 // test hook: exhaustive sqrt_ieee check; out9[0] = mismatches, out9[1] = mismatches of the bare core in its range, out9[2..8] = inputs
