@@ -73,7 +73,7 @@ PT_DEV void winner_uv(const KParams &K, Hit &h, f3 o, f3 d) {
     tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), r, T_FAR, t, h.u, h.v);
 }
 
-// LDS bytes: PMODE 0 the lanes' stacks (GEOM > 0), else pair_lds_bytes of the host (ptrt_capi.hip), which this carve fits.
+// LDS bytes: PMODE 0 the lanes' stacks (GEOM > 0), else pair_lds_bytes of the host (ptrt_render.hip.h), which this carve fits.
 template <int GEOM, int PMODE, int KIND>
 __global__ __launch_bounds__(64) void ray_query_kernel(const KParams K, const float *__restrict__ origins,
                                                        const float *__restrict__ dirs, const float *__restrict__ tmax,

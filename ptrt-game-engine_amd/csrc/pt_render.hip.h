@@ -116,7 +116,7 @@ PT_DEV PairLds carve_pair_lds(void *base, int tri_slots, int meshes, int stack_e
 // PMODE 1 (every BLAS one leaf, the scene's triangles in LDS).  A workgroup of WG waves = WG neighbouring tiles shares ONE copy
 // of what is read-only -- triangle packets, mesh table, mesh heads, jitter table, light and material records -- and each
 // wave has its own lists behind it: the rays' minima / flags, the pair list, the lanes' blue-noise values, the ray totals.
-// Layout (host: pm1_layout in ptrt_capi.hip): [tris + pads | meshtab | meshbox] [lds_extra: jit | lights | mats]
+// Layout (host: pm1_layout in ptrt_render.hip.h): [tris + pads | meshtab | meshbox] [lds_extra: jit | lights | mats]
 // [lds_wave + wave * lds_wave_bytes: best 512 | pairs 128 * meshes | bn 512 (if staged) | count 16].
 // PMODE 1, per wave: the minima (512 B) and the pair list behind them are scratch of the traversal phases [B] / [D]; the
 // lane-refill kernel parks a finished pixel's six generator words there across [R] (6 x 256 B), so the list is never
