@@ -50,6 +50,8 @@ lib.oracle_taa_jitter.argtypes = [C.c_int, _fp]
 lib.oracle_detmath.argtypes = [C.c_int, _fp, _fp, C.c_int, _fp]
 lib.oracle_eval_bsdf.argtypes = [C.c_void_p, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp]
 lib.oracle_scatter.argtypes = [C.c_void_p, C.c_int, _fp, _fp, C.c_int, _up, _fp]
+lib.oracle_eval_bsdf_n.argtypes = [C.c_void_p, C.c_int, _fp, _fp]
+lib.oracle_scatter_n.argtypes = [C.c_void_p, C.c_int, _fp, _fp]
 
 HIT_DTYPE = np.dtype([("hit", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3),
                       ("mesh_index", "<i4"), ("front_face", "<i4"), ("u", "<f4"), ("v", "<f4"),
@@ -87,6 +89,23 @@ def xorwow_draw(state6, n, uniform=False):
         out = np.zeros(n, dtype=np.uint32)
         lib.oracle_xorwow_draw(_u(st), n, _u(out), None)
     return out, st
+
+
+def eval_bsdf_n(mats, items):
+    """evaluateBSDF and material_pdf over (n, 11) items {material, N, V, L, front_face} -> (n, 4) {f, pdf}."""
+    x = np.ascontiguousarray(items, dtype=np.float32)
+    out = np.zeros((x.shape[0], 4), np.float32)
+    lib.oracle_eval_bsdf_n(mats, x.shape[0], _f(x), _f(out))
+    return out
+
+
+def scatter_n(mats, items):
+    """material_scatter over (n, 14) items {material, N, ray_dir, front_face, state} -> (n, 14) {direction, attenuation,
+    out_pdf, flags (1 ok | 2 specular), state after}."""
+    x = np.ascontiguousarray(items, dtype=np.float32)
+    out = np.zeros((x.shape[0], 14), np.float32)
+    lib.oracle_scatter_n(mats, x.shape[0], _f(x), _f(out))
+    return out
 
 
 def render(scene_desc_ptr, width, height, spp, max_depth, frame_count, blue_noise, rng, tile_y0=0, tile_rows=0,

@@ -1738,4 +1738,27 @@ void oracle_scatter(const ptrt_materials *mats, int mat_id, const float *N, cons
         state6[1 + k] = s.v[k];
 }
 
+/* the two hooks above over many items, in the layout of the device probe (ptrt_debug_shade):
+ * eval item = {material id, N(3), V(3), L(3), front_face} -> {f(3), pdf};
+ * scatter item = {material id, N(3), ray_dir(3), front_face, state (6 words)} ->
+ *                {dir(3), attenuation(3), out_pdf, flags, state after (6 words)} */
+void oracle_eval_bsdf_n(const ptrt_materials *mats, int n, const float *items11, float *out4) {
+    for (int i = 0; i < n; ++i) {
+        const float *p = items11 + (size_t)i * 11;
+        oracle_eval_bsdf(mats, (int)p[0], p + 1, p + 4, p + 7, p[10] != 0.0f, out4 + (size_t)i * 4,
+                         out4 + (size_t)i * 4 + 3);
+    }
+}
+
+void oracle_scatter_n(const ptrt_materials *mats, int n, const float *items14, float *out14) {
+    for (int i = 0; i < n; ++i) {
+        const float *p = items14 + (size_t)i * 14;
+        float *o = out14 + (size_t)i * 14;
+        uint32_t st[6];
+        memcpy(st, p + 8, sizeof st);
+        oracle_scatter(mats, (int)p[0], p + 1, p + 4, p[7] != 0.0f, st, o);
+        memcpy(o + 8, st, sizeof st);
+    }
+}
+
 } // extern "C"
