@@ -640,6 +640,14 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         on when the leaves are uniform, decided on the host at upload; 0: never.  The batched ray queries
  *                         share the loops.  ptrt_get_option "pm1_full_leaf_eff" says what the last frame did (0 as well when
  *                         the leaves differ or another traversal mode rendered it).
+ *   pm1_lane_groups -1|0|1   PMODE 1 with pm1_full_leaf in effect: the last, partial batch of a trace's pair list (n < 64 pairs)
+ *                         gives every pair g lanes with g a DIVISOR of the leaf size -- 1, 2, 3, 4, 6 or 12 for cubes, where the
+ *                         2^sh rule had 1, 2, 4 and, in the guarded loop, 8 -- and may run as several sub-batches (40 pairs: 32
+ *                         at 2 lanes and 8 at 6, 6 + 2 test iterations for 12), by a plan the host makes at upload from the leaf
+ *                         size (ptrt_pm1_plan).  The same (ray, triangle) tests and merges: same bits.  -1
+ *                         (default) and 1: on when pm1_full_leaf is; 0: the 2^sh rule.  Closest-hit traces of a scene with an
+ *                         instanced mesh keep one lane per pair.  The batched ray queries share the loops.  ptrt_get_option
+ *                         "pm1_lane_groups_eff" says what the last frame or ray query did.
  *   tile_run 0..64        the one-tile-per-workgroup kernels' workgroup -> tile map.  Consecutive workgroups go to the eight XCDs in
  *                         turn; with n > 0, of every 8 n consecutive tiles XCD x renders tiles [x n, (x + 1) n) -- neighbours,
  *                         whose rays walk the same part of the trees, share an L2 -- instead of every eighth tile.  8 (default):
@@ -670,6 +678,18 @@ int ptrt_set_option(ptrt_ctx *ctx, const char *name, long long value);
  * merged = -1 is still sampling), launches.  ABI 5.  Also read-only (ABI 6): query_pmode, the traversal of the last
  * ptrt_query_rays / ptrt_trace_rays (-1 none yet), and stream, the hipStream_t the context enqueues on. */
 int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
+
+/* The plan behind option "pm1_lane_groups" for leaves of `leaf_triangles` triangles, as ptrt_upload_geometry builds it; needs
+ * no device and no context.  For a tail of n = 1 .. 63 pairs, element n - 1 of out_g63 / out_take63 holds the first
+ * sub-batch: g lanes per pair (a divisor of the leaf size; 0: this tail keeps the 2^sh rule's single batch, which then takes
+ * all n) and the pairs it takes, min(n, 64 / g); the rest of the tail follows its own entry.  Optional (may be NULL): out_mul63,
+ * the constant m with lane / g == (lane * m) >> 12 for lanes 0 .. 63; out_cost63, the whole tail's cost in the model's
+ * wave-instructions; out_model2, the model {one test, one sub-batch header}.  Returns 1, 0 when the leaf size is outside the
+ * plan's range (every tail keeps the 2^sh rule), -1 for a bad argument.  ptrt_pm1_div_mul: that m for g = 1 .. 64 (0
+ * outside).  ABI 6, additions only. */
+int ptrt_pm1_plan(int leaf_triangles, int32_t *out_g63, int32_t *out_take63, int32_t *out_mul63, int32_t *out_cost63,
+                  int32_t *out_model2);
+int ptrt_pm1_div_mul(int g);
 
 /* Render on a caller-owned HIP stream (a `hipStream_t` passed as void*; NULL returns to the
  * context's own stream).  Lets a host that already orders work on a stream (a GL-interop map,

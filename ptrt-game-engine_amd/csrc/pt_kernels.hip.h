@@ -41,6 +41,7 @@
 //      reference's 24-entry stack-overflow drop can never trigger.
 #pragma once
 #include "pt_device.hip.h"
+#include "pm1_plan.h"
 
 namespace pt {
 
@@ -81,6 +82,8 @@ struct KParams {
     int pair_split;     // PMODE 1: a batch that does not fill the wave may give each pair several lanes
     int pm1_full_leaf;  // PMODE 1: every staged leaf has exactly pair_max_leaf triangles: the triangle loops skip the partial-leaf handling
     int pm1_dense;      // PMODE 1: a call with at most 32 live rays deals its root-box tests over all lanes (build_pairs_dense)
+    int pm1_groups;     // PMODE 1: a tail of n < 64 pairs runs as the sub-batches of pm1_plan (only with pm1_full_leaf)
+    Pm1Plan pm1_plan;   // ... by n: lanes per pair and pairs of the first sub-batch (pm1_plan.h); read with scalar loads, n is wave-uniform
     int steal;          // PMODE 2 any-hit: 0 off; n > 0: idle lanes steal subtrees, node loop yields every n steps
     int csteal;         // PMODE 2 closest hit: 0 off; n > 0: verified subtree stealing (run_closest_queue), node loop yields every n steps
     int csteal_min;     // ... node steps a walk must have taken before its stack may be stolen from

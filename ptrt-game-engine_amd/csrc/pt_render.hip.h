@@ -184,6 +184,7 @@ PT_DEV PairLds carve_pair_lds_wg(void *base, int wave, int meshes, int stack_ent
 // triangle lane-tests, outer iterations; [16] persistent-loop iterations, [17] live lanes in them.
 __device__ unsigned long long g_trav_bounce[64]; // the traversal counters [0..15] once more, split by the rays' bounce: [bounce 0..3][16]
 __device__ unsigned long long g_trav_rhist[8]; // build_pairs calls by live rays (TS_RHIST)
+__device__ unsigned long long g_trav_pm1[2 * 68]; // PMODE 1 triangle loops, closest then any-hit (TS_PM1_*): wave-iterations, batches, calls, calls without pairs, [4 + n] calls by their tail n = P mod 64 (P > 0)
 __device__ unsigned long long g_trav_stats[32]; // [0..7] closest, [8..15] any-hit, [16..17] loop, [18..23] lanes per phase (TS_LANES), [24..31] cycles (CycleAcc)
 // -DPT_MARKS: "; MARK x" comments in the ISA at the phase boundaries of path_trace_kernel (tools/asm_phases.py counts the
 // instructions between them)
@@ -251,6 +252,21 @@ struct CycleAcc {
         if (lane == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))                                                   \
             atomicAdd(&g_trav_rhist[((any) ? 4 : 0) + (ts_r == 0 ? 0 : ts_r <= 16 ? 1 : ts_r <= 32 ? 2 : 3)], 1ull);       \
     } while (0)
+// the triangle loops of closest_hit_pairs / any_hit_pairs: a call by its pair count, a batch by its iterations
+#define TS_PM1_CALL(any, P)                                                                                              \
+    do {                                                                                                                 \
+        if (lane == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) {                                                 \
+            atomicAdd(&g_trav_pm1[((any) ? 68 : 0) + 2], 1ull);                                                          \
+            atomicAdd(&g_trav_pm1[((any) ? 68 : 0) + ((P) > 0 ? 4 + ((P) & 63) : 3)], 1ull);                             \
+        }                                                                                                                \
+    } while (0)
+#define TS_PM1_BATCH(any, iters)                                                                                         \
+    do {                                                                                                                 \
+        if (lane == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) {                                                 \
+            atomicAdd(&g_trav_pm1[((any) ? 68 : 0)], (unsigned long long)(iters));                                       \
+            atomicAdd(&g_trav_pm1[((any) ? 68 : 0) + 1], 1ull);                                                          \
+        }                                                                                                                \
+    } while (0)
 #define TS_NOW() __builtin_readcyclecounter()
 #define TS_ADD(slot, t) (cyc.c[(slot) - 8] += __builtin_readcyclecounter() - (t))
 #define TS_ADDL(slot, t) (L.cyc->c[(slot) - 8] += __builtin_readcyclecounter() - (t))
@@ -279,6 +295,8 @@ struct CycleAcc {
 };
 #define TS_LANES(slot, cond)
 #define TS_RHIST(any, cond)
+#define TS_PM1_CALL(any, P)
+#define TS_PM1_BATCH(any, iters)
 #define TS_NOW() 0ull
 #define TS_ADD(slot, t) (void)(t)
 #define TS_ADDL(slot, t) (void)(t)
@@ -468,22 +486,58 @@ template <int GEN = 0> PT_DEV void pair_ray_from(const KParams &K, const int4 mt
 // do not divide that count has a tail behind the leaf's end and keeps the guarded loop (12 triangles: never -- sh <= 2).
 PT_DEV bool pm1_full_batch(const KParams &K, int sh) { return K.pm1_full_leaf && (K.pair_max_leaf & ((1 << sh) - 1)) == 0; }
 
+// One batch of the triangle loops: its first `take` pairs of the n <= 64 that are left get g lanes each; lane l serves pair q
+// = l / g and tests triangles sub = l mod g, sub + g, ...: `iters` iterations, of the full-leaf loop if `full`.  Wave-uniform
+// but q and sub.  `split` = 0: one lane per pair (closest hit with instanced meshes).
+//   Option "pm1_lane_groups" (K.pm1_groups): g, take and the iterations of a tail n < 64 come from the host's
+// plan (pm1_plan.h) -- g any divisor of the leaf size, the tail cut into sub-batches where that saves iterations (40 pairs of
+// 12 triangles: 32 at 2 lanes and 8 at 6, 6 + 2 iterations for 12) -- read by scalar loads from the kernel arguments; l / g is a
+// multiply and a shift by the entry's constant.  A lane keeps one pair for the whole sub-batch and the loop bodies are the
+// same: the same (ray, triangle) tests, merged by the same 64-bit min / flag, so the same bits as the 2^sh rule's.
+//   Otherwise, and where the plan says so (g = 0), the present rule: 2^sh lanes per pair, n << sh <= 64, 2^sh <= the largest leaf.
+struct PairBatch {
+    int g, take, iters, q, sub;
+    bool full;
+};
+PT_DEV PairBatch pair_batch(const KParams &K, int lane, int n, bool split) {
+    PairBatch B;
+    const Pm1Entry e = (K.pm1_groups && split) ? K.pm1_plan.e[n & 63] : Pm1Entry{0u, 0u};
+    if (e.w & 0xffu) {
+        B.g = (int)(e.w & 0xffu);
+        B.take = (int)((e.w >> 8) & 0xffu);
+        B.iters = (int)(e.w >> 16);
+        B.q = (int)(((uint32_t)lane * e.m) >> PM1_DIV_SHIFT);
+        B.sub = lane - B.q * B.g;
+        B.full = true;
+        return B;
+    }
+    int sh = 0;
+    while (split && (n << (sh + 1)) <= 64 && (2 << sh) <= K.pair_max_leaf)
+        ++sh;
+    B.g = 1 << sh;
+    B.take = n;
+    B.iters = (K.pair_max_leaf + (1 << sh) - 1) >> sh;
+    B.q = lane >> sh;
+    B.sub = lane & ((1 << sh) - 1);
+    B.full = pm1_full_batch(K, sh);
+    return B;
+}
+
 template <bool DENSE = false>
 PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool alive, f3 o, f3 d, int &order) {
     const int P = build_pairs<false, DENSE>(K, L, lane, alive, o, d, T_FAR);
     wave_sync();
-    for (int c = 0; c < P; c += 64) {
+    TS_PM1_CALL(false, P);
+    for (int c = 0, take = 64; c < P; c += take) {
         // a batch that does not fill the wave (the last one) gives every pair 2^sh lanes, each testing every
         // 2^sh-th triangle: 18 left-over pairs cost 6 iterations instead of 12.  The lanes of a pair merge
         // like the pairs of a ray: 64-bit min on {t, mesh order, triangle} = first minimum in leaf order.
         const int n = (P - c) < 64 ? (P - c) : 64;
-        int sh = 0;
         // (not with instanced meshes: their key carries t / dirScale, and two local distances that round to
         // the same world distance must resolve by LOCAL distance first, as one lane's running minimum does)
-        while (K.pair_split && (n << (sh + 1)) <= 64 && (2 << sh) <= K.pair_max_leaf)
-            ++sh;
-        const int p = c + (lane >> sh), sub = lane & ((1 << sh) - 1);
-        const bool valid = (lane >> sh) < n;
+        const PairBatch B = pair_batch(K, lane, n, K.pair_split != 0);
+        const int p = c + B.q, sub = B.sub;
+        const bool valid = B.q < B.take;
         const uint32_t e = ((const uint16_t *)L.pairs)[valid ? p : 0];
         const int r = (int)(e & 63u), oi = (int)(e >> 6);
         const int4 mt = L.meshtab[oi];
@@ -499,13 +553,15 @@ PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool 
         int bi = -1;
         // (software-pipelining these LDS reads one packet ahead was measured: 2.82 vs 2.75 ms -- with four
         // waves per SIMD the latency is already covered and the extra live registers cost more)
-        const int iters = (K.pair_max_leaf + (1 << sh) - 1) >> sh;
-        if (pm1_full_batch(K, sh)) {
+        const int iters = B.iters;
+        take = B.take;
+        TS_PM1_BATCH(false, iters);
+        if (B.full) {
             // every staged leaf holds pair_max_leaf triangles and 2^sh divides that: no test lies behind the end of a leaf,
             // so the count compare, the clamped slot and the address arithmetic go -- one pointer per pair, one step per
             // test.  The same tests in the same order as the loop below: same bits.
             const float4 *tp = L.tris + (mt.x + sub) * 3 + oi * PAIR_PAD;
-            const int step = 3 << sh;
+            const int step = 3 * B.g;
             int bit = -1;
             for (int it = 0; it < iters; ++it, tp += step) {
                 const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
@@ -516,10 +572,10 @@ PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool 
                     bit = it;
                 }
             }
-            bi = bit < 0 ? -1 : sub + (bit << sh);
+            bi = bit < 0 ? -1 : sub + bit * B.g;
         } else {
             for (int it = 0; it < iters; ++it) {
-                const int i = sub + (it << sh);
+                const int i = sub + it * B.g;
                 const int slot = mt.x + (i < mt.y ? i : 0);
                 const float4 *tp = L.tris + slot * 3 + oi * PAIR_PAD;
                 const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
@@ -579,13 +635,12 @@ PT_DEV bool any_hit_pairs(const KParams &K, const PairLds &L, int lane, bool ali
     tmaxv[DENSE ? lane_here(lane) : lane] = tMax;
     const int P = build_pairs<true, DENSE>(K, L, lane, alive, o, d, tMax);
     wave_sync();
-    for (int c = 0; c < P; c += 64) {
-        const int n = (P - c) < 64 ? (P - c) : 64; // 2^sh lanes per pair in a batch that does not fill the wave
-        int sh = 0;
-        while ((n << (sh + 1)) <= 64 && (2 << sh) <= K.pair_max_leaf)
-            ++sh;
-        const int p = c + (lane >> sh), sub = lane & ((1 << sh) - 1);
-        const bool valid = (lane >> sh) < n;
+    TS_PM1_CALL(true, P);
+    for (int c = 0, take = 64; c < P; c += take) {
+        const int n = (P - c) < 64 ? (P - c) : 64; // several lanes per pair in a batch that does not fill the wave
+        const PairBatch B = pair_batch(K, lane, n, true);
+        const int p = c + B.q, sub = B.sub;
+        const bool valid = B.q < B.take;
         const uint32_t e = ((const uint16_t *)L.pairs)[valid ? p : 0];
         const int r = (int)(e & 63u), oi = (int)(e >> 6);
         const int4 mt = L.meshtab[oi];
@@ -601,10 +656,12 @@ PT_DEV bool any_hit_pairs(const KParams &K, const PairLds &L, int lane, bool ali
         if (mt.z & 1)
             tm = tm * dirScale;
         bool found = false;
-        const int iters = (K.pair_max_leaf + (1 << sh) - 1) >> sh;
-        if (pm1_full_batch(K, sh)) { // (as in closest_hit_pairs)
+        const int iters = B.iters;
+        take = B.take;
+        TS_PM1_BATCH(true, iters);
+        if (B.full) { // (as in closest_hit_pairs)
             const float4 *tp = L.tris + (mt.x + sub) * 3 + oi * PAIR_PAD;
-            const int step = 3 << sh;
+            const int step = 3 * B.g;
             for (int it = 0; it < iters; ++it, tp += step) {
                 const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
                 asm volatile("" ::"v"(p0.w), "v"(p1.w), "v"(p2.w)); // keep the loads ds_read_b128 (b96 is half rate)
@@ -613,7 +670,7 @@ PT_DEV bool any_hit_pairs(const KParams &K, const PairLds &L, int lane, bool ali
             }
         } else {
             for (int it = 0; it < iters; ++it) {
-                const int i = sub + (it << sh);
+                const int i = sub + it * B.g;
                 const int slot = mt.x + (i < mt.y ? i : 0);
                 const float4 *tp = L.tris + slot * 3 + oi * PAIR_PAD;
                 const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];

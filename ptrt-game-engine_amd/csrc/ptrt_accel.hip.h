@@ -866,6 +866,7 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
     c->pair_leaf_uniform = c->pair_max_leaf > 0;
     for (const int2 &lf : R.leaves)
         c->pair_leaf_uniform = c->pair_leaf_uniform && lf.y == c->pair_max_leaf;
+    c->pm1_plan_ok = c->pair_leaf_uniform && pt::pm1_build_plan(c->pair_max_leaf, &c->pm1_plan);
     if (int rc = upload_instance_pretests(c, meshes, mesh_count))
         return rc;
     c->have_geometry = true;

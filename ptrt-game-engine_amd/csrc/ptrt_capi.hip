@@ -133,6 +133,8 @@ struct ptrt_ctx {
     int stack_entries = 1;
     int pair_meshes = 0, pair_tri_slots = 0, pair_max_leaf = 0;
     bool pair_leaf_uniform = false; // every leaf has exactly pair_max_leaf triangles
+    pt::Pm1Plan pm1_plan{};         // ... then: the sub-batches of a pair-list tail (pm1_plan.h), built at upload
+    bool pm1_plan_ok = false;
     int tlas_max_leaf = 0, tlas_depth = 0;
     bool have_geometry = false, have_materials = false;
 
@@ -195,6 +197,8 @@ struct ptrt_ctx {
     int pm1_dense_roots_eff = 0;     // ... the last frame (0 as well when another traversal mode rendered it)
     int pm1_full_leaf = -1;          // option "pm1_full_leaf": -1 (default) and 1: on when the leaves are uniform, 0 never (make_params)
     int pm1_full_leaf_eff = 0;       // ... the last frame (0 as well when another traversal mode rendered it)
+    int pm1_lane_groups = -1;        // option "pm1_lane_groups": -1 (default) and 1: on where pm1_full_leaf is in effect, 0 the 2^sh rule (make_params)
+    int pm1_lane_groups_eff = 0;     // ... the last frame or ray query (0 as well when another traversal mode ran it)
     int tile_run = 8;                // option "tile_run": of every 8 * run consecutive tiles XCD x renders a run of neighbours (path_trace_kernel); 0: tile k on workgroup k
     int ticket_tiles = 1;            // option "ticket_tiles": consecutive tiles per ticket of the queue
     int persist = 0, n_cus = 0;      // option "persist": persistent waves per CU (0 = the variant's occupancy)
@@ -402,6 +406,9 @@ pt::KParams make_params(ptrt_ctx *c) {
     K.tlas_any_rounds = (c->n_meshes > 1024 || c->tlas_rounds) ? 1 : 0; // (TLAS indices beyond 10 bits do not fit a 16-bit pair entry)
     K.pair_split = (c->pair_split && !c->any_transform) ? 1 : 0;
     K.pm1_full_leaf = (c->pm1_full_leaf != 0 && c->pair_leaf_uniform) ? 1 : 0;
+    K.pm1_groups = (c->pm1_lane_groups != 0 && K.pm1_full_leaf && c->pm1_plan_ok) ? 1 : 0;
+    if (K.pm1_groups)
+        K.pm1_plan = c->pm1_plan;
     K.fetch_min = c->fetch_min > 0 ? c->fetch_min : 64; // 0 = refill only when the whole wave is idle: batches of 64
     K.pair_cap = merged_pair_cap(c);
     K.n_nodes = c->n_nodes;
@@ -1100,6 +1107,7 @@ int launch_query(ptrt_ctx *c, int kind, const float *o, const float *d, const fl
     const int geom = pick_geom(c);
     const int pmode = pair_mode(c, geom, false);
     c->query_pmode = pmode;
+    c->pm1_lane_groups_eff = pmode == 1 ? K.pm1_groups : 0;
     const size_t lds = trace_lds_bytes(c, geom, pmode);
     if (pmode == 3)
         if (int rc = refresh_tlas_heads(c, false))

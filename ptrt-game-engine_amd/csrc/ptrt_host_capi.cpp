@@ -6,6 +6,7 @@
 #include "../host/ptrt/serialize.hpp"
 #include "../host/ptrt/farm.hpp"
 #include "../host/ptrt/view.hpp"
+#include "pm1_plan.h"
 
 #include <chrono>
 #include <cstring>
@@ -66,6 +67,30 @@ int mesh_index(Scene *s, Mesh *m) {
 extern "C" {
 
 const char *hs_last_error(void) { return g_err.c_str(); }
+
+// include/ptrt.h: the PMODE 1 lane-group plan as the device library builds it at upload (pm1_plan.h), without a device
+int ptrt_pm1_plan(int leaf_triangles, int32_t *out_g63, int32_t *out_take63, int32_t *out_mul63, int32_t *out_cost63,
+                  int32_t *out_model2) {
+    if (leaf_triangles < 1 || !out_g63 || !out_take63)
+        return -1;
+    pt::Pm1Plan plan;
+    int cost[64];
+    const bool ok = pt::pm1_build_plan(leaf_triangles, &plan, cost);
+    for (int n = 1; n < 64; ++n) {
+        out_g63[n - 1] = (int32_t)(plan.e[n].w & 0xffu);
+        out_take63[n - 1] = (int32_t)((plan.e[n].w >> 8) & 0xffu);
+        if (out_mul63)
+            out_mul63[n - 1] = (int32_t)plan.e[n].m;
+        if (out_cost63)
+            out_cost63[n - 1] = cost[n];
+    }
+    if (out_model2) {
+        out_model2[0] = pt::PM1_BODY;
+        out_model2[1] = pt::PM1_HEADER;
+    }
+    return ok ? 1 : 0;
+}
+int ptrt_pm1_div_mul(int g) { return (g >= 1 && g <= 64 && pt::pm1_div_exact(g)) ? (int)pt::pm1_div_mul(g) : 0; }
 
 void hs_material_default(float *out27) { to_floats(Material(), out27); }
 // Material(albedo, roughness, metallic) constructor (material_lib.cuh:91-104)

@@ -64,6 +64,7 @@ const Option OPTIONS[] = {
     {"sample_sync", &ptrt_ctx::sample_sync, OPT_TRISTATE},
     {"pm1_dense_roots", &ptrt_ctx::pm1_dense_roots, OPT_TRISTATE}, // PMODE 1: root-box tests of a half-empty wave dealt over all lanes
     {"pm1_full_leaf", &ptrt_ctx::pm1_full_leaf, OPT_TRISTATE}, // PMODE 1: triangle loops without partial-leaf handling when every leaf is full (0: never)
+    {"pm1_lane_groups", &ptrt_ctx::pm1_lane_groups, OPT_TRISTATE}, // PMODE 1: a pair-list tail's lanes per pair from the leaf's divisors, by the upload's plan (0: the 2^sh rule)
     {"tile_run", &ptrt_ctx::tile_run, OPT_REJECT, 0, 64}, // 0 (tile k on workgroup k) or the tiles per XCD and run, 1..64
     {"ticket_tiles", &ptrt_ctx::ticket_tiles, OPT_CLAMP, 1, 16},
     {"refill", &ptrt_ctx::refill, OPT_CLAMP, 0, 2},
@@ -86,6 +87,7 @@ const Option OPTIONS[] = {
     {"sample_sync_eff", &ptrt_ctx::sample_sync_eff, OPT_READ_ONLY},
     {"pm1_dense_roots_eff", &ptrt_ctx::pm1_dense_roots_eff, OPT_READ_ONLY},
     {"pm1_full_leaf_eff", &ptrt_ctx::pm1_full_leaf_eff, OPT_READ_ONLY},
+    {"pm1_lane_groups_eff", &ptrt_ctx::pm1_lane_groups_eff, OPT_READ_ONLY}, // ... of the last frame or ray query, whichever came last
     {"refilled", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->refill_eff ? 1 : 0; }},
     {"split_eff", &ptrt_ctx::split_eff, OPT_READ_ONLY},
     {"pipelined", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->pipelined_last ? 1 : 0; }},
@@ -192,6 +194,17 @@ int ptrt_debug_trav_rhist(ptrt_ctx *c, unsigned long long *out8) {
     HIP_TRY(c, hipMemcpyFromSymbol(out8, HIP_SYMBOL(pt::g_trav_rhist), 8 * sizeof(unsigned long long)));
     unsigned long long zero[8] = {};
     HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(pt::g_trav_rhist), zero, sizeof(zero)));
+    return PTRT_OK;
+}
+
+// ... and pt::g_trav_pm1 (136 words: the PMODE 1 triangle loops' iterations, batches and tail histogram, TS_PM1_*)
+int ptrt_debug_trav_pm1(ptrt_ctx *c, unsigned long long *out136) {
+    if (!ctx_live(c) || !out136)
+        return fail(c, PTRT_E_INVALID, "ptrt_debug_trav_pm1: bad argument");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyFromSymbol(out136, HIP_SYMBOL(pt::g_trav_pm1), 136 * sizeof(unsigned long long)));
+    unsigned long long zero[136] = {};
+    HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(pt::g_trav_pm1), zero, sizeof(zero)));
     return PTRT_OK;
 }
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Lane-occupancy statistics of the PMODE 2 traversals (library built with -DPT_TRAV_STATS):
+"""Lane-occupancy statistics of the PMODE 2 traversals and PMODE 1's triangle loops (library built with -DPT_TRAV_STATS):
    PTRT_AMD_LIB=ptrt-game-engine_amd/build/variants/libptrt_stats.so python tools/trav_stats.py [scene] [W H spp]"""
 import ctypes as C
 import os
@@ -69,6 +69,70 @@ if hasattr(P.lib, "ptrt_debug_trav_rhist"):  # root-test calls by the rays they 
             print(f"{name} root-test calls {n} by live rays R: " + ", ".join(
                 f"{lab} {100.0 * rh[o + k] / n:.1f} %" for k, lab in enumerate(("0", "1-16", "17-32", "33-64"))) +
                 f"  (dense roots: {s.get_option('pm1_dense_roots_eff')})")
+if hasattr(P.lib, "ptrt_debug_trav_pm1") and s.get_option("pmode") == 1:
+    # PMODE 1 triangle loops (TS_PM1_*): wave-iterations, batches and the tails n = P mod 64 of the pair lists, and from the
+    # tails what the 2^sh rule and the lane-group plan (ptrt_pm1_plan) each make of this frame: tests, and tests with every
+    # batch header charged at H tests
+    pm = (C.c_ulonglong * 136)()
+    P.lib.ptrt_debug_trav_pm1.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    assert P.lib.ptrt_debug_trav_pm1(s.ctx, pm) == 0
+    d = s.flatten().contents
+    leaf = {d.meshes[i].face_count for i in range(d.mesh_count) if d.meshes[i].node_count == 1}
+    groups = s.get_option("pm1_lane_groups_eff")
+    print(f"PMODE 1 triangle loops (pm1_lane_groups_eff {groups}, pm1_full_leaf_eff {s.get_option('pm1_full_leaf_eff')}):")
+    L = leaf.pop() if len(leaf) == 1 and all(d.meshes[i].node_count == 1 for i in range(d.mesh_count)) else 0
+    if L:
+        g63, t63, c63 = ((C.c_int32 * 63)() for _ in range(3))
+        model = (C.c_int32 * 2)()
+        P.lib.ptrt_pm1_plan.argtypes = [C.c_int] + [C.POINTER(C.c_int32)] * 5
+        assert P.lib.ptrt_pm1_plan(L, g63, t63, None, c63, model) == 1
+        H = model[1] / model[0]
+
+        def present(n):  # (iterations, batches) of the 2^sh rule
+            sh = 0
+            while (n << (sh + 1)) <= 64 and (2 << sh) <= L:
+                sh += 1
+            return (L + (1 << sh) - 1) >> sh, 1
+
+        def planned(n):
+            it = b = 0
+            while n:
+                if g63[n - 1] == 0:
+                    return it + present(n)[0], b + 1
+                it, b, n = it + L // g63[n - 1], b + 1, n - t63[n - 1]
+            return it, b
+    tot = {}
+    for name, o in (("closest", 0), ("any-hit", 68)):
+        iters, batches, calls, empty = pm[o:o + 4]
+        hist = list(pm[o + 4:o + 68])
+        if not calls:
+            continue
+        print(f"   {name}: calls {calls} ({100.0 * empty / calls:.1f} % without a pair), batches {batches}, triangle-loop wave-iterations "
+              f"{iters} ({iters / calls:.2f} per call)")
+        with_tail = sum(hist[1:])
+        bands = ((1, 5), (6, 10), (11, 16), (17, 21), (22, 32), (33, 53), (54, 63))
+        print("      tail n = P mod 64, share of the calls with pairs: 0: "
+              f"{100.0 * hist[0] / max(1, calls - empty):.1f} %, " +
+              ", ".join(f"{a}-{b}: {100.0 * sum(hist[a:b + 1]) / max(1, calls - empty):.1f} %" for a, b in bands))
+        print("      tail histogram n=1..63: " + " ".join(str(h) for h in hist[1:]))
+        if L and (name == "any-hit" or not any(d.meshes[i].has_transform for i in range(d.mesh_count))):
+            rule = planned if groups else present
+            full = batches - sum(hist[n] * rule(n)[1] for n in range(1, 64))
+            check = full * L + sum(hist[n] * rule(n)[0] for n in range(1, 64))
+            row = {}
+            for label, fn in (("2^sh rule", present), ("plan", planned)):
+                tests = full * L + sum(hist[n] * fn(n)[0] for n in range(1, 64))
+                heads = full + sum(hist[n] * fn(n)[1] for n in range(1, 64))
+                row[label] = (tests, tests + H * heads)
+                tot[label] = tuple(a + b for a, b in zip(tot.get(label, (0, 0)), row[label]))
+            print(f"      full batches {full}, calls with a tail {with_tail}; counted {iters} against {check} from the histogram")
+            print(f"      from the histogram (L = {L}, H = {H:.2f}): 2^sh rule {row['2^sh rule'][0]} tests, {row['2^sh rule'][1]:.0f} with headers; "
+                  f"plan {row['plan'][0]} ({100.0 * (row['plan'][0] / row['2^sh rule'][0] - 1):+.1f} %), "
+                  f"{row['plan'][1]:.0f} with headers ({100.0 * (row['plan'][1] / row['2^sh rule'][1] - 1):+.1f} %)")
+    if len(tot) == 2:
+        a, b = tot["2^sh rule"], tot["plan"]
+        print(f"   both loops: {a[0]} -> {b[0]} wave-tests ({100.0 * (b[0] / a[0] - 1):+.1f} %), with headers {a[1]:.0f} -> {b[1]:.0f} "
+              f"({100.0 * (b[1] / a[1] - 1):+.1f} %)")
 if hasattr(P.lib, "ptrt_debug_trav_dbg"):
     import struct
     dbg = (C.c_ulonglong * 1033)()
