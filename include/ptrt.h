@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
+#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
 
 enum {
     PTRT_OK = 0,
@@ -331,7 +331,26 @@ int ptrt_read_prim_order(ptrt_ctx *ctx, int mesh_index, int32_t *prim_indices_ou
  * PTRT_E_INVALID unless count is the uploaded index count.
  *
  * ptrt_read_tlas: synchronises; the uploaded nodes' left / right / start / count with the boxes the device holds now
- * (the counterpart of ptrt_read_prim_order).  PTRT_E_INVALID unless node_count is the uploaded node count. */
+ * (the counterpart of ptrt_read_prim_order).  PTRT_E_INVALID unless node_count is the uploaded node count.
+ *
+ * ptrt_set_instance_poses_device: what the reference keeps per mesh -- Transform3D::position, rotation (Euler radians) and
+ * scale, nine floats -- from DEVICE memory ordered on the context's stream; one launch derives the has_transform bit and the
+ * world / inverse / normal rows of meshes [first_mesh, first_mesh + count) from them and writes them into the mesh records
+ * (flag bit 1, the materials', and the root boxes are kept).  No copy, no staging, no allocation, no synchronisation,
+ * use_graphs 0 and 1; follow with ONE ptrt_refit_tlas or ptrt_reorder_tlas.  The arithmetic is the reference's host code
+ * operation by operation (Transform3D::updateMatrices, transform.cuh:260-306; mat4::operator* with its typo and
+ * mat4::inverse with its identity below |det| 1e-10, mat4.cuh:211-323; the has_transform rule of scene.cuh:718-721, which
+ * looks at scale.x only): every product and sum rounded separately in the written order, 1 / det and the square roots
+ * correctly rounded, sine and cosine the library's own deterministic ones (not a libm's).  A NaN or an infinity propagates as
+ * that arithmetic propagates it.  The context's host copy lags as after ptrt_set_instance_transforms_device.  Ranges and
+ * refusals as there, and PTRT_E_INVALID (nothing enqueued) unless d_pose is count * 36 bytes of device memory on the
+ * context's device: the kernel follows the pointer.
+ *
+ * ptrt_read_instance_transforms: synchronises; the has_transform bit (0 or 1) and matrices of meshes [first_mesh, first_mesh
+ * + count) as the device's mesh records hold them now: rows 0-2 of world, inverse and normal in floats 0-11 (a normal row's
+ * fourth word is 0: the records do not keep it), floats 12-15 are 0 0 0 1.  The records may be handed unchanged to
+ * ptrt_set_instance_transforms of another context, which reads only those nine rows.  PTRT_E_INVALID for a range outside the
+ * uploaded meshes, a negative count or NULL. */
 typedef struct ptrt_instance_xform {
     float world[16], inverse[16], normal[16]; /* as in ptrt_mesh_desc */
     int32_t has_transform;
@@ -342,6 +361,11 @@ int ptrt_refit_tlas(ptrt_ctx *ctx);
 int ptrt_read_tlas(ptrt_ctx *ctx, ptrt_bvh_node *nodes_out, int node_count);
 int ptrt_reorder_tlas(ptrt_ctx *ctx);
 int ptrt_read_tlas_order(ptrt_ctx *ctx, int32_t *mesh_indices_out, int count);
+typedef struct ptrt_instance_pose {
+    ptrt_vec3 position, rotation, scale; /* Transform3D's state, 36 B */
+} ptrt_instance_pose;
+int ptrt_set_instance_poses_device(ptrt_ctx *ctx, int first_mesh, int count, const ptrt_instance_pose *d_pose);
+int ptrt_read_instance_transforms(ptrt_ctx *ctx, int first_mesh, int count, ptrt_instance_xform *out);
 
 /* The `Triangles` path of updatePTScene with a CHANGING triangle count (PTRTtransfer.cuh:2204-2385:
  * a new triangle list every frame, e.g. a fluid surface).  For a triangle-soup mesh (face i =

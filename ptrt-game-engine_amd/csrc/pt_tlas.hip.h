@@ -5,7 +5,8 @@
 // scene.cuh:458-594); it has no refit.  Here the child pairs, leaf ranges and mesh indices of the upload
 // stay, and everything that depends on boxes and matrices is derived again on the context's stream:
 //   1. scatter_xforms_kernel  the flag bit and nine matrix rows of the meshes a caller moved, from staging
-//                             into the mesh records (root boxes untouched)
+//                             into the mesh records (root boxes untouched); or compose_poses_kernel, which derives
+//                             them on the device from the nine floats of the reference's Transform3D (below)
 //   2. refit_tlas_kernel      ONE workgroup, barriers between its phases:
 //        a. per TLAS index: the mesh's world box (Transform3D::transformAABB, transform.cuh:399-416, the
 //           arithmetic of tlas_root_box) into scratch, and the instance's first-pass box
@@ -65,6 +66,138 @@ __global__ void scatter_xforms_kernel(const float *__restrict__ xf, XformLayout 
         const int b = (k - 1) / 12, j = (k - 1) - b * 12; // matrix b (inverse, world, normal), float j of its first three rows
         const int off = b == 0 ? L.inverse : (b == 1 ? L.world : L.normal);
         rec[8 + k - 1] = (b == 2 && (j & 3) == 3) ? 0.0f : src[off + j]; // (a normal row's fourth word is 0 in the records)
+    }
+}
+
+// ---- poses -> mesh records (ptrt_set_instance_poses_device) ----------------------------------------------------------------
+// The reference keeps nine floats per mesh -- Transform3D::position, rotation (Euler radians), scale -- and derives the three
+// matrices and the has_transform bit from them on the HOST (Transform3D::updateMatrices, transform.cuh:260-306; the descriptor
+// loop, scene.cuh:718-721).  compose_poses_kernel is that derivation, one instance per thread, with this arithmetic contract:
+//   * every product and sum is a rounded multiply followed by a rounded add, in the order the reference's expressions are
+//     written: nothing is fused (no fma_ here, unlike dot and cross; the translation unit is built with -ffp-contract=off);
+//   * sinf / cosf of the three angles are det_sincos, the project's one sine and cosine (dm_sincos of oracle/detmath.h bit
+//     for bit): whichever libm the reference's caller links is not reproducible;
+//   * the rotation matrix as transform.cuh:270-288; world = rot * diag(scale) through mat4::operator* (mat4.cuh:280-323) with
+//     its typo in r.m[3] (b.m[11] where b.m[1] belongs).  With these operands the typo only ever multiplies zeros, but the
+//     zero terms are added (they decide the sign of a zero and carry a NaN), so the four-term sums stay; then position goes
+//     into m[3], m[7], m[11];
+//   * inverse = mat4::inverse (mat4.cuh:211-262): the eighteen 2x2 determinants, det, the identity when fabsf(det) < 1e-10f,
+//     otherwise invDet = 1.0f / det correctly rounded (rcp_ieee) and every entry invDet * (+-(...)), negations as written;
+//   * normal = the inverse's transpose (the records keep its 3x3 part);
+//   * has_transform = position.length() > 0.001f || rotation.length() > 0.001f || fabsf(scale.x - 1.0f) > 0.001f with
+//     length = sqrtf(x*x + y*y + z*z), left to right, the root correctly rounded (sqrt_ieee).  Only scale.x is looked at:
+//     a mesh scaled in y alone at the origin is NOT an instance, as in the reference;
+//   * a NaN or an infinity in a pose propagates as that arithmetic propagates it: no special case but the determinant test.
+// Only rows 0-2 of each matrix reach the records, so what feeds row 3 alone is not computed.
+// Mapping: a thread composes one instance into LDS (37 words, an odd stride: no bank conflicts), then the workgroup copies
+// its instances' 37-word runs -- flags word and nine rows are contiguous in a record -- with consecutive lanes on consecutive
+// words: a thread storing its own record would put every lane of a store on another cache line.  Bit 1 of the flags word
+// belongs to the materials and is kept; the root box is not touched.
+constexpr int POSE_F = 9;         // floats per pose: position, rotation, scale
+constexpr int POSE_BLOCK = 256;   // instances (= threads) per workgroup
+constexpr int POSE_OUT = 37;      // words per instance: the flags word and the nine rows (floats 7 .. 43 of a mesh record)
+
+struct PoseMat4 {
+    float m[16];
+};
+// mat4::operator* as the reference writes it (column-major product; r.m[3] takes b.m[11] for b.m[1])
+__device__ __forceinline__ PoseMat4 pose_mul(const PoseMat4 &a, const PoseMat4 &b) {
+    PoseMat4 r;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float b1 = (c == 0 && k == 3) ? b.m[11] : b.m[c * 4 + 1];
+            r.m[c * 4 + k] = a.m[k] * b.m[c * 4] + a.m[4 + k] * b1 + a.m[8 + k] * b.m[c * 4 + 2] + a.m[12 + k] * b.m[c * 4 + 3];
+        }
+    return r;
+}
+__device__ __forceinline__ float pose_length(float x, float y, float z) { return sqrt_ieee(x * x + y * y + z * z); }
+
+__global__ __launch_bounds__(POSE_BLOCK) void compose_poses_kernel(const float *__restrict__ poses, float4 *mesh_recs, int first,
+                                                                   int count) {
+    __shared__ float out[POSE_BLOCK * POSE_OUT];
+    const int base = blockIdx.x * POSE_BLOCK, t = threadIdx.x;
+    const int here = min(POSE_BLOCK, count - base); // instances of this workgroup (the grid covers `count`: here >= 1)
+    if (t < here) {
+        const float *p = poses + (size_t)(base + t) * POSE_F;
+        const float px = p[0], py = p[1], pz = p[2], rx = p[3], ry = p[4], rz = p[5], scx = p[6], scy = p[7], scz = p[8];
+        float sx, cx, sy, cy, sz, cz;
+        det_sincos(rx, sx, cx);
+        det_sincos(ry, sy, cy);
+        det_sincos(rz, sz, cz);
+        PoseMat4 rot, w;
+        rot.m[0] = cy * cz;
+        rot.m[1] = cz * sx * sy - cx * sz;
+        rot.m[2] = cx * cz * sy + sx * sz;
+        rot.m[3] = 0.0f;
+        rot.m[4] = cy * sz;
+        rot.m[5] = cx * cz + sx * sy * sz;
+        rot.m[6] = cx * sy * sz - cz * sx;
+        rot.m[7] = 0.0f;
+        rot.m[8] = -sy;
+        rot.m[9] = cy * sx;
+        rot.m[10] = cx * cy;
+        rot.m[11] = 0.0f;
+        rot.m[12] = rot.m[13] = rot.m[14] = 0.0f;
+        rot.m[15] = 1.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            w.m[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+        w.m[0] = scx;
+        w.m[5] = scy;
+        w.m[10] = scz;
+        w = pose_mul(rot, w);
+        w.m[3] = px;
+        w.m[7] = py;
+        w.m[11] = pz;
+        const float *m = w.m;
+        const float A2323 = m[10] * m[15] - m[11] * m[14], A1323 = m[9] * m[15] - m[11] * m[13];
+        const float A1223 = m[9] * m[14] - m[10] * m[13], A0323 = m[8] * m[15] - m[11] * m[12];
+        const float A0223 = m[8] * m[14] - m[10] * m[12], A0123 = m[8] * m[13] - m[9] * m[12];
+        const float A2313 = m[6] * m[15] - m[7] * m[14], A1313 = m[5] * m[15] - m[7] * m[13];
+        const float A1213 = m[5] * m[14] - m[6] * m[13], A0313 = m[4] * m[15] - m[7] * m[12];
+        const float A0113 = m[4] * m[13] - m[5] * m[12]; // (A0213 and A0212 feed row 3 of the inverse alone)
+        const float A2312 = m[6] * m[11] - m[7] * m[10], A1312 = m[5] * m[11] - m[7] * m[9];
+        const float A1212 = m[5] * m[10] - m[6] * m[9], A0312 = m[4] * m[11] - m[7] * m[8];
+        const float A0112 = m[4] * m[9] - m[5] * m[8];
+        const float det = m[0] * (m[5] * A2323 - m[6] * A1323 + m[7] * A1223) - m[1] * (m[4] * A2323 - m[6] * A0323 + m[7] * A0223) +
+                          m[2] * (m[4] * A1323 - m[5] * A0323 + m[7] * A0123) - m[3] * (m[4] * A1223 - m[5] * A0223 + m[6] * A0123);
+        float inv[12] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f}; // (rows 0-2 of the identity)
+        if (!(__builtin_fabsf(det) < 1e-10f)) {
+            const float invDet = rcp_ieee(det);
+            inv[0] = invDet * (m[5] * A2323 - m[6] * A1323 + m[7] * A1223);
+            inv[1] = invDet * -(m[1] * A2323 - m[2] * A1323 + m[3] * A1223);
+            inv[2] = invDet * (m[1] * A2313 - m[2] * A1313 + m[3] * A1213);
+            inv[3] = invDet * -(m[1] * A2312 - m[2] * A1312 + m[3] * A1212);
+            inv[4] = invDet * -(m[4] * A2323 - m[6] * A0323 + m[7] * A0223);
+            inv[5] = invDet * (m[0] * A2323 - m[2] * A0323 + m[3] * A0223);
+            inv[6] = invDet * -(m[0] * A2313 - m[2] * A0313 + m[3] * A0113);
+            inv[7] = invDet * (m[0] * A2312 - m[2] * A0312 + m[3] * A0112);
+            inv[8] = invDet * (m[4] * A1323 - m[5] * A0323 + m[7] * A0123);
+            inv[9] = invDet * -(m[0] * A1323 - m[1] * A0323 + m[3] * A0123);
+            inv[10] = invDet * (m[0] * A1313 - m[1] * A0313 + m[3] * A0113);
+            inv[11] = invDet * -(m[0] * A1312 - m[1] * A0312 + m[3] * A0112);
+        }
+        const bool has = pose_length(px, py, pz) > 0.001f || pose_length(rx, ry, rz) > 0.001f || __builtin_fabsf(scx - 1.0f) > 0.001f;
+        float *o = out + t * POSE_OUT;
+        o[0] = __int_as_float(has ? 1 : 0);
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+            o[1 + j] = inv[j];
+            o[13 + j] = m[j];
+            o[25 + j] = (j & 3) == 3 ? 0.0f : inv[(j & 3) * 4 + (j >> 2)]; // (a normal row's fourth word is 0 in the records)
+        }
+    }
+    __syncthreads();
+    float *dst = reinterpret_cast<float *>(mesh_recs + (size_t)(first + base) * MESH_REC_F4) + 7;
+    for (int i = t; i < here * POSE_OUT; i += POSE_BLOCK) {
+        const int r = i / POSE_OUT, k = i - r * POSE_OUT; // word k of this workgroup's instance r
+        float *word = dst + (size_t)r * (MESH_REC_F4 * 4) + k;
+        float v = out[i];
+        if (k == 0)
+            v = __int_as_float((__float_as_int(*word) & ~1) | __float_as_int(v)); // (bit 1 belongs to the materials)
+        *word = v;
     }
 }
 

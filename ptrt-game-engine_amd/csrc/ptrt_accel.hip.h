@@ -1,5 +1,5 @@
 // ptrt_accel.hip.h -- the acceleration-structure half of the C ABI: the caller's reference-shaped meshes and TLAS re-laid-out
-// and uploaded (ptrt_upload_geometry, ptrt_update_instances), instances moved (ptrt_set_instance_transforms*, ptrt_refit_tlas,
+// and uploaded (ptrt_upload_geometry, ptrt_update_instances), instances moved (ptrt_set_instance_transforms*, ptrt_set_instance_poses_device, ptrt_refit_tlas,
 // ptrt_reorder_tlas), meshes moved (ptrt_update_vertices, ptrt_update_triangles, ptrt_refit, ptrt_build_bvh) and the read-backs.
 // Included by ptrt_capi.hip behind struct ptrt_ctx and the helpers every entry point shares (fail, HIP_TRY, upload, ctx_live,
 // set_device); the state only this file touches is in ptrt_accel_state.hip.h.  Nothing here is on the frame path.
@@ -1011,6 +1011,67 @@ int ptrt_set_instance_transforms_device(ptrt_ctx *c, int first_mesh, int count, 
     hipLaunchKernelGGL(pt::scatter_xforms_kernel, dim3((count * 37 + 255) / 256), dim3(256), 0, c->stream,
                        reinterpret_cast<const float *>(d_xf), abi, c->d_mesh_recs, first_mesh, count);
     HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+// Poses (Transform3D's nine floats) from DEVICE memory: one launch derives the has_transform bit and the nine matrix rows as the
+// reference's host code would (pt::compose_poses_kernel) and writes them into the mesh records.  Host bookkeeping as above.
+// The kernel follows d_pose for count * 36 bytes, so memory that is not the device's is refused here, before the launch.
+int ptrt_set_instance_poses_device(ptrt_ctx *c, int first_mesh, int count, const ptrt_instance_pose *d_pose) {
+    static_assert(sizeof(ptrt_instance_pose) == pt::POSE_F * sizeof(float) && offsetof(ptrt_instance_pose, rotation) == 12 &&
+                      offsetof(ptrt_instance_pose, scale) == 24,
+                  "ptrt_instance_pose is read as nine floats: position, rotation, scale");
+    if (int rc = enter_geometry(c, "ptrt_set_instance_poses_device"))
+        return rc;
+    if (!d_pose || count < 0 || first_mesh < 0 || first_mesh > c->n_meshes || count > c->n_meshes - first_mesh)
+        return fail(c, PTRT_E_INVALID, "ptrt_set_instance_poses_device: meshes [%d, %d + %d) of %d%s", first_mesh, first_mesh, count,
+                    c->n_meshes, d_pose ? "" : ", NULL poses");
+    if (count == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const size_t bytes = (size_t)count * sizeof(ptrt_instance_pose);
+    if (!device_span(c, d_pose, bytes))
+        return fail(c, PTRT_E_INVALID, "ptrt_set_instance_poses_device: poses are not %zu bytes of device memory on device %d", bytes,
+                    c->device);
+    c->xf_host_stale = true;
+    c->any_transform = true;
+    c->inst_pre_ok = false; // the first-pass boxes follow with the next ptrt_refit_tlas / ptrt_reorder_tlas
+    hipLaunchKernelGGL(pt::compose_poses_kernel, dim3((count + pt::POSE_BLOCK - 1) / pt::POSE_BLOCK), dim3(pt::POSE_BLOCK), 0, c->stream,
+                       reinterpret_cast<const float *>(d_pose), c->d_mesh_recs, first_mesh, count);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+// What the device's mesh records hold now, as records ptrt_set_instance_transforms takes: rows 0-2 of each matrix (a normal
+// row's fourth word is 0: the records do not keep it), row 3 = 0 0 0 1.
+int ptrt_read_instance_transforms(ptrt_ctx *c, int first_mesh, int count, ptrt_instance_xform *out) {
+    if (int rc = enter_geometry(c, "ptrt_read_instance_transforms"))
+        return rc;
+    if (!out || count < 0 || first_mesh < 0 || first_mesh > c->n_meshes || count > c->n_meshes - first_mesh)
+        return fail(c, PTRT_E_INVALID, "ptrt_read_instance_transforms: meshes [%d, %d + %d) of %d%s", first_mesh, first_mesh, count,
+                    c->n_meshes, out ? "" : ", NULL output");
+    if (count == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    std::vector<float4> dev((size_t)count * pt::MESH_REC_F4);
+    HIP_TRY(c, hipMemcpyAsync(dev.data(), c->d_mesh_recs + (size_t)first_mesh * pt::MESH_REC_F4, dev.size() * sizeof(float4),
+                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < count; ++i) {
+        const float4 *rec = &dev[(size_t)i * pt::MESH_REC_F4];
+        ptrt_instance_xform &X = out[i];
+        std::memcpy(X.inverse, &rec[2], 3 * sizeof(float4));
+        std::memcpy(X.world, &rec[5], 3 * sizeof(float4));
+        std::memcpy(X.normal, &rec[8], 3 * sizeof(float4));
+        X.normal[3] = X.normal[7] = X.normal[11] = 0.0f;
+        for (float *m : {X.world, X.inverse, X.normal}) {
+            m[12] = m[13] = m[14] = 0.0f;
+            m[15] = 1.0f;
+        }
+        X.has_transform = (rec_flags(rec) & REC_INSTANCE) ? 1 : 0;
+    }
     return PTRT_OK;
 }
 

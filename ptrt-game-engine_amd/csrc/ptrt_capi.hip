@@ -488,6 +488,25 @@ void free_post(ptrt_ctx *c) {
     c->bloom_on = 0;
 }
 
+// `bytes` of device memory at p, all inside one allocation on the context's device
+bool device_span(ptrt_ctx *c, const void *p, size_t bytes) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError(); // (memory HIP has never seen: an error it would report again later)
+        return false;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != c->device)
+        return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const size_t off = (size_t)((const char *)p - (const char *)base);
+    return off <= size && bytes <= size - off;
+}
+
 } // namespace
 
 #include "ptrt_present.hip.h"
@@ -1114,25 +1133,6 @@ int launch_query(ptrt_ctx *c, int kind, const float *o, const float *d, const fl
             return rc;
     return kind == PTRT_QUERY_CLOSEST ? dispatch_query<pt::QUERY_CLOSEST>(c, geom, pmode, K, lds, o, d, tmax, n, out)
                                       : dispatch_query<pt::QUERY_OCCLUDED>(c, geom, pmode, K, lds, o, d, tmax, n, out);
-}
-
-// `bytes` of device memory at p, all inside one allocation on the context's device
-bool device_span(ptrt_ctx *c, const void *p, size_t bytes) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError(); // (memory HIP has never seen: an error it would report again later)
-        return false;
-    }
-    if (a.type != hipMemoryTypeDevice || a.device != c->device)
-        return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    const size_t off = (size_t)((const char *)p - (const char *)base);
-    return off <= size && bytes <= size - off;
 }
 
 extern "C" {

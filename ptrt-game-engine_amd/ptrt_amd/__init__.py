@@ -69,6 +69,10 @@ class InstanceXform(C.Structure):
                 ("has_transform", C.c_int32)]
 
 
+class InstancePose(C.Structure):
+    _fields_ = [("position", Vec3), ("rotation", Vec3), ("scale", Vec3)]
+
+
 class Light(C.Structure):
     _fields_ = [("type", C.c_int32), ("position", Vec3), ("direction", Vec3), ("color", Vec3),
                 ("intensity", C.c_float), ("range", C.c_float), ("inner_cone", C.c_float),
@@ -120,6 +124,8 @@ assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
+INSTANCE_XFORM_DTYPE = np.dtype([("world", "<f4", 16), ("inverse", "<f4", 16), ("normal", "<f4", 16), ("has_transform", "<i4")])
+assert INSTANCE_XFORM_DTYPE.itemsize == C.sizeof(InstanceXform) == 196 and C.sizeof(InstancePose) == 36
 
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -162,6 +168,7 @@ _sig("ptrt_set_stream", C.c_int, _vp, _vp)
 _sig("ptrt_kernel_ms_history", C.c_int, _vp, _fp, C.c_int)
 _sig("ptrt_launch_ms_history", C.c_int, _vp, _fp, _fp, C.c_int)
 _sig("ptrt_debug_detmath", C.c_int, _vp, C.c_int, _fp, _fp, C.c_int, _fp)
+_sig("ptrt_debug_upload_counts", C.c_int, _vp, C.POINTER(C.c_int))
 
 # ---- Scene mirror (csrc/ptrt_host_capi.cpp) ---------------------------------------------
 _sig("hs_last_error", C.c_char_p)
@@ -261,6 +268,8 @@ _sig("ptrt_read_tlas", C.c_int, _vp, C.POINTER(BvhNode), C.c_int)
 _sig("hs_refit_instance_changes", C.c_int, _vp, C.c_int)
 _sig("ptrt_reorder_tlas", C.c_int, _vp)
 _sig("ptrt_read_tlas_order", C.c_int, _vp, C.POINTER(C.c_int32), C.c_int)
+_sig("ptrt_set_instance_poses_device", C.c_int, _vp, C.c_int, C.c_int, _vp)
+_sig("ptrt_read_instance_transforms", C.c_int, _vp, C.c_int, C.c_int, _vp)
 _sig("hs_reseat_tlas", C.c_int, _vp)
 _sig("hs_reorder_tlas", C.c_int, _vp, C.c_int)
 _sig("hs_rebuild_object_changes", C.c_int, _vp, C.c_int)
@@ -574,12 +583,48 @@ class Scene:
         if not tensor.is_contiguous() or tensor.dim() != 2 or tensor.shape[1] * tensor.element_size() != rec:
             raise ValueError(f"set_instance_transforms_device: needs a contiguous (count, {rec} bytes) tensor, got "
                              f"{tuple(tensor.shape)} of {tensor.dtype}")
+        self._order_behind_torch(tensor)
+        self._cchk(lib.ptrt_set_instance_transforms_device(self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr())))
+
+    def _order_behind_torch(self, tensor):
+        """the context's stream waits for what torch's current stream holds now"""
         import torch
         cur = torch.cuda.current_stream(tensor.device)
         ctx_stream = torch.cuda.ExternalStream(self.get_option("stream"), device=tensor.device)
         if ctx_stream.cuda_stream != cur.cuda_stream:
             ctx_stream.wait_stream(cur)
-        self._cchk(lib.ptrt_set_instance_transforms_device(self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr())))
+
+    def set_instance_poses_device(self, first, tensor):
+        """`ptrt_set_instance_poses_device`: meshes first .. first + count - 1 take their has_transform bit and matrices from the
+        poses in `tensor`, a contiguous (count, 9) float32 torch tensor on this scene's device whose rows are `ptrt_instance_pose`
+        records -- position, rotation (Euler radians), scale -- read in place by one launch on the context's stream, which
+        derives the matrices as the reference's Transform3D does: no copy, no synchronisation.  The context's stream is ordered
+        behind torch's current stream.  Follow with ptrt_refit_tlas / ptrt_reorder_tlas."""
+        if not _is_tensor(tensor):
+            raise ValueError("set_instance_poses_device: needs a torch tensor on the scene's device")
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError(f"set_instance_poses_device: tensor on {tensor.device}, this scene renders on cuda:{self.device}")
+        import torch
+        if not tensor.is_contiguous() or tensor.dim() != 2 or tensor.shape[1] != 9 or tensor.dtype != torch.float32:
+            raise ValueError(f"set_instance_poses_device: needs a contiguous (count, 9) float32 tensor, got "
+                             f"{tuple(tensor.shape)} of {tensor.dtype}")
+        self._order_behind_torch(tensor)
+        self._cchk(lib.ptrt_set_instance_poses_device(self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr())))
+
+    def read_instance_transforms(self, first=0, count=None):
+        """The has_transform bits and matrices the device's mesh records hold now (ptrt_read_instance_transforms; synchronises):
+        a structured array with world, inverse and normal as (3, 4) float32 rows and has_transform (0 or 1), for meshes
+        first .. first + count - 1 (count=None: all from `first`)."""
+        if count is None:
+            count = self.flatten().contents.mesh_count - int(first)
+        raw = np.zeros(max(int(count), 0), dtype=INSTANCE_XFORM_DTYPE)
+        self._cchk(lib.ptrt_read_instance_transforms(self.ctx, int(first), int(count), raw.ctypes.data_as(_vp)))
+        out = np.zeros(len(raw), dtype=[("world", "<f4", (3, 4)), ("inverse", "<f4", (3, 4)), ("normal", "<f4", (3, 4)),
+                                        ("has_transform", "<i4")])
+        for k in ("world", "inverse", "normal"):
+            out[k] = raw[k][:, :12].reshape(-1, 3, 4)
+        out["has_transform"] = raw["has_transform"]
+        return out
 
     def read_tlas_order(self):
         """The TLAS index array as the device holds it (ptrt_read_tlas_order; synchronises): int32 mesh indices."""

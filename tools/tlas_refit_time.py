@@ -18,6 +18,14 @@ Also: the PMODE 3 frame time after a vertex refit of one mesh, with the instance
 alone: inst_pre_ok 0) and recomputed on the device (ptrt_refit + ptrt_refit_tlas: inst_pre_ok 1), same frames otherwise.
 
     python3 tools/tlas_refit_time.py --out profiles/tlas_refit_time.json
+
+--poses-device measures this instead, and nothing else: the same k moving instances per frame committed
+  (b) by refitInstanceChanges(), as above: matrices made by the host mirror, staged, scattered;
+  (d) by a pose tensor written on the device (torch, on the context's stream) + set_instance_poses_device +
+      ptrt_refit_tlas: nine floats per mesh of the moved span, matrices derived by the device, no host copy of anything.
+Host microseconds per commit and event-timed frame time, the same windows and medians.
+
+    python3 tools/tlas_refit_time.py --poses-device --out profiles/instance_pose_time.json
 """
 import argparse
 import json
@@ -93,6 +101,73 @@ def measure_moves(a):
         row = {"case": "moved_instances", "meshes": BASE + N_EXTRA, "moved_per_frame": k, "frames_per_window": a.frames,
                "size": [a.width, a.height], "spp": a.spp, "depth": a.depth, "pmode": scenes["refit"].get_option("pmode"),
                "tlas_refits": counts, "library": P.library_info()["sha16"]}
+        for name in scenes:
+            row[f"{name}_host_us"] = summary(res[name]["host_us"])
+            row[f"{name}_frame_ms"] = summary(res[name]["frame_ms"])
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        for s in scenes.values():
+            s.sync()
+            s.close()
+    return rows
+
+
+def home_poses():
+    """(N_EXTRA, 9) float32: the pose of every extra mesh of scenes.many, by replaying its draws; a mesh with baked vertices has
+    the identity pose, which is what its record holds"""
+    rs = np.random.RandomState(3)
+    out = np.tile(np.array([0, 0, 0, 0, 0, 0, 1, 1, 1], np.float32), (N_EXTRA, 1))
+    for k in range(N_EXTRA):
+        rs.uniform(0.2, 0.9, 3), rs.uniform(0.05, 0.8)
+        pos = (rs.uniform(-4, 4), rs.uniform(-4.5, 3.5), rs.uniform(-9, -2))
+        if k % 3 == 0:
+            out[k] = np.concatenate([pos, rs.uniform(-1, 1, 3), rs.uniform(0.2, 0.5, 3)])
+        else:
+            rs.uniform(0.2, 0.5, 3)
+    return out
+
+
+def measure_poses(a):
+    """k moving instances per frame: (b) refitInstanceChanges() against (d) poses written on the device +
+    set_instance_poses_device + ptrt_refit_tlas, alternating window by window in one process"""
+    rows = []
+    for k in (int(x) for x in a.moved.split(",")):
+        k = min(k, (N_EXTRA + 2) // 3)
+        scenes = {"refit": build(a.width, a.height, a.spp, a.depth), "poses": build(a.width, a.height, a.spp, a.depth)}
+        stream = torch.cuda.Stream()
+        out = torch.empty(a.width * a.height * 3, dtype=torch.uint8, device="cuda")
+        for s in scenes.values():
+            s.set_stream(stream.cuda_stream)
+        span = 3 * (k - 1) + 1                                # meshes BASE .. BASE + span - 1 hold the k instances
+        poses = torch.from_numpy(home_poses()[:span]).cuda()
+        moving = poses[::3, 0:3]                              # the instances' positions: a view into the pose tensor
+        j = torch.arange(k, dtype=torch.float32, device="cuda")
+        sp = scenes["poses"]
+        frame = {"f": 0}
+
+        def commit_poses():
+            t = 0.05 * frame["f"]
+            moving[:, 0] = 3.0 * torch.sin(t + j)
+            moving[:, 1] = -1.0 + 2.0 * torch.cos(0.7 * t + j)
+            moving[:, 2] = -5.0 + 2.0 * torch.sin(0.3 * t + 2.0 * j)
+            sp.set_instance_poses_device(BASE, poses)
+            sp._cchk(P.lib.ptrt_refit_tlas(sp.ctx))
+            frame["f"] += 1
+
+        commits = {"refit": scenes["refit"].refitInstanceChanges, "poses": commit_poses}
+        res = {name: {"host_us": [], "frame_ms": []} for name in scenes}
+        with torch.cuda.stream(stream):
+            for w in range(a.windows + 1):  # (window 0 warms both paths up)
+                for name, s in scenes.items():
+                    frame["f"] = w * a.frames
+                    h, ms = run_frames(s, stream, out, a.frames, k if name == "refit" else 0, commits[name], w * a.frames)
+                    if w:
+                        res[name]["host_us"].append(h)
+                        res[name]["frame_ms"].append(ms)
+        row = {"case": "poses_on_the_device", "meshes": BASE + N_EXTRA, "moved_per_frame": k, "posed_span": span,
+               "frames_per_window": a.frames, "size": [a.width, a.height], "spp": a.spp, "depth": a.depth,
+               "pmode": sp.get_option("pmode"), "tlas_refits": {name: s.get_option("tlas_refits") for name, s in scenes.items()},
+               "library": P.library_info()["sha16"]}
         for name in scenes:
             row[f"{name}_host_us"] = summary(res[name]["host_us"])
             row[f"{name}_frame_ms"] = summary(res[name]["frame_ms"])
@@ -207,12 +282,17 @@ def main():
     ap.add_argument("--walk-frames", type=int, default=600, help="frames of the random walk (0: skip it)")
     ap.add_argument("--walk-step", type=float, default=0.05, help="largest step per axis and frame")
     ap.add_argument("--reorder-every", type=int, default=20, help="every k-th frame of the walk takes the path under test")
+    ap.add_argument("--poses-device", action="store_true", help="only: refitInstanceChanges() against poses written on the device")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    rows = measure_moves(a) + (measure_walk(a) if a.walk_frames >= 2 * a.reorder_every else []) + measure_pretest(a)
+    if a.poses_device:
+        rows = measure_poses(a)
+    else:
+        rows = measure_moves(a) + (measure_walk(a) if a.walk_frames >= 2 * a.reorder_every else []) + measure_pretest(a)
     if a.out:
         with open(a.out, "w") as f:
-            json.dump({"command": f"python3 tools/tlas_refit_time.py --moved {a.moved} --frames {a.frames} --windows {a.windows} "
+            json.dump({"command": f"python3 tools/tlas_refit_time.py {'--poses-device ' if a.poses_device else ''}"
+                                  f"--moved {a.moved} --frames {a.frames} --windows {a.windows} "
                                   f"--width {a.width} --height {a.height} --spp {a.spp} --depth {a.depth}",
                        "device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
             f.write("\n")
