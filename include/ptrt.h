@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
+#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms, + ptrt_query_radiance / ptrt_camera_rays / ptrt_init_rng_states (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
 
 enum {
     PTRT_OK = 0,
@@ -149,6 +149,15 @@ typedef struct ptrt_hit {
     int32_t face_index;
     ptrt_vec3 local_point;
 } ptrt_hit;
+
+/* One ray's answer from ptrt_query_radiance: what a frame leaves for a pixel in PTRT_BUF_ACCUM, _DEPTH, _NORMAL and
+ * _OBJECT_ID, in one 32-byte record. */
+typedef struct ptrt_radiance {
+    float radiance[3]; /* mean over the samples: what ACCUM holds for a pixel */
+    float depth;       /* first hit of sample 0, 1e30f on a miss (DEPTH)      */
+    float normal[3];   /* first hit of sample 0, zeros on a miss (NORMAL)     */
+    int32_t object_id; /* first hit of sample 0, -1 on a miss (OBJECT_ID)     */
+} ptrt_radiance;
 
 /* Per-frame counters of the trace stage (Mrays/s numerator). */
 typedef struct ptrt_stats {
@@ -522,6 +531,45 @@ int ptrt_trace_rays(ptrt_ctx *ctx, const float *origins, const float *directions
 int ptrt_query_rays(ptrt_ctx *ctx, int kind, const float *origins, const float *directions, const float *tmax, int n,
                     void *out);
 
+/* Path-traced radiance for caller-supplied rays on DEVICE memory (ABI 6, addition only; no counterpart in the reference,
+ * whose path tracer starts at its own camera).  Per ray i: for s < samples, tracePath(ray i, state i, max_depth)
+ * (path_logic.cuh:782-899) with the same ray each time, each sample soft-clamped as path_trace_kernel clamps it
+ * (scene_kernels.cuh:170), added in order to a sum that starts at zero, the sum divided by (float)samples; depth, normal and
+ * object_id are the first hit of sample 0 (scene_kernels.cuh:179-193).  Fed a pinhole frame's own primary rays
+ * (ptrt_camera_rays) and the generator states that frame started from, the records are that frame's ACCUM, DEPTH, NORMAL and
+ * OBJECT_ID and the states those the frame leaves, bit for bit: past the primary ray tracePath reads nothing of the pixel.
+ * `origins` and `directions` are n*3 floats as for ptrt_query_rays; `rng_states` is n*6 uint32 in the canonical order
+ * {d, v0..v4} of PTRT_BUF_RNG / ptrt_write_rng (ptrt_init_rng_states makes fresh ones), read and written back IN PLACE, so a
+ * later call continues each ray's stream; `out` is n records.  All four pointers must be device memory of the context's
+ * device, each allocation large enough for n rays.  Ordering and side effects are those of ptrt_query_rays: enqueued on the
+ * context's stream with no allocation, copy or synchronisation, behind earlier frames, uploads, refits and instance
+ * updates; later frames are ordered behind it; it touches none of the context's generator states, accumulation, G-buffers,
+ * RGB8 image, ptrt_get_stats counters or timing history.  The traversal is the path tracer's for the scene and options
+ * (reported by ptrt_get_option "query_pmode"), the materials the simple or the full set as a frame would choose.  Sky,
+ * environment map, lights and materials are the context's current ones; the camera plays no part.  Band and interleaved
+ * contexts answer for the whole scene.  PTRT_E_INVALID (nothing enqueued) for n < 0, a NULL pointer, memory that is not the
+ * context's device memory, or samples / max_depth outside 1..32767 (ptrt_render's range); PTRT_E_NOT_READY before
+ * geometry and materials are uploaded (lights are optional, as for a frame); n == 0 returns PTRT_OK and launches nothing. */
+int ptrt_query_radiance(ptrt_ctx *ctx, const float *origins, const float *directions, uint32_t *rng_states, int n,
+                        int samples, int max_depth, ptrt_radiance *out);
+
+/* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
+ * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small
+ * kernel on the context's stream into DEVICE memory: rows*W*3 floats each (render_w*render_h*3 at a reduced render size),
+ * ray yl*W + x, the order of PTRT_BUF_ACCUM.  The frame's own device functions make them.  The starting point of a custom
+ * camera, and what lets ptrt_query_radiance be compared with a frame.  PTRT_E_INVALID for a thin lens (lens_radius > 0:
+ * that ray's lens sample belongs to the pixel's generator stream, not to the camera), a negative frame_index or sample, a
+ * NULL pointer or memory that is not the context's device memory.  (ABI 6, addition only.) */
+int ptrt_camera_rays(ptrt_ctx *ctx, int frame_index, int sample, float *d_origins, float *d_directions);
+
+/* n generator states in the canonical order {d, v0..v4} for subsequences first_subsequence .. first_subsequence + n - 1 of
+ * `seed`, offset 0, written into DEVICE memory (n*6 uint32) by one kernel on the context's stream: curand_init(seed,
+ * subsequence, 0, ..) as ptrt_reset_rng computes it for pixel `subsequence` (init_curand_kernel, scene_kernels.cuh:26-35).
+ * PTRT_E_INVALID for n < 0, NULL, memory that is not the context's device memory, or a last subsequence of 2^40 or more;
+ * n == 0 returns PTRT_OK.  (ABI 6, addition only.) */
+int ptrt_init_rng_states(ptrt_ctx *ctx, unsigned long long seed, unsigned long long first_subsequence, int n,
+                         uint32_t *d_states);
+
 /* The body of Scene::render_to_device_wireframe (scene.cuh:1211-1245): render_kernel_wireframe
  * (scene_kernels.cuh:53-117, wireframeMode true) over the full width x height -- the render size of the path tracer,
  * bloom and the denoiser play no part.  Per pixel: the RNG-free Camera::get_ray(s, t) (camera.cuh:173-199, device branch:
@@ -646,6 +694,8 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         2: wherever PMODE 1 runs; 0: never.  ptrt_get_option "refilled" says what the last frame did.
  *                         ticket_tiles 1..16: consecutive tiles per draw from the queue (1; more only pays where the counter
  *                         itself binds -- 1 spp: 0.61 -> 0.49 ms with 4, still behind the one-tile-per-wave kernel's 0.43).
+ *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance: N one-wave workgroups per CU
+ *                         instead of what the kernel's occupancy holds (tests: a grid smaller than the batch's chunks).
  *   sample_sync -1|0|1    the lanes of a wave start their samples together (1) instead of each as soon as its path has ended (0):
  *                         the wave's lanes then sit at the same bounce, the light-sample phases are skipped by the whole wave at a
  *                         first hit and the primary rays are made once per sample for 64 lanes; lanes wait for the sample's
@@ -700,7 +750,7 @@ int ptrt_set_option(ptrt_ctx *ctx, const char *name, long long value);
  * timed: render_mode (0 megakernel, 1 wavefront stages, 2 asynchronous lanes), pmode (0 lock-step, 1 pairs over LDS-staged
  * triangles, 2 pair queue, 3 TLAS rounds, 4 merged queue), merged_eff (loop shape of that launch), merged_decided (0 while
  * merged = -1 is still sampling), launches.  ABI 5.  Also read-only (ABI 6): query_pmode, the traversal of the last
- * ptrt_query_rays / ptrt_trace_rays (-1 none yet), and stream, the hipStream_t the context enqueues on. */
+ * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance (-1 none yet), and stream, the hipStream_t the context enqueues on. */
 int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
 
 /* The plan behind option "pm1_lane_groups" for leaves of `leaf_triangles` triangles, as ptrt_upload_geometry builds it; needs

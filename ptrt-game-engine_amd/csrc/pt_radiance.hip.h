@@ -1,0 +1,383 @@
+// pt_radiance.hip.h -- radiance_query_kernel: the path tracer asked about rays the caller chooses (ptrt_query_radiance), and
+// the two small kernels that let a caller start where a frame starts: camera_rays_kernel (ptrt_camera_rays) and
+// rng_states_kernel (ptrt_init_rng_states).
+//
+// Ray i with generator state i: for s < samples, tracePath(ray, state, max_depth) (path_logic.cuh:782-899), each sample soft-
+// clamped and added in order to a sum that starts at zero, the sum divided by (float)samples -- what path_trace_kernel
+// (scene_kernels.cuh:122-194) leaves in ACCUM for a pixel -- and the first hit of sample 0 as NORMAL / DEPTH / OBJECT_ID hold it
+// (scene_kernels.cuh:179-193).  Past the primary ray tracePath reads nothing of the pixel -- no blue noise, no frame count -- so a
+// query fed a pinhole frame's own primary rays and generator states reproduces that frame bit for bit, states included
+// (tests/test_radiance_query_gpu.py).
+//
+// The frame is ray_query_kernel's (pt_query.hip.h): a persistent grid of one-wave workgroups, a grid-stride loop over chunks of
+// 64 rays, dead lanes of the tail chunk taking part in the wave's collectives, size_t indices, the same LDS carve and staging,
+// the same traversal by PMODE.  Per chunk the 64 lanes run the path loop in lock step -- closest hit, the shading of tracePath
+// stated operation by operation as phases [C], [C2], [D], [E] of path_trace_kernel and wf_shade_path state it, the light
+// sample's shadow ray, the scatter -- until no lane has a path left, then the next sample.  No lane refill, no staged shading
+// inputs, no counters: a lane whose path has ended idles until the chunk's longest path is done.
+#pragma once
+#include "pt_query.hip.h"
+
+namespace pt {
+
+struct RadianceOut { // == ptrt_radiance (include/ptrt.h)
+    float radiance[3];
+    float depth;
+    float normal[3];
+    int object_id;
+};
+
+// Waves per SIMD the kernel is built for (its register budget: 512 / waves, in steps of 8): the most at which the pair variants
+// keep a lane's whole path state -- ray, throughput, radiance, sum, generator, hit and light sample across the shadow walk -- in
+// registers.  At four (128 VGPRs, path_trace_kernel's budget, which parks part of that state in LDS and recomputes the rest)
+// every variant but PMODE 1 with the simple materials spilled 16 to 112 bytes per lane into scratch; at three none does.
+constexpr int RADIANCE_WAVES = 3;
+template <int GEOM, bool FULL, int PMODE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAVES, 8))) void radiance_query_kernel(
+    const KParams Kin, const float *__restrict__ origins, const float *__restrict__ dirs, uint32_t *__restrict__ rng_states, size_t n,
+    RadianceOut *__restrict__ out) {
+    // The parameters are read where they are used, through the kernarg segment (scalar loads that hit the constant cache), and
+    // each phase of the loop gets its own opaque copy of the pointer, as in path_trace_kernel: held in SGPRs across the loop, the
+    // ~110 dwords of the by-value copy are spilled into VGPR lanes, and from there into scratch.
+    (void)Kin;
+    const kparams_ptr kp0 = (kparams_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    const KParams &K = kparams(kp0); // staging
+    extern __shared__ uint2 lds_raw[];
+    const int lane = threadIdx.x;
+    LdsStack stk{lds_raw + lane};
+    CycleAcc cyc;
+    PairLds PL{};
+    if (PMODE == 1) {
+        // ray_query_kernel's staging: the leaf's triangle packets (PAIR_PAD float4 apart per mesh), mesh table, heads
+        PL = carve_pair_lds((void *)lds_raw, K.pair_tri_slots, K.pair_meshes);
+        const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
+        for (int i = 0; i < K.pair_meshes; ++i) {
+            const int m = K.tlas_mesh_ids[lf.x + i];
+            const int2 leaf = K.leaves[~__float_as_int(K.mesh_recs[m * MESH_REC_F4].w)];
+            for (int k = lane; k < leaf.y * 3; k += 64)
+                PL.tris[leaf.x * 3 + i * PAIR_PAD + k] = K.tris[leaf.x * 3 + k];
+        }
+        for (int i = lane; i < K.pair_meshes; i += 64) {
+            const int m = K.tlas_mesh_ids[lf.x + i];
+            const MeshHead mh = load_mesh_head(K, m);
+            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
+            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
+            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
+            PL.meshbox[2 * i + 1] = hb;
+            const int2 leaf = K.leaves[~mh.root_ref];
+            PL.meshtab[i] = make_int4(leaf.x, leaf.y, mh.flags, m);
+        }
+    } else if (PMODE) {
+        PL = carve_pair_lds((void *)lds_raw, 0, PMODE == 3 ? 0 : K.pair_meshes, K.stack_entries, PMODE == 3 ? K.tlas_max_leaf : 0,
+                            PMODE == 3 ? K.tlas_depth : 0);
+        const int2 lf = PMODE == 3 ? make_int2(0, 0) : K.tlas_leaves[~K.tlas_root_ref];
+        for (int i = lane; PMODE != 3 && i < K.pair_meshes; i += 64) {
+            const int m = K.tlas_mesh_ids[lf.x + i];
+            const MeshHead mh = load_mesh_head(K, m);
+            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
+            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
+            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8));
+            PL.meshbox[2 * i + 1] = hb;
+        }
+    }
+    PL.cyc = &cyc;
+    PL.stat_bounce = 0;
+    __syncthreads();
+    const size_t chunks = (n + 63) / 64;
+    for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (wave-uniform)
+        const size_t i = ch * 64 + (size_t)lane;
+        const bool live = i < n;
+        f3 o0 = mk3(0.0f), d0 = mk3(0.0f);
+        Rng rng = {0, 0, 0, 0, 0, 0};
+        if (live) {
+            o0 = mk3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]);
+            d0 = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
+            const uint32_t *st = rng_states + i * 6; // canonical order {d, v0..v4}
+            rng.d = st[0];
+            rng.v0 = st[1];
+            rng.v1 = st[2];
+            rng.v2 = st[3];
+            rng.v3 = st[4];
+            rng.v4 = st[5];
+        }
+        f3 sum = mk3(0.0f); // avg_color of path_trace_kernel (scene_kernels.cuh:171-176)
+        for (int s = 0; s < kparams(kp0).spp; ++s) { // (wave-uniform)
+            // the sample's own copy of the ray: tracePath starts every sample from the caller's ray
+            f3 ro = o0, rd = d0;
+            bool ray_spec = true, prev_was_specular = true;
+            f3 throughput = mk3(1.0f), acc = mk3(0.0f);
+            int bounce = 0;
+            bool act = live;
+            while (__builtin_amdgcn_ballot_w64(act)) {
+                // ---- [B] closest hit, all lanes that have a path together
+                const KParams &KB = kparams(kp0);
+                int h_order = 0;
+                const Hit h = (PMODE == 1)   ? closest_hit_pairs(KB, PL, lane, act, ro, rd, h_order)
+                              : (PMODE == 2) ? closest_hit_pairs_dyn(KB, PL, lane, act, ro, rd)
+                              : (PMODE == 3) ? closest_hit_pairs_tlas(KB, PL, lane, act, ro, rd, cyc)
+                                             : closest_hit<GEOM>(KB, act, ro, rd, stk);
+                // ---- [C] first half of the shading
+                const KParams &KC = kparams(kp0);
+                bool end_path = false, shaded = false, want_shadow = false;
+                Surface hit;
+                hit.point = hit.normal = mk3(0.0f);
+                hit.t = 0.0f;
+                hit.front_face = true;
+                f3 L = mk3(0.0f), light_scale = mk3(0.0f), shadow_o = mk3(0.0f);
+                float pdf_sample = 1.0f, shadow_tmax = 0.0f, light_att = 1.0f;
+                if (act) {
+                    if (h.mesh < 0) {
+                        if (s == 0 && bounce == 0) { // first hit of the first sample (scene_kernels.cuh:181-193): HitInfo() defaults
+                            RadianceOut *r = out + i;
+                            r->depth = 1e30f;
+                            r->normal[0] = 0.0f;
+                            r->normal[1] = 0.0f;
+                            r->normal[2] = 0.0f;
+                            r->object_id = -1;
+                        }
+                        if (KC.use_sky) { // sampleSky (render_utils.cuh:115-137): gradient, or the equirect map
+                            if (KC.env) {
+                                const float phi = det_atan2(rd.z, rd.x);
+                                const float theta = det_acos(max_(-1.0f, min_(1.0f, rd.y)));
+                                const float u = (phi + PI_F) * (1.0f / TWO_PI_F);
+                                const float v = theta * (1.0f / PI_F);
+                                acc = acc + throughput * tex2d_env(KC.env, KC.env_w, KC.env_h, u, v);
+                            } else {
+                                const float t = 0.5f * (rd.y + 1.0f);
+                                acc = acc + throughput * lerp(KC.sky_bottom, KC.sky_top, t);
+                            }
+                        } else {
+                            acc = acc + throughput * mk3(0.0f);
+                        }
+                        end_path = true;
+                    } else {
+                        shaded = true;
+                        hit = make_surface(KC, h, ro, rd, nullptr, nullptr);
+                        if (s == 0 && bounce == 0) {
+                            RadianceOut *r = out + i;
+                            r->depth = hit.t;
+                            r->normal[0] = hit.normal.x;
+                            r->normal[1] = hit.normal.y;
+                            r->normal[2] = hit.normal.z;
+                            r->object_id = h.mesh;
+                        }
+                        const float4 m0 = KC.materials[h.mesh * 6 + 0], m2 = KC.materials[h.mesh * 6 + 2];
+                        if (!hit.front_face) { // Beer-Lambert on back faces (path_logic.cuh:823-829)
+                            const f3 T_unit = mk3(max_(1e-6f, m0.x), max_(1e-6f, m0.y), max_(1e-6f, m0.z));
+                            const f3 absorption = mk3(-det_log(T_unit.x), -det_log(T_unit.y), -det_log(T_unit.z));
+                            throughput = throughput * beerLambert(absorption, hit.t);
+                        }
+                        if (m2.x > 0.0f || m2.y > 0.0f || m2.z > 0.0f) {
+                            if (bounce == 0 || prev_was_specular)
+                                acc = acc + throughput * mk3(m2.x, m2.y, m2.z);
+                        }
+                        // light sample of next-event estimation (path_logic.cuh:305-382, 840)
+                        if (!ray_spec && KC.n_lights > 0) {
+                            float r = rng_uniform(rng);
+                            r = min_(r, 0.99999994f);
+                            const int light_index = (int)(r * (float)KC.n_lights);
+                            const LightRec light = load_light(KC.lights, light_index);
+                            const float pdf_pick = 1.0f / (float)KC.n_lights;
+                            float attenuation = 1.0f;
+                            float light_dist = 1e30f;
+                            const f3 light_radiance = light.color * light.intensity;
+                            if (light.type == 1) {
+                                L = -light.direction;
+                                pdf_sample = pdf_pick;
+                            } else {
+                                const f3 toLight = light.position - hit.point;
+                                const float light_dist_sq = dot(toLight, toLight);
+                                light_dist = sqrt_ieee(light_dist_sq);
+                                if (light.radius <= 0.0f) {
+                                    L = toLight / light_dist;
+                                    pdf_sample = pdf_pick;
+                                } else {
+                                    float sin_theta_max_sq = (light.radius * light.radius) / light_dist_sq;
+                                    sin_theta_max_sq = min_(sin_theta_max_sq, 0.9999f);
+                                    const float cos_theta_max = sqrt_ieee(1.0f - sin_theta_max_sq);
+                                    L = sample_cone_direction(rng, toLight / light_dist, cos_theta_max);
+                                    const float solid_angle = TWO_PI_F * (1.0f - cos_theta_max);
+                                    pdf_sample = (solid_angle > 1e-6f) ? (pdf_pick / solid_angle) : pdf_pick;
+                                }
+                                attenuation = attenuate(light_dist, light.range);
+                                if (light.type == 2) {
+                                    const float theta = dot(L, -light.direction);
+                                    const float epsilon = light.inner - light.outer;
+                                    float spotIntensity;
+                                    if (epsilon <= 1e-6f)
+                                        spotIntensity = (theta >= light.outer) ? 1.0f : 0.0f;
+                                    else
+                                        spotIntensity = clampf((theta - light.outer) / epsilon, 0.0f, 1.0f);
+                                    attenuation *= spotIntensity;
+                                }
+                            }
+                            const f3 shadow_offset = dot(hit.normal, L) > 0.0f ? hit.normal * 1e-4f : -hit.normal * 1e-4f;
+                            shadow_o = hit.point + shadow_offset;
+                            shadow_tmax = light_dist - 1e-3f;
+                            // bsdf * light_radiance * attenuation / pdf: the last three factors are kept apart so the product is
+                            // formed in the reference's order
+                            light_scale = light_radiance;
+                            light_att = attenuation;
+                            want_shadow = true;
+                        }
+                    }
+                }
+                // ---- [C2] the light sample's value, before its visibility is known (path_logic.cuh:840-867): what a visible
+                // sample adds to `acc`, formed from the same operands in the same order as in the reference.  A sample that adds
+                // nothing either way (outside a spot cone, BSDF zero below the horizon) is not walked; the frame does not walk it.
+                const KParams &KC2 = kparams(kp0);
+                bool lit = false;
+                f3 lit_now = mk3(0.0f);
+                if (want_shadow) {
+                    const Material mat = load_material(KC2.materials, h.mesh);
+                    const f3 V = -rd;
+                    const f3 bsdf = evaluateBSDF<FULL>(hit, mat, L, V);
+                    if (pdf_sample > 0.0f) {
+                        f3 direct = bsdf * light_scale * light_att / pdf_sample;
+                        direct = clamp_vector_soft(direct, 500.0f);
+                        if (direct.x > 0.0f || direct.y > 0.0f || direct.z > 0.0f) {
+                            const float pdf_brdf = material_pdf<FULL>(hit, mat, V, L);
+                            const float wgt = mis_weight(pdf_sample, pdf_brdf);
+                            lit_now = throughput * direct * wgt;
+                            lit = true;
+                        }
+                    }
+                }
+                // ---- [D] shadow rays, all lanes that have one together (bvh_any_hit_tlas); the contribution is added once its
+                // visibility is known and before anything else touches the path's radiance
+                const KParams &KD = kparams(kp0);
+                if (__builtin_amdgcn_ballot_w64(lit)) {
+                    const bool in_shadow = (PMODE == 1)   ? any_hit_pairs(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
+                                           : (PMODE == 2) ? any_hit_pairs_dyn(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
+                                           : (PMODE == 3) ? any_hit_pairs_tlas(KD, PL, lane, lit, shadow_o, L, shadow_tmax, cyc)
+                                                          : any_hit<GEOM>(KD, lit, shadow_o, L, shadow_tmax, stk);
+                    if (lit && !in_shadow)
+                        acc = acc + lit_now;
+                }
+                // ---- [E] second half of the shading
+                const KParams &KE = kparams(kp0);
+                if (shaded) {
+                    const Material mat = load_material(KE.materials, h.mesh);
+                    f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
+                    bool is_specular = false;
+                    if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular)) {
+                        end_path = true;
+                    } else {
+                        prev_was_specular = is_specular;
+                        bool killed = false;
+                        if (bounce >= 2) { // Russian roulette (path_logic.cuh:871-880)
+                            const float p = max_(0.05f, min_(0.95f, max_(throughput.x, max_(throughput.y, throughput.z))));
+                            if (rng_uniform(rng) > p)
+                                killed = true;
+                            else
+                                throughput = throughput / p;
+                        }
+                        if (killed) {
+                            end_path = true;
+                        } else {
+                            throughput = throughput * att;
+                            throughput = clamp_vector_soft(throughput, 50.0f);
+                            const f3 off = hit.normal * 1e-4f;
+                            ro = (dot(scatter_dir, hit.normal) > 0.0f) ? (hit.point + off) : (hit.point - off);
+                            rd = scatter_dir;
+                            ray_spec = is_specular;
+                            ++bounce;
+                            if (bounce >= KE.max_depth)
+                                end_path = true;
+                        }
+                    }
+                }
+                if (act && end_path) { // the sample is complete (scene_kernels.cuh:170-171)
+                    acc = clamp_vector_soft(acc, 100.0f);
+                    sum = sum + acc;
+                    act = false;
+                }
+            }
+        }
+        if (live) {
+            uint32_t *st = rng_states + i * 6;
+            st[0] = rng.d;
+            st[1] = rng.v0;
+            st[2] = rng.v1;
+            st[3] = rng.v2;
+            st[4] = rng.v3;
+            st[5] = rng.v4;
+            const f3 mean = sum / (float)kparams(kp0).spp;
+            RadianceOut *r = out + i;
+            r->radiance[0] = mean.x;
+            r->radiance[1] = mean.y;
+            r->radiance[2] = mean.z;
+        }
+    }
+    cyc.flush(lane);
+}
+
+// The primary rays ptrt_render(frame, ..) gives sample `sample` of every pixel of the context's rows, pinhole camera: phase [A]
+// of path_trace_kernel (scene_kernels.cuh:147-167, camera.cuh:156-158) through the same device functions, one thread per pixel,
+// ray yl * width + x.  K.frame_count = frame + sample.
+__global__ __launch_bounds__(256) void camera_rays_kernel(const KParams K, float *__restrict__ origins, float *__restrict__ dirs) {
+    const size_t npix = (size_t)K.rows * K.width;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix)
+        return;
+    const int yl = (int)(i / (size_t)K.width), x = (int)(i % (size_t)K.width);
+    const int y = global_row(yl, K.y0, K.il_period, K.il_phase);
+    float tjx, tjy, bnx, bny;
+    taa_jitter(K.frame_count, tjx, tjy);
+    blue_noise_jitter(K.blue_noise, x, y, K.frame_count, bnx, bny);
+    const float jitter_x = tjx + (bnx - 0.5f) * 0.25f;
+    const float jitter_y = tjy + (bny - 0.5f) * 0.25f;
+    const float u = ((float)x + 0.5f + jitter_x) / (float)K.width;
+    const float v = 1.0f - ((float)y + 0.5f + jitter_y) / (float)K.height;
+    const f3 dir = K.cam.llc + u * K.cam.horizontal + v * K.cam.vertical - K.cam.origin;
+    const f3 ro = K.cam.origin;
+    const f3 rd = normalize(dir);
+    origins[i * 3 + 0] = ro.x;
+    origins[i * 3 + 1] = ro.y;
+    origins[i * 3 + 2] = ro.z;
+    dirs[i * 3 + 0] = rd.x;
+    dirs[i * 3 + 1] = rd.y;
+    dirs[i * 3 + 2] = rd.z;
+}
+
+// n generator states in canonical order {d, v0..v4}, state(seed) advanced by first, first + 1, .. subsequences of 2^67 draws:
+// xorwow_init_kernel's arithmetic (the jump matrices selected by the bits of the subsequence number) for a number the caller
+// chooses instead of the pixel's.
+__global__ __launch_bounds__(256) void rng_states_kernel(uint32_t *__restrict__ states, size_t n, unsigned long long first,
+                                                         uint32_t d0, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3,
+                                                         uint32_t s4, const uint32_t *__restrict__ jump, int n_jump) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    unsigned long long sub = first + (unsigned long long)i;
+    uint32_t v[5] = {s0, s1, s2, s3, s4};
+    for (int k = 0; k < n_jump && sub; ++k, sub >>= 1) {
+        if (!(sub & 1ull))
+            continue;
+        const uint32_t *M = jump + (size_t)k * 800;
+        uint32_t a[5] = {0, 0, 0, 0, 0};
+        for (int w = 0; w < 5; ++w) {
+            uint32_t bits = v[w];
+            while (bits) {
+                const int b = __builtin_ctz(bits);
+                bits &= bits - 1;
+                const uint32_t *c = M + (w * 32 + b) * 5;
+                a[0] ^= c[0];
+                a[1] ^= c[1];
+                a[2] ^= c[2];
+                a[3] ^= c[3];
+                a[4] ^= c[4];
+            }
+        }
+        for (int w = 0; w < 5; ++w)
+            v[w] = a[w];
+    }
+    states[i * 6 + 0] = d0;
+    states[i * 6 + 1] = v[0];
+    states[i * 6 + 2] = v[1];
+    states[i * 6 + 3] = v[2];
+    states[i * 6 + 4] = v[3];
+    states[i * 6 + 5] = v[4];
+}
+
+} // namespace pt

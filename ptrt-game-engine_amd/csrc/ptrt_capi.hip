@@ -17,6 +17,7 @@
 #include "pt_async.hip.h"
 #include "pt_wireframe.hip.h"
 #include "pt_query.hip.h"
+#include "pt_radiance.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -201,7 +202,7 @@ struct ptrt_ctx {
     int pm1_lane_groups_eff = 0;     // ... the last frame or ray query (0 as well when another traversal mode ran it)
     int tile_run = 8;                // option "tile_run": of every 8 * run consecutive tiles XCD x renders a run of neighbours (path_trace_kernel); 0: tile k on workgroup k
     int ticket_tiles = 1;            // option "ticket_tiles": consecutive tiles per ticket of the queue
-    int persist = 0, n_cus = 0;      // option "persist": persistent waves per CU (0 = the variant's occupancy)
+    int persist = 0, n_cus = 0;      // option "persist": persistent waves per CU (0 = the variant's occupancy): lane refill and the radiance query
     int as_blocks[2] = {0, 0}; // resident workgroups of the <false>/<true> kernel at as_lds bytes of LDS
     size_t as_lds = 0;
 
@@ -369,6 +370,35 @@ const std::vector<uint32_t> &jump_matrices() {
     }
     });
     return out;
+}
+
+// The jump matrices on the device, enough of them for subsequence numbers up to `last` (one per bit).
+int ensure_jump(ptrt_ctx *c, unsigned long long last, const char *who) {
+    int bits = 1;
+    while (bits < 64 && (last >> bits) != 0)
+        ++bits;
+    if (bits > c->n_jump) {
+        if (bits > JUMP_MAX)
+            return fail(c, PTRT_E_INVALID, "%s: subsequence numbers of %d bits (at most %d: 2^%d pixels or states)", who, bits, JUMP_MAX, JUMP_MAX);
+        const std::vector<uint32_t> &J = jump_matrices();
+        dfree(c->d_jump);
+        c->n_jump = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_jump, (size_t)bits * 800 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemcpy(c->d_jump, J.data(), (size_t)bits * 800 * sizeof(uint32_t), hipMemcpyHostToDevice));
+        c->n_jump = bits;
+    }
+    return PTRT_OK;
+}
+// curand_init's state scrambling (published cuRAND XORWOW; constants unverified)
+struct XorwowSeed {
+    uint32_t d, v[5];
+};
+XorwowSeed xorwow_seed(unsigned long long seed) {
+    const uint32_t s0 = ((uint32_t)seed) ^ 0xaad26b49u;
+    const uint32_t s1 = (uint32_t)(seed >> 32) ^ 0xf7dcefddu;
+    const uint32_t t0 = 1099087573u * s0;
+    const uint32_t t1 = 2591861531u * s1;
+    return XorwowSeed{6615241u + t1 + t0, {123456789u + t0, 362436069u ^ t0, 521288629u + t1, 88675123u ^ t1, 5783321u + t0}};
 }
 
 int set_device(ptrt_ctx *c) {
@@ -724,29 +754,12 @@ int ptrt_reset_rng(ptrt_ctx *c, unsigned long long seed) {
         return rc;
     // bits needed for the largest global pixel index of this tile
     const unsigned long long last = (unsigned long long)(c->il_period > 1 ? c->H : c->y0 + c->rows) * (unsigned long long)c->W;
-    int bits = 1;
-    while ((last >> bits) != 0)
-        ++bits;
-    if (bits > c->n_jump) {
-        if (bits > JUMP_MAX)
-            return fail(c, PTRT_E_INVALID, "ptrt_reset_rng: frame of 2^%d pixels (at most 2^%d)", bits, JUMP_MAX);
-        const std::vector<uint32_t> &J = jump_matrices();
-        dfree(c->d_jump);
-        HIP_TRY(c, hipMalloc((void **)&c->d_jump, (size_t)bits * 800 * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemcpy(c->d_jump, J.data(), (size_t)bits * 800 * sizeof(uint32_t), hipMemcpyHostToDevice));
-        c->n_jump = bits;
-    }
-    // curand_init's state scrambling (published cuRAND XORWOW; constants unverified)
-    const uint32_t s0 = ((uint32_t)seed) ^ 0xaad26b49u;
-    const uint32_t s1 = (uint32_t)(seed >> 32) ^ 0xf7dcefddu;
-    const uint32_t t0 = 1099087573u * s0;
-    const uint32_t t1 = 2591861531u * s1;
-    const uint32_t d0 = 6615241u + t1 + t0;
-    const uint32_t v0 = 123456789u + t0, v1 = 362436069u ^ t0, v2 = 521288629u + t1, v3 = 88675123u ^ t1,
-                   v4 = 5783321u + t0;
+    if (int rc = ensure_jump(c, last, "ptrt_reset_rng"))
+        return rc;
+    const XorwowSeed s = xorwow_seed(seed);
     const int grid = (int)((c->npix + 255) / 256);
     hipLaunchKernelGGL(pt::xorwow_init_kernel, dim3(grid), dim3(256), 0, c->stream, c->d_rng, c->W, c->rows, c->y0,
-                       c->il_period, c->il_phase, d0, v0, v1, v2, v3, v4, c->d_jump, c->n_jump);
+                       c->il_period, c->il_phase, s.d, s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], c->d_jump, c->n_jump);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the reference synchronises here too (scene.cuh:455)
     c->rng_ready = true;
@@ -1192,6 +1205,138 @@ int ptrt_query_rays(ptrt_ctx *c, int kind, const float *origins, const float *di
     // a path frame that follows is ordered behind the query on the stream, as behind the wireframe view (option "pipeline")
     c->touched = true;
     return launch_query(c, kind, origins, directions, tmax, rays, out);
+}
+
+} // extern "C"
+
+// radiance_query_kernel (pt_radiance.hip.h) over n rays and generator states in device memory, on the context's stream: the
+// launch of run_query -- the same traversal mode, LDS size and persistent grid -- with the materials a frame would use
+// (plan_frame's `full`).
+template <int GEOM, bool FULL, int PMODE>
+int run_radiance(ptrt_ctx *c, const pt::KParams &K, size_t lds, const float *o, const float *d, uint32_t *rng, size_t n,
+                 pt::RadianceOut *out) {
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt::radiance_query_kernel<GEOM, FULL, PMODE>, 64, lds));
+    if (c->persist > 0) // option "persist": persistent waves per CU
+        per_cu = c->persist;
+    const size_t chunks = (n + 63) / 64, slots = (size_t)(c->n_cus > 0 ? c->n_cus : 1) * (size_t)(per_cu > 0 ? per_cu : 1);
+    const unsigned grid = (unsigned)(chunks < slots ? chunks : slots);
+    hipLaunchKernelGGL((pt::radiance_query_kernel<GEOM, FULL, PMODE>), dim3(grid), dim3(64), lds, c->stream, K, o, d, rng, n, out);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+template <bool FULL>
+int dispatch_radiance(ptrt_ctx *c, int geom, int pmode, const pt::KParams &K, size_t lds, const float *o, const float *d,
+                      uint32_t *rng, size_t n, pt::RadianceOut *out) {
+    switch (pmode ? pmode : -geom) { // (as dispatch_query)
+    case 1: return run_radiance<0, FULL, 1>(c, K, lds, o, d, rng, n, out);
+    case 2: return run_radiance<1, FULL, 2>(c, K, lds, o, d, rng, n, out);
+    case 3: return run_radiance<2, FULL, 3>(c, K, lds, o, d, rng, n, out);
+    case 0: return run_radiance<0, FULL, 0>(c, K, lds, o, d, rng, n, out);
+    case -1: return run_radiance<1, FULL, 0>(c, K, lds, o, d, rng, n, out);
+    default: return run_radiance<2, FULL, 0>(c, K, lds, o, d, rng, n, out);
+    }
+}
+
+extern "C" {
+
+int ptrt_query_radiance(ptrt_ctx *c, const float *origins, const float *directions, uint32_t *rng_states, int n, int samples,
+                        int max_depth, ptrt_radiance *out) {
+    static_assert(sizeof(pt::RadianceOut) == sizeof(ptrt_radiance) && sizeof(ptrt_radiance) == 32, "RadianceOut must mirror ptrt_radiance");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: bad context");
+    if (n < 0 || !origins || !directions || !rng_states || !out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: bad argument (n %d, origins %p, directions %p, rng_states %p, out %p)", n,
+                    (const void *)origins, (const void *)directions, (const void *)rng_states, (const void *)out);
+    if (samples < 1 || max_depth < 1 || samples > 32767 || max_depth > 32767) // (ptrt_render's range)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: samples=%d max_depth=%d (1..32767)", samples, max_depth);
+    if (!c->have_geometry || !c->have_materials)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_radiance: %s not uploaded", c->have_geometry ? "materials" : "geometry");
+    if (c->n_materials < c->n_meshes)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_radiance: %d materials for %d meshes", c->n_materials, c->n_meshes);
+    if (n == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const size_t rays = (size_t)n;
+    const char *bad = !device_span(c, origins, rays * 12)                      ? "origins"
+                      : !device_span(c, directions, rays * 12)                 ? "directions"
+                      : !device_span(c, rng_states, rays * 24)                 ? "rng_states"
+                      : !device_span(c, out, rays * sizeof(ptrt_radiance))     ? "out"
+                                                                               : nullptr;
+    if (bad)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: %s is not %zu bytes of device memory on device %d", bad,
+                    rays * (bad[0] == 'r' ? 24 : bad[0] == 'o' && bad[1] == 'u' ? sizeof(ptrt_radiance) : 12), c->device);
+    pt::KParams K = make_params(c);
+    K.spp = samples;
+    K.max_depth = max_depth;
+    // (the context's own per-pixel buffers are no business of the query's)
+    K.rng = nullptr;
+    K.accum = K.normal = K.depth = nullptr;
+    K.object_id = nullptr;
+    K.rgb8 = nullptr;
+    const int geom = pick_geom(c);
+    const int pmode = pair_mode(c, geom, false);
+    const bool full = c->mats_full || c->force_full;
+    const size_t lds = trace_lds_bytes(c, geom, pmode);
+    // a path frame that follows is ordered behind the query on the stream (option "pipeline"), as behind ptrt_query_rays
+    c->touched = true;
+    c->query_pmode = pmode;
+    c->pm1_lane_groups_eff = pmode == 1 ? K.pm1_groups : 0;
+    if (pmode == 3)
+        if (int rc = refresh_tlas_heads(c, false))
+            return rc;
+    pt::RadianceOut *o = reinterpret_cast<pt::RadianceOut *>(out);
+    return full ? dispatch_radiance<true>(c, geom, pmode, K, lds, origins, directions, rng_states, rays, o)
+                : dispatch_radiance<false>(c, geom, pmode, K, lds, origins, directions, rng_states, rays, o);
+}
+
+int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins, float *d_directions) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: bad context");
+    if (frame_index < 0 || sample < 0 || frame_index > INT_MAX - sample)
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: frame_index=%d sample=%d", frame_index, sample);
+    if (!d_origins || !d_directions)
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: a target is NULL");
+    if (c->cam.lens_radius > 0.0f)
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: a thin lens (lens_radius %g): the lens sample of a primary ray is drawn "
+                                       "from the pixel's generator stream", (double)c->cam.lens_radius);
+    if (int rc = set_device(c))
+        return rc;
+    pt::KParams K = make_params(c);
+    K.frame_count = frame_index + sample;
+    const size_t rays = (size_t)K.rows * K.width;
+    const char *bad = !device_span(c, d_origins, rays * 12) ? "d_origins" : !device_span(c, d_directions, rays * 12) ? "d_directions" : nullptr;
+    if (bad)
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: %s is not %zu bytes of device memory on device %d", bad, rays * 12, c->device);
+    c->touched = true;
+    hipLaunchKernelGGL(pt::camera_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, c->stream, K, d_origins, d_directions);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_init_rng_states(ptrt_ctx *c, unsigned long long seed, unsigned long long first_subsequence, int n, uint32_t *d_states) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: bad context");
+    if (n < 0 || !d_states)
+        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: bad argument (n %d, d_states %p)", n, (const void *)d_states);
+    if (n == 0)
+        return PTRT_OK;
+    const unsigned long long last = first_subsequence + (unsigned long long)(n - 1);
+    if (last < first_subsequence)
+        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: subsequence numbers beyond 2^64");
+    if (int rc = set_device(c))
+        return rc;
+    if (!device_span(c, d_states, (size_t)n * 24))
+        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: d_states is not %zu bytes of device memory on device %d", (size_t)n * 24, c->device);
+    if (int rc = ensure_jump(c, last, "ptrt_init_rng_states"))
+        return rc;
+    const XorwowSeed s = xorwow_seed(seed);
+    c->touched = true;
+    hipLaunchKernelGGL(pt::rng_states_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream, d_states, (size_t)n,
+                       first_subsequence, s.d, s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], c->d_jump, c->n_jump);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
 }
 
 int ptrt_render_wireframe(ptrt_ctx *c, float thickness, void *out_rgb8, int out_is_device) {

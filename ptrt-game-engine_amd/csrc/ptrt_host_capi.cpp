@@ -394,6 +394,21 @@ int hs_query_occluded(void *s, const void *d_origins, const void *d_dirs, const 
                                                         static_cast<const float *>(d_tmax), n, static_cast<int32_t *>(d_out)));
     return 0;
 }
+int hs_query_radiance(void *s, const void *d_origins, const void *d_dirs, void *d_rng_states, int n, int samples, int max_depth,
+                      void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryRadiance(static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs),
+                                                  static_cast<uint32_t *>(d_rng_states), n, samples, max_depth,
+                                                  static_cast<ptrt_radiance *>(d_out)));
+    return 0;
+}
+int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
+    HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
+    return 0;
+}
+int hs_init_rng_states(void *s, unsigned long long seed, unsigned long long first, int n, void *d_states) {
+    HS_TRY(static_cast<Scene *>(s)->initRngStates(seed, first, n, static_cast<uint32_t *>(d_states)));
+    return 0;
+}
 int hs_render_wireframe_to_host(void *s, void *host_pixels, float thickness) {
     HS_TRY(static_cast<Scene *>(s)->render_wireframe_to_host(static_cast<unsigned char *>(host_pixels), thickness));
     return 0;

@@ -1049,6 +1049,30 @@ class Scene {
         updateAccelerationStructures();
         check(ptrt_query_rays(ctx, PTRT_QUERY_OCCLUDED, d_origins, d_dirs, d_tmax, n, d_out), "Occlusion query failed");
     }
+    // Path-traced radiance for rays the caller chooses (ptrt_query_radiance): per ray tracePath with the ray's own generator
+    // state (d_rng_states: n * 6 words, canonical order, advanced in place), `samples` times, the mean and the first hit of
+    // sample 0 in d_out.  Everything a frame reads is committed first -- geometry, materials, lights, sky, environment map.
+    // max_depth <= 0: the frame's bounce depth (perfSettings.maxBounceDepth).
+    void queryRadiance(const float *d_origins, const float *d_dirs, uint32_t *d_rng_states, int n, int samples, int max_depth,
+                       ptrt_radiance *d_out) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_query_radiance(ctx, d_origins, d_dirs, d_rng_states, n, samples,
+                                  max_depth > 0 ? max_depth : perfSettings.maxBounceDepth, d_out),
+              "Radiance query failed");
+    }
+    // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
+    // tile rows * width * 3 floats each, in the order of the colour buffer.
+    void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_camera_rays(ctx, frame, sample, d_origins, d_dirs), "Camera rays failed");
+    }
+    // n fresh generator states for subsequences first .. first + n - 1 of `seed` (ptrt_init_rng_states), n * 6 words.
+    void initRngStates(unsigned long long seed, unsigned long long first, int n, uint32_t *d_states) {
+        needBackend();
+        check(ptrt_init_rng_states(ctx, seed, first, n, d_states), "Generator states failed");
+    }
 
     void saveAsPPM(const std::string &filename, unsigned char *pixels) const { // ASCII P3, scene.cuh:1694-1708
         std::ofstream ofs(filename, std::ios::binary);

@@ -112,6 +112,11 @@ class Hit(C.Structure):
                 ("face_index", C.c_int32), ("local_point", Vec3)]
 
 
+class Radiance(C.Structure):
+    """`ptrt_radiance`: one ray's answer from ptrt_query_radiance."""
+    _fields_ = [("radiance", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("object_id", C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64),
                 ("shadow_rays_walked", C.c_uint64)]
@@ -121,6 +126,8 @@ HIT_DTYPE = np.dtype([("hit", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("norma
                       ("mesh_index", "<i4"), ("front_face", "<i4"), ("u", "<f4"), ("v", "<f4"),
                       ("face_index", "<i4"), ("local_point", "<f4", 3)])
 assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
+RADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("object_id", "<i4")])
+assert RADIANCE_DTYPE.itemsize == C.sizeof(Radiance) == 32
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
@@ -160,6 +167,9 @@ _sig("ptrt_write_rng", C.c_int, _vp, C.POINTER(C.c_uint32), C.c_size_t)
 _sig("ptrt_trace_rays", C.c_int, _vp, _fp, _fp, C.c_int, _vp)
 _sig("ptrt_render_wireframe", C.c_int, _vp, C.c_float, _vp, C.c_int)
 _sig("ptrt_query_rays", C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp)
+_sig("ptrt_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
+_sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
 _sig("ptrt_set_option", C.c_int, _vp, C.c_char_p, C.c_longlong)
 _sig("ptrt_get_option", C.c_int, _vp, C.c_char_p, C.POINTER(C.c_longlong))
@@ -282,6 +292,9 @@ _sig("hs_render_wireframe_to_device", C.c_int, _vp, _vp, C.c_float)
 _sig("hs_render_wireframe_to_host", C.c_int, _vp, _vp, C.c_float)
 _sig("hs_query_closest", C.c_int, _vp, _vp, _vp, C.c_int, _vp)
 _sig("hs_query_occluded", C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp)
+_sig("hs_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
+_sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
 _sig("hs_get_frame_count", C.c_int, _vp)
 _sig("hs_set_frame_count", None, _vp, C.c_int)
@@ -358,6 +371,21 @@ def _is_tensor(a):
 HIT_COLUMNS = dict(hit=(0, 1, False), t=(1, 2, True), point=(2, 5, True), normal=(5, 8, True), mesh_index=(8, 9, False),
                    front_face=(9, 10, False), u=(10, 11, True), v=(11, 12, True), face_index=(12, 13, False),
                    local_point=(13, 16, True))
+
+
+# columns of the (n, 8) float32 rows of Scene.query_radiance: the fields of ptrt_radiance / RADIANCE_DTYPE
+RADIANCE_COLUMNS = dict(radiance=(0, 3, True), depth=(3, 4, True), normal=(4, 7, True), object_id=(7, 8, False))
+
+
+def radiance_fields(records):
+    """Named views of query_radiance's (n, 8) float32 tensor: object_id reinterpreted as int32, scalars as (n,)."""
+    import torch
+    i = records.view(torch.int32)
+    out = {}
+    for name, (a, b, is_f) in RADIANCE_COLUMNS.items():
+        col = (records if is_f else i)[:, a:b]
+        out[name] = col[:, 0] if b - a == 1 else col
+    return out
 
 
 def hit_fields(hits):
@@ -863,6 +891,89 @@ class Scene:
             cur.wait_stream(ctx_stream)
         return out
 
+    # ---- path-traced radiance for caller-supplied rays (ptrt_query_radiance through Scene::queryRadiance) ----
+    def _device_tensor(self, what, a, cols, dtype):
+        if not _is_tensor(a):
+            raise ValueError(f"{what}: needs a torch tensor on the scene's device, got {type(a).__name__}")
+        if a.device.type != "cuda" or a.device.index != self.device:
+            raise ValueError(f"{what}: tensor on {a.device}, this scene renders on " +
+                             (f"cuda:{self.device}" if self.device >= 0 else "no device (host-only)"))
+        if a.dim() != 2 or a.shape[1] != cols or str(a.dtype) not in dtype.split("|"):
+            raise ValueError(f"{what}: shape {tuple(a.shape)} of {a.dtype}, expected (n, {cols}) of {dtype}")
+        if not a.is_contiguous():
+            raise ValueError(f"{what}: tensors must be contiguous")
+
+    def _enqueue_between_streams(self, dev, call):
+        """`call()` enqueues on the context's stream: that stream waits for what torch's current stream holds, torch's
+        current stream for the call (the convention of query_closest)"""
+        import torch
+        cur = torch.cuda.current_stream(dev)
+        ctx_stream = torch.cuda.ExternalStream(self.get_option("stream"), device=dev)
+        other = ctx_stream.cuda_stream != cur.cuda_stream
+        if other:
+            ctx_stream.wait_stream(cur)
+        call()
+        if other:
+            cur.wait_stream(ctx_stream)
+
+    def query_radiance(self, origins, directions, rng_states, samples=1, max_depth=None, out=None):
+        """Path-traced radiance along every ray: tracePath with the ray's own generator state, `samples` times, `max_depth`
+        bounces (None: the scene's bounce depth).  torch tensors on this scene's device, contiguous, read in place: origins and
+        directions (n, 3) float32, rng_states (n, 6) int32 (or uint32) in the canonical order of `read(BUF_RNG)` -- `init_rng_states` makes
+        fresh ones -- ADVANCED IN PLACE, so a later call continues each ray's stream.  Returns an (n, 8) float32 tensor, one
+        32-byte `ptrt_radiance` per row: radiance 0:3, depth 3, normal 4:7 and the object id's int32 bits in column 7
+        (`radiance_fields` names them); `out` takes such a tensor to write into.  No synchronisation."""
+        self._device_tensor("query_radiance: origins", origins, 3, "torch.float32")
+        self._device_tensor("query_radiance: directions", directions, 3, "torch.float32")
+        self._device_tensor("query_radiance: rng_states", rng_states, 6, "torch.int32|torch.uint32")
+        n = origins.shape[0]
+        if directions.shape[0] != n or rng_states.shape[0] != n:
+            raise ValueError(f"query_radiance: {n} origins, {directions.shape[0]} directions, {rng_states.shape[0]} states")
+        if n >= 2 ** 31:
+            raise ValueError(f"query_radiance: {n} rays (at most 2^31 - 1 per call)")
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=origins.device)
+        else:
+            self._device_tensor("query_radiance: out", out, 8, "torch.float32")
+            if out.shape[0] != n:
+                raise ValueError(f"query_radiance: out has {out.shape[0]} rows for {n} rays")
+        if n == 0:
+            return out
+        self._enqueue_between_streams(origins.device, lambda: self._chk(lib.hs_query_radiance(
+            self._h, _vp(origins.data_ptr()), _vp(directions.data_ptr()), _vp(rng_states.data_ptr()), n, int(samples),
+            0 if max_depth is None else int(max_depth), _vp(out.data_ptr()))))
+        return out
+
+    def camera_rays(self, frame, sample=0):
+        """(origins, directions): (rows * width, 3) float32 tensors on this scene's device holding the primary rays
+        render_to_device gives sample `sample` of frame `frame`, in the order of `read(BUF_ACCUM)` (ptrt_camera_rays; pinhole
+        cameras only).  No synchronisation."""
+        import torch
+        if self.device < 0:
+            self._chk(lib.hs_camera_rays(self._h, int(frame), int(sample), None, None))
+        dev = torch.device("cuda", self.device)
+        rw, rh = self.renderSize()
+        n = self.tile_rows * self.width if (rw, rh) == (self.width, self.height) else rw * rh
+        o = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        d = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        self._enqueue_between_streams(dev, lambda: self._chk(lib.hs_camera_rays(
+            self._h, int(frame), int(sample), _vp(o.data_ptr()), _vp(d.data_ptr()))))
+        return o, d
+
+    def init_rng_states(self, seed, first, n):
+        """(n, 6) int32 tensor on this scene's device: fresh generator states for subsequences first .. first + n - 1 of
+        `seed` in the canonical order (ptrt_init_rng_states) -- what reset_rng(seed) gives pixel `first + i`."""
+        import torch
+        if self.device < 0:
+            self._chk(lib.hs_init_rng_states(self._h, int(seed), int(first), int(n), None))
+        dev = torch.device("cuda", self.device)
+        st = torch.empty((int(n), 6), dtype=torch.int32, device=dev)
+        if n:
+            self._enqueue_between_streams(dev, lambda: self._chk(lib.hs_init_rng_states(
+                self._h, int(seed), int(first), int(n), _vp(st.data_ptr()))))
+        return st
+
     def traceSingleRay(self, origin, direction):
         h = Hit()
         self._chk(lib.hs_trace_single_ray(self._h, _f3(origin), _f3(direction), C.byref(h)))
@@ -942,4 +1053,4 @@ class TileFarm:
             pass
 
 
-from . import scenes  # noqa: E402,F401
+from . import cameras, scenes  # noqa: E402,F401
