@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms, + ptrt_query_radiance / ptrt_camera_rays / ptrt_init_rng_states (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
+#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms, + ptrt_query_radiance / ptrt_camera_rays / ptrt_init_rng_states, + ptrt_query_probes (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
 
 enum {
     PTRT_OK = 0,
@@ -158,6 +158,16 @@ typedef struct ptrt_radiance {
     float normal[3];   /* first hit of sample 0, zeros on a miss (NORMAL)     */
     int32_t object_id; /* first hit of sample 0, -1 on a miss (OBJECT_ID)     */
 } ptrt_radiance;
+
+/* One light probe's answer from ptrt_query_probes: means over the probe's n_dirs rays, 128 bytes.  (Two reserved words, not
+ * one: 27 + 3 values and the padding that makes the record one 128-byte row.) */
+typedef struct ptrt_probe {
+    float sh[9][3];         /* mean of Y_i(d_k) * L_c(p, k): radiance on the real spherical harmonics of bands 0-2, RGB */
+    float mean_distance;    /* mean of dist = min(depth, max_distance); a miss has depth 1e30f                           */
+    float mean_distance_sq; /* mean of dist * dist                                                                       */
+    float hit_fraction;     /* mean of (object_id >= 0 ? 1.0f : 0.0f)                                                    */
+    float reserved[2];      /* 0.0f                                                                                      */
+} ptrt_probe;
 
 /* Per-frame counters of the trace stage (Mrays/s numerator). */
 typedef struct ptrt_stats {
@@ -553,6 +563,42 @@ int ptrt_query_rays(ptrt_ctx *ctx, int kind, const float *origins, const float *
 int ptrt_query_radiance(ptrt_ctx *ctx, const float *origins, const float *directions, uint32_t *rng_states, int n,
                         int samples, int max_depth, ptrt_radiance *out);
 
+/* Light probes on DEVICE memory (ABI 6, addition only; no counterpart in the reference): probe p sends n_dirs rays from
+ * positions[p] (n_probes*3 floats), ray (p, k) along directions[k] (n_dirs*3 floats, ONE set shared by all probes, used as
+ * given and NOT normalised, for the ray and for the basis) with generator state p*n_dirs + k of `rng_states`
+ * (n_probes*n_dirs*6 uint32, canonical order, advanced IN PLACE as by ptrt_query_radiance).  L(p,k), the first-hit depth and
+ * the object id of ray (p, k) are exactly what ptrt_query_radiance puts into ptrt_radiance for that ray and state with the same
+ * `samples` and `max_depth` -- the quirk that a primary ray takes no light sample at its first hit included -- and probe p's
+ * record holds MEANS over k of these terms, all in float32:
+ *     sh[i][c]          Y_i(d_k) * L_c          with d_k = (x, y, z) and, in this operation order,
+ *                           Y0 = 0.282095f
+ *                           Y1 = 0.488603f*y
+ *                           Y2 = 0.488603f*z
+ *                           Y3 = 0.488603f*x
+ *                           Y4 = 1.092548f*(x*y)
+ *                           Y5 = 1.092548f*(y*z)
+ *                           Y6 = 0.315392f*(3.0f*(z*z) - 1.0f)
+ *                           Y7 = 1.092548f*(x*z)
+ *                           Y8 = 0.546274f*(x*x - y*y)
+ *     mean_distance     dist = min(depth, max_distance)   (a miss has depth 1e30f)
+ *     mean_distance_sq  dist*dist
+ *     hit_fraction      object_id >= 0 ? 1.0f : 0.0f
+ * and reserved is 0.0f.  The sum order of every quantity is part of the contract: a chunk of 64 consecutive k, padded with
+ * +0.0f terms for absent k, is summed by folding halves -- v[j] + v[j + 32], then 16, 8, 4, 2, 1 --, the chunk sums are added
+ * in chunk order to a total that starts at +0.0f, and the total is divided by (float)n_dirs (IEEE division, exactly rounded).
+ * tests/probe_restatement.py states it in numpy.  The outputs are means: for directions uniform on the sphere the caller
+ * multiplies by 4 pi to get the projection's integral (ptrt_amd.probes.sh9_irradiance does).
+ * Ordering and side effects are those of ptrt_query_radiance: enqueued on the context's stream with no allocation, copy or
+ * synchronisation; it touches none of the context's generator states, frame buffers, ptrt_get_stats counters or timing
+ * histories; ptrt_get_option "query_pmode" reports the traversal.  One wave owns a probe, so a call with few probes and very
+ * many directions fills the device better through ptrt_query_radiance.  PTRT_E_INVALID (nothing enqueued, `d_out` and the
+ * states untouched) for n_probes < 0, n_dirs < 1, a NULL pointer, memory that is not the context's device memory or an
+ * allocation too small (byte counts are formed in size_t), samples / max_depth outside 1..32767, or a max_distance that is
+ * not positive and finite; PTRT_E_NOT_READY before geometry and materials are uploaded; n_probes == 0 returns PTRT_OK and
+ * launches nothing. */
+int ptrt_query_probes(ptrt_ctx *ctx, const float *d_positions, int n_probes, const float *d_directions, int n_dirs,
+                      uint32_t *d_rng_states, int samples, int max_depth, float max_distance, ptrt_probe *d_out);
+
 /* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
  * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small
  * kernel on the context's stream into DEVICE memory: rows*W*3 floats each (render_w*render_h*3 at a reduced render size),
@@ -694,7 +740,7 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         2: wherever PMODE 1 runs; 0: never.  ptrt_get_option "refilled" says what the last frame did.
  *                         ticket_tiles 1..16: consecutive tiles per draw from the queue (1; more only pays where the counter
  *                         itself binds -- 1 spp: 0.61 -> 0.49 ms with 4, still behind the one-tile-per-wave kernel's 0.43).
- *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance: N one-wave workgroups per CU
+ *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance and ptrt_query_probes: N one-wave workgroups per CU
  *                         instead of what the kernel's occupancy holds (tests: a grid smaller than the batch's chunks).
  *   sample_sync -1|0|1    the lanes of a wave start their samples together (1) instead of each as soon as its path has ended (0):
  *                         the wave's lanes then sit at the same bounce, the light-sample phases are skipped by the whole wave at a
@@ -750,7 +796,7 @@ int ptrt_set_option(ptrt_ctx *ctx, const char *name, long long value);
  * timed: render_mode (0 megakernel, 1 wavefront stages, 2 asynchronous lanes), pmode (0 lock-step, 1 pairs over LDS-staged
  * triangles, 2 pair queue, 3 TLAS rounds, 4 merged queue), merged_eff (loop shape of that launch), merged_decided (0 while
  * merged = -1 is still sampling), launches.  ABI 5.  Also read-only (ABI 6): query_pmode, the traversal of the last
- * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance (-1 none yet), and stream, the hipStream_t the context enqueues on. */
+ * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes (-1 none yet), and stream, the hipStream_t the context enqueues on. */
 int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
 
 /* The plan behind option "pm1_lane_groups" for leaves of `leaf_triangles` triangles, as ptrt_upload_geometry builds it; needs

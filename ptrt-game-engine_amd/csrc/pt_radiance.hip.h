@@ -27,25 +27,215 @@ struct RadianceOut { // == ptrt_radiance (include/ptrt.h)
     int object_id;
 };
 
-// Waves per SIMD the kernel is built for (its register budget: 512 / waves, in steps of 8): the most at which the pair variants
-// keep a lane's whole path state -- ray, throughput, radiance, sum, generator, hit and light sample across the shadow walk -- in
-// registers.  At four (128 VGPRs, path_trace_kernel's budget, which parks part of that state in LDS and recomputes the rest)
-// every variant but PMODE 1 with the simple materials spilled 16 to 112 bytes per lane into scratch; at three none does.
-constexpr int RADIANCE_WAVES = 3;
-template <int GEOM, bool FULL, int PMODE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAVES, 8))) void radiance_query_kernel(
-    const KParams Kin, const float *__restrict__ origins, const float *__restrict__ dirs, uint32_t *__restrict__ rng_states, size_t n,
-    RadianceOut *__restrict__ out) {
-    // The parameters are read where they are used, through the kernarg segment (scalar loads that hit the constant cache), and
-    // each phase of the loop gets its own opaque copy of the pointer, as in path_trace_kernel: held in SGPRs across the loop, the
-    // ~110 dwords of the by-value copy are spilled into VGPR lanes, and from there into scratch.
-    (void)Kin;
-    const kparams_ptr kp0 = (kparams_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-    const KParams &K = kparams(kp0); // staging
-    extern __shared__ uint2 lds_raw[];
-    const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
-    CycleAcc cyc;
+// Where the first hit of sample 0 goes, as DEPTH / NORMAL / OBJECT_ID hold it (a miss: 1e30f, zeros, -1): the query writes it
+// straight into the ray's record, while the path is still running, so nothing of it stays in registers across the loop.
+struct FirstHitToRecord {
+    RadianceOut *out;
+    size_t i;
+    PT_DEV void operator()(float depth, f3 normal, int object_id) const {
+        RadianceOut *r = out + i;
+        r->depth = depth;
+        r->normal[0] = normal.x;
+        r->normal[1] = normal.y;
+        r->normal[2] = normal.z;
+        r->object_id = object_id;
+    }
+};
+
+// The samples of one chunk: the 64 lanes' rays (o0, d0; `live` lanes only) through phases [B]-[E] in lock step, K.spp times,
+// each lane's generator advanced in `rng`; returns the lane's sum of soft-clamped samples (avg_color of path_trace_kernel,
+// scene_kernels.cuh:171-176, before its division).  `first` takes the first hit of sample 0.  radiance_query_kernel and
+// probe_query_kernel (pt_probe.hip.h) are this loop in two frames; inlined, so each kernel keeps its own register allocation.
+template <int GEOM, bool FULL, int PMODE, class FirstHit>
+PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const LdsStack stk, CycleAcc &cyc, const int lane,
+                              const bool live, const f3 o0, const f3 d0, Rng &rng, const FirstHit first) {
+    f3 sum = mk3(0.0f); // avg_color of path_trace_kernel (scene_kernels.cuh:171-176)
+    for (int s = 0; s < kparams(kp0).spp; ++s) { // (wave-uniform)
+        // the sample's own copy of the ray: tracePath starts every sample from the caller's ray
+        f3 ro = o0, rd = d0;
+        bool ray_spec = true, prev_was_specular = true;
+        f3 throughput = mk3(1.0f), acc = mk3(0.0f);
+        int bounce = 0;
+        bool act = live;
+        while (__builtin_amdgcn_ballot_w64(act)) {
+            // ---- [B] closest hit, all lanes that have a path together
+            const KParams &KB = kparams(kp0);
+            int h_order = 0;
+            const Hit h = (PMODE == 1)   ? closest_hit_pairs(KB, PL, lane, act, ro, rd, h_order)
+                          : (PMODE == 2) ? closest_hit_pairs_dyn(KB, PL, lane, act, ro, rd)
+                          : (PMODE == 3) ? closest_hit_pairs_tlas(KB, PL, lane, act, ro, rd, cyc)
+                                         : closest_hit<GEOM>(KB, act, ro, rd, stk);
+            // ---- [C] first half of the shading
+            const KParams &KC = kparams(kp0);
+            bool end_path = false, shaded = false, want_shadow = false;
+            Surface hit;
+            hit.point = hit.normal = mk3(0.0f);
+            hit.t = 0.0f;
+            hit.front_face = true;
+            f3 L = mk3(0.0f), light_scale = mk3(0.0f), shadow_o = mk3(0.0f);
+            float pdf_sample = 1.0f, shadow_tmax = 0.0f, light_att = 1.0f;
+            if (act) {
+                if (h.mesh < 0) {
+                    if (s == 0 && bounce == 0) // first hit of the first sample (scene_kernels.cuh:181-193): HitInfo() defaults
+                        first(1e30f, mk3(0.0f), -1);
+                    if (KC.use_sky) { // sampleSky (render_utils.cuh:115-137): gradient, or the equirect map
+                        if (KC.env) {
+                            const float phi = det_atan2(rd.z, rd.x);
+                            const float theta = det_acos(max_(-1.0f, min_(1.0f, rd.y)));
+                            const float u = (phi + PI_F) * (1.0f / TWO_PI_F);
+                            const float v = theta * (1.0f / PI_F);
+                            acc = acc + throughput * tex2d_env(KC.env, KC.env_w, KC.env_h, u, v);
+                        } else {
+                            const float t = 0.5f * (rd.y + 1.0f);
+                            acc = acc + throughput * lerp(KC.sky_bottom, KC.sky_top, t);
+                        }
+                    } else {
+                        acc = acc + throughput * mk3(0.0f);
+                    }
+                    end_path = true;
+                } else {
+                    shaded = true;
+                    hit = make_surface(KC, h, ro, rd, nullptr, nullptr);
+                    if (s == 0 && bounce == 0)
+                        first(hit.t, hit.normal, h.mesh);
+                    const float4 m0 = KC.materials[h.mesh * 6 + 0], m2 = KC.materials[h.mesh * 6 + 2];
+                    if (!hit.front_face) { // Beer-Lambert on back faces (path_logic.cuh:823-829)
+                        const f3 T_unit = mk3(max_(1e-6f, m0.x), max_(1e-6f, m0.y), max_(1e-6f, m0.z));
+                        const f3 absorption = mk3(-det_log(T_unit.x), -det_log(T_unit.y), -det_log(T_unit.z));
+                        throughput = throughput * beerLambert(absorption, hit.t);
+                    }
+                    if (m2.x > 0.0f || m2.y > 0.0f || m2.z > 0.0f) {
+                        if (bounce == 0 || prev_was_specular)
+                            acc = acc + throughput * mk3(m2.x, m2.y, m2.z);
+                    }
+                    // light sample of next-event estimation (path_logic.cuh:305-382, 840)
+                    if (!ray_spec && KC.n_lights > 0) {
+                        float r = rng_uniform(rng);
+                        r = min_(r, 0.99999994f);
+                        const int light_index = (int)(r * (float)KC.n_lights);
+                        const LightRec light = load_light(KC.lights, light_index);
+                        const float pdf_pick = 1.0f / (float)KC.n_lights;
+                        float attenuation = 1.0f;
+                        float light_dist = 1e30f;
+                        const f3 light_radiance = light.color * light.intensity;
+                        if (light.type == 1) {
+                            L = -light.direction;
+                            pdf_sample = pdf_pick;
+                        } else {
+                            const f3 toLight = light.position - hit.point;
+                            const float light_dist_sq = dot(toLight, toLight);
+                            light_dist = sqrt_ieee(light_dist_sq);
+                            if (light.radius <= 0.0f) {
+                                L = toLight / light_dist;
+                                pdf_sample = pdf_pick;
+                            } else {
+                                float sin_theta_max_sq = (light.radius * light.radius) / light_dist_sq;
+                                sin_theta_max_sq = min_(sin_theta_max_sq, 0.9999f);
+                                const float cos_theta_max = sqrt_ieee(1.0f - sin_theta_max_sq);
+                                L = sample_cone_direction(rng, toLight / light_dist, cos_theta_max);
+                                const float solid_angle = TWO_PI_F * (1.0f - cos_theta_max);
+                                pdf_sample = (solid_angle > 1e-6f) ? (pdf_pick / solid_angle) : pdf_pick;
+                            }
+                            attenuation = attenuate(light_dist, light.range);
+                            if (light.type == 2) {
+                                const float theta = dot(L, -light.direction);
+                                const float epsilon = light.inner - light.outer;
+                                float spotIntensity;
+                                if (epsilon <= 1e-6f)
+                                    spotIntensity = (theta >= light.outer) ? 1.0f : 0.0f;
+                                else
+                                    spotIntensity = clampf((theta - light.outer) / epsilon, 0.0f, 1.0f);
+                                attenuation *= spotIntensity;
+                            }
+                        }
+                        const f3 shadow_offset = dot(hit.normal, L) > 0.0f ? hit.normal * 1e-4f : -hit.normal * 1e-4f;
+                        shadow_o = hit.point + shadow_offset;
+                        shadow_tmax = light_dist - 1e-3f;
+                        // bsdf * light_radiance * attenuation / pdf: the last three factors are kept apart so the product is
+                        // formed in the reference's order
+                        light_scale = light_radiance;
+                        light_att = attenuation;
+                        want_shadow = true;
+                    }
+                }
+            }
+            // ---- [C2] the light sample's value, before its visibility is known (path_logic.cuh:840-867): what a visible
+            // sample adds to `acc`, formed from the same operands in the same order as in the reference.  A sample that adds
+            // nothing either way (outside a spot cone, BSDF zero below the horizon) is not walked; the frame does not walk it.
+            const KParams &KC2 = kparams(kp0);
+            bool lit = false;
+            f3 lit_now = mk3(0.0f);
+            if (want_shadow) {
+                const Material mat = load_material(KC2.materials, h.mesh);
+                const f3 V = -rd;
+                const f3 bsdf = evaluateBSDF<FULL>(hit, mat, L, V);
+                if (pdf_sample > 0.0f) {
+                    f3 direct = bsdf * light_scale * light_att / pdf_sample;
+                    direct = clamp_vector_soft(direct, 500.0f);
+                    if (direct.x > 0.0f || direct.y > 0.0f || direct.z > 0.0f) {
+                        const float pdf_brdf = material_pdf<FULL>(hit, mat, V, L);
+                        const float wgt = mis_weight(pdf_sample, pdf_brdf);
+                        lit_now = throughput * direct * wgt;
+                        lit = true;
+                    }
+                }
+            }
+            // ---- [D] shadow rays, all lanes that have one together (bvh_any_hit_tlas); the contribution is added once its
+            // visibility is known and before anything else touches the path's radiance
+            const KParams &KD = kparams(kp0);
+            if (__builtin_amdgcn_ballot_w64(lit)) {
+                const bool in_shadow = (PMODE == 1)   ? any_hit_pairs(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
+                                       : (PMODE == 2) ? any_hit_pairs_dyn(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
+                                       : (PMODE == 3) ? any_hit_pairs_tlas(KD, PL, lane, lit, shadow_o, L, shadow_tmax, cyc)
+                                                      : any_hit<GEOM>(KD, lit, shadow_o, L, shadow_tmax, stk);
+                if (lit && !in_shadow)
+                    acc = acc + lit_now;
+            }
+            // ---- [E] second half of the shading
+            const KParams &KE = kparams(kp0);
+            if (shaded) {
+                const Material mat = load_material(KE.materials, h.mesh);
+                f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
+                bool is_specular = false;
+                if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular)) {
+                    end_path = true;
+                } else {
+                    prev_was_specular = is_specular;
+                    bool killed = false;
+                    if (bounce >= 2) { // Russian roulette (path_logic.cuh:871-880)
+                        const float p = max_(0.05f, min_(0.95f, max_(throughput.x, max_(throughput.y, throughput.z))));
+                        if (rng_uniform(rng) > p)
+                            killed = true;
+                        else
+                            throughput = throughput / p;
+                    }
+                    if (killed) {
+                        end_path = true;
+                    } else {
+                        throughput = throughput * att;
+                        throughput = clamp_vector_soft(throughput, 50.0f);
+                        const f3 off = hit.normal * 1e-4f;
+                        ro = (dot(scatter_dir, hit.normal) > 0.0f) ? (hit.point + off) : (hit.point - off);
+                        rd = scatter_dir;
+                        ray_spec = is_specular;
+                        ++bounce;
+                        if (bounce >= KE.max_depth)
+                            end_path = true;
+                    }
+                }
+            }
+            if (act && end_path) { // the sample is complete (scene_kernels.cuh:170-171)
+                acc = clamp_vector_soft(acc, 100.0f);
+                sum = sum + acc;
+                act = false;
+            }
+        }
+    }
+    return sum;
+}
+
+// ray_query_kernel's LDS carve and staging by PMODE (pt_query.hip.h), for the two kernels below; the caller synchronises.
+template <int PMODE> PT_DEV PairLds stage_pair_lds(const KParams &K, uint2 *lds_raw, const int lane) {
     PairLds PL{};
     if (PMODE == 1) {
         // ray_query_kernel's staging: the leaf's triangle packets (PAIR_PAD float4 apart per mesh), mesh table, heads
@@ -80,6 +270,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
             PL.meshbox[2 * i + 1] = hb;
         }
     }
+    return PL;
+}
+
+// Waves per SIMD the kernel is built for (its register budget: 512 / waves, in steps of 8): the most at which the pair variants
+// keep a lane's whole path state -- ray, throughput, radiance, sum, generator, hit and light sample across the shadow walk -- in
+// registers.  At four (128 VGPRs, path_trace_kernel's budget, which parks part of that state in LDS and recomputes the rest)
+// every variant but PMODE 1 with the simple materials spilled 16 to 112 bytes per lane into scratch; at three none does.
+constexpr int RADIANCE_WAVES = 3;
+template <int GEOM, bool FULL, int PMODE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAVES, 8))) void radiance_query_kernel(
+    const KParams Kin, const float *__restrict__ origins, const float *__restrict__ dirs, uint32_t *__restrict__ rng_states, size_t n,
+    RadianceOut *__restrict__ out) {
+    // The parameters are read where they are used, through the kernarg segment (scalar loads that hit the constant cache), and
+    // each phase of the loop gets its own opaque copy of the pointer, as in path_trace_kernel: held in SGPRs across the loop, the
+    // ~110 dwords of the by-value copy are spilled into VGPR lanes, and from there into scratch.
+    (void)Kin;
+    const kparams_ptr kp0 = (kparams_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    const KParams &K = kparams(kp0); // staging
+    extern __shared__ uint2 lds_raw[];
+    const int lane = threadIdx.x;
+    LdsStack stk{lds_raw + lane};
+    CycleAcc cyc;
+    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
     PL.cyc = &cyc;
     PL.stat_bounce = 0;
     __syncthreads();
@@ -100,200 +313,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
             rng.v3 = st[4];
             rng.v4 = st[5];
         }
-        f3 sum = mk3(0.0f); // avg_color of path_trace_kernel (scene_kernels.cuh:171-176)
-        for (int s = 0; s < kparams(kp0).spp; ++s) { // (wave-uniform)
-            // the sample's own copy of the ray: tracePath starts every sample from the caller's ray
-            f3 ro = o0, rd = d0;
-            bool ray_spec = true, prev_was_specular = true;
-            f3 throughput = mk3(1.0f), acc = mk3(0.0f);
-            int bounce = 0;
-            bool act = live;
-            while (__builtin_amdgcn_ballot_w64(act)) {
-                // ---- [B] closest hit, all lanes that have a path together
-                const KParams &KB = kparams(kp0);
-                int h_order = 0;
-                const Hit h = (PMODE == 1)   ? closest_hit_pairs(KB, PL, lane, act, ro, rd, h_order)
-                              : (PMODE == 2) ? closest_hit_pairs_dyn(KB, PL, lane, act, ro, rd)
-                              : (PMODE == 3) ? closest_hit_pairs_tlas(KB, PL, lane, act, ro, rd, cyc)
-                                             : closest_hit<GEOM>(KB, act, ro, rd, stk);
-                // ---- [C] first half of the shading
-                const KParams &KC = kparams(kp0);
-                bool end_path = false, shaded = false, want_shadow = false;
-                Surface hit;
-                hit.point = hit.normal = mk3(0.0f);
-                hit.t = 0.0f;
-                hit.front_face = true;
-                f3 L = mk3(0.0f), light_scale = mk3(0.0f), shadow_o = mk3(0.0f);
-                float pdf_sample = 1.0f, shadow_tmax = 0.0f, light_att = 1.0f;
-                if (act) {
-                    if (h.mesh < 0) {
-                        if (s == 0 && bounce == 0) { // first hit of the first sample (scene_kernels.cuh:181-193): HitInfo() defaults
-                            RadianceOut *r = out + i;
-                            r->depth = 1e30f;
-                            r->normal[0] = 0.0f;
-                            r->normal[1] = 0.0f;
-                            r->normal[2] = 0.0f;
-                            r->object_id = -1;
-                        }
-                        if (KC.use_sky) { // sampleSky (render_utils.cuh:115-137): gradient, or the equirect map
-                            if (KC.env) {
-                                const float phi = det_atan2(rd.z, rd.x);
-                                const float theta = det_acos(max_(-1.0f, min_(1.0f, rd.y)));
-                                const float u = (phi + PI_F) * (1.0f / TWO_PI_F);
-                                const float v = theta * (1.0f / PI_F);
-                                acc = acc + throughput * tex2d_env(KC.env, KC.env_w, KC.env_h, u, v);
-                            } else {
-                                const float t = 0.5f * (rd.y + 1.0f);
-                                acc = acc + throughput * lerp(KC.sky_bottom, KC.sky_top, t);
-                            }
-                        } else {
-                            acc = acc + throughput * mk3(0.0f);
-                        }
-                        end_path = true;
-                    } else {
-                        shaded = true;
-                        hit = make_surface(KC, h, ro, rd, nullptr, nullptr);
-                        if (s == 0 && bounce == 0) {
-                            RadianceOut *r = out + i;
-                            r->depth = hit.t;
-                            r->normal[0] = hit.normal.x;
-                            r->normal[1] = hit.normal.y;
-                            r->normal[2] = hit.normal.z;
-                            r->object_id = h.mesh;
-                        }
-                        const float4 m0 = KC.materials[h.mesh * 6 + 0], m2 = KC.materials[h.mesh * 6 + 2];
-                        if (!hit.front_face) { // Beer-Lambert on back faces (path_logic.cuh:823-829)
-                            const f3 T_unit = mk3(max_(1e-6f, m0.x), max_(1e-6f, m0.y), max_(1e-6f, m0.z));
-                            const f3 absorption = mk3(-det_log(T_unit.x), -det_log(T_unit.y), -det_log(T_unit.z));
-                            throughput = throughput * beerLambert(absorption, hit.t);
-                        }
-                        if (m2.x > 0.0f || m2.y > 0.0f || m2.z > 0.0f) {
-                            if (bounce == 0 || prev_was_specular)
-                                acc = acc + throughput * mk3(m2.x, m2.y, m2.z);
-                        }
-                        // light sample of next-event estimation (path_logic.cuh:305-382, 840)
-                        if (!ray_spec && KC.n_lights > 0) {
-                            float r = rng_uniform(rng);
-                            r = min_(r, 0.99999994f);
-                            const int light_index = (int)(r * (float)KC.n_lights);
-                            const LightRec light = load_light(KC.lights, light_index);
-                            const float pdf_pick = 1.0f / (float)KC.n_lights;
-                            float attenuation = 1.0f;
-                            float light_dist = 1e30f;
-                            const f3 light_radiance = light.color * light.intensity;
-                            if (light.type == 1) {
-                                L = -light.direction;
-                                pdf_sample = pdf_pick;
-                            } else {
-                                const f3 toLight = light.position - hit.point;
-                                const float light_dist_sq = dot(toLight, toLight);
-                                light_dist = sqrt_ieee(light_dist_sq);
-                                if (light.radius <= 0.0f) {
-                                    L = toLight / light_dist;
-                                    pdf_sample = pdf_pick;
-                                } else {
-                                    float sin_theta_max_sq = (light.radius * light.radius) / light_dist_sq;
-                                    sin_theta_max_sq = min_(sin_theta_max_sq, 0.9999f);
-                                    const float cos_theta_max = sqrt_ieee(1.0f - sin_theta_max_sq);
-                                    L = sample_cone_direction(rng, toLight / light_dist, cos_theta_max);
-                                    const float solid_angle = TWO_PI_F * (1.0f - cos_theta_max);
-                                    pdf_sample = (solid_angle > 1e-6f) ? (pdf_pick / solid_angle) : pdf_pick;
-                                }
-                                attenuation = attenuate(light_dist, light.range);
-                                if (light.type == 2) {
-                                    const float theta = dot(L, -light.direction);
-                                    const float epsilon = light.inner - light.outer;
-                                    float spotIntensity;
-                                    if (epsilon <= 1e-6f)
-                                        spotIntensity = (theta >= light.outer) ? 1.0f : 0.0f;
-                                    else
-                                        spotIntensity = clampf((theta - light.outer) / epsilon, 0.0f, 1.0f);
-                                    attenuation *= spotIntensity;
-                                }
-                            }
-                            const f3 shadow_offset = dot(hit.normal, L) > 0.0f ? hit.normal * 1e-4f : -hit.normal * 1e-4f;
-                            shadow_o = hit.point + shadow_offset;
-                            shadow_tmax = light_dist - 1e-3f;
-                            // bsdf * light_radiance * attenuation / pdf: the last three factors are kept apart so the product is
-                            // formed in the reference's order
-                            light_scale = light_radiance;
-                            light_att = attenuation;
-                            want_shadow = true;
-                        }
-                    }
-                }
-                // ---- [C2] the light sample's value, before its visibility is known (path_logic.cuh:840-867): what a visible
-                // sample adds to `acc`, formed from the same operands in the same order as in the reference.  A sample that adds
-                // nothing either way (outside a spot cone, BSDF zero below the horizon) is not walked; the frame does not walk it.
-                const KParams &KC2 = kparams(kp0);
-                bool lit = false;
-                f3 lit_now = mk3(0.0f);
-                if (want_shadow) {
-                    const Material mat = load_material(KC2.materials, h.mesh);
-                    const f3 V = -rd;
-                    const f3 bsdf = evaluateBSDF<FULL>(hit, mat, L, V);
-                    if (pdf_sample > 0.0f) {
-                        f3 direct = bsdf * light_scale * light_att / pdf_sample;
-                        direct = clamp_vector_soft(direct, 500.0f);
-                        if (direct.x > 0.0f || direct.y > 0.0f || direct.z > 0.0f) {
-                            const float pdf_brdf = material_pdf<FULL>(hit, mat, V, L);
-                            const float wgt = mis_weight(pdf_sample, pdf_brdf);
-                            lit_now = throughput * direct * wgt;
-                            lit = true;
-                        }
-                    }
-                }
-                // ---- [D] shadow rays, all lanes that have one together (bvh_any_hit_tlas); the contribution is added once its
-                // visibility is known and before anything else touches the path's radiance
-                const KParams &KD = kparams(kp0);
-                if (__builtin_amdgcn_ballot_w64(lit)) {
-                    const bool in_shadow = (PMODE == 1)   ? any_hit_pairs(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
-                                           : (PMODE == 2) ? any_hit_pairs_dyn(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
-                                           : (PMODE == 3) ? any_hit_pairs_tlas(KD, PL, lane, lit, shadow_o, L, shadow_tmax, cyc)
-                                                          : any_hit<GEOM>(KD, lit, shadow_o, L, shadow_tmax, stk);
-                    if (lit && !in_shadow)
-                        acc = acc + lit_now;
-                }
-                // ---- [E] second half of the shading
-                const KParams &KE = kparams(kp0);
-                if (shaded) {
-                    const Material mat = load_material(KE.materials, h.mesh);
-                    f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
-                    bool is_specular = false;
-                    if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular)) {
-                        end_path = true;
-                    } else {
-                        prev_was_specular = is_specular;
-                        bool killed = false;
-                        if (bounce >= 2) { // Russian roulette (path_logic.cuh:871-880)
-                            const float p = max_(0.05f, min_(0.95f, max_(throughput.x, max_(throughput.y, throughput.z))));
-                            if (rng_uniform(rng) > p)
-                                killed = true;
-                            else
-                                throughput = throughput / p;
-                        }
-                        if (killed) {
-                            end_path = true;
-                        } else {
-                            throughput = throughput * att;
-                            throughput = clamp_vector_soft(throughput, 50.0f);
-                            const f3 off = hit.normal * 1e-4f;
-                            ro = (dot(scatter_dir, hit.normal) > 0.0f) ? (hit.point + off) : (hit.point - off);
-                            rd = scatter_dir;
-                            ray_spec = is_specular;
-                            ++bounce;
-                            if (bounce >= KE.max_depth)
-                                end_path = true;
-                        }
-                    }
-                }
-                if (act && end_path) { // the sample is complete (scene_kernels.cuh:170-171)
-                    acc = clamp_vector_soft(acc, 100.0f);
-                    sum = sum + acc;
-                    act = false;
-                }
-            }
-        }
+        const FirstHitToRecord first{out, i};
+        const f3 sum = trace_chunk_samples<GEOM, FULL, PMODE>(kp0, PL, stk, cyc, lane, live, o0, d0, rng, first);
         if (live) {
             uint32_t *st = rng_states + i * 6;
             st[0] = rng.d;

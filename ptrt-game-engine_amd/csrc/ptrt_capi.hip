@@ -18,6 +18,7 @@
 #include "pt_wireframe.hip.h"
 #include "pt_query.hip.h"
 #include "pt_radiance.hip.h"
+#include "pt_probe.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -1238,6 +1239,35 @@ int dispatch_radiance(ptrt_ctx *c, int geom, int pmode, const pt::KParams &K, si
     }
 }
 
+// probe_query_kernel (pt_probe.hip.h) over n_probes probes of n_dirs rays each: run_radiance's launch with the grid striding
+// over probes, one wave per probe.
+template <int GEOM, bool FULL, int PMODE>
+int run_probes(ptrt_ctx *c, const pt::KParams &K, size_t lds, const float *pos, int n_probes, const float *d, int n_dirs,
+               uint32_t *rng, float max_distance, pt::ProbeOut *out) {
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt::probe_query_kernel<GEOM, FULL, PMODE>, 64, lds));
+    if (c->persist > 0) // option "persist": persistent waves per CU
+        per_cu = c->persist;
+    const size_t slots = (size_t)(c->n_cus > 0 ? c->n_cus : 1) * (size_t)(per_cu > 0 ? per_cu : 1);
+    const unsigned grid = (unsigned)((size_t)n_probes < slots ? (size_t)n_probes : slots);
+    hipLaunchKernelGGL((pt::probe_query_kernel<GEOM, FULL, PMODE>), dim3(grid), dim3(64), lds, c->stream, K, pos, n_probes, d, n_dirs,
+                       rng, max_distance, out);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+template <bool FULL>
+int dispatch_probes(ptrt_ctx *c, int geom, int pmode, const pt::KParams &K, size_t lds, const float *pos, int n_probes,
+                    const float *d, int n_dirs, uint32_t *rng, float max_distance, pt::ProbeOut *out) {
+    switch (pmode ? pmode : -geom) { // (as dispatch_radiance)
+    case 1: return run_probes<0, FULL, 1>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
+    case 2: return run_probes<1, FULL, 2>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
+    case 3: return run_probes<2, FULL, 3>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
+    case 0: return run_probes<0, FULL, 0>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
+    case -1: return run_probes<1, FULL, 0>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
+    default: return run_probes<2, FULL, 0>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
+    }
+}
+
 extern "C" {
 
 int ptrt_query_radiance(ptrt_ctx *c, const float *origins, const float *directions, uint32_t *rng_states, int n, int samples,
@@ -1289,6 +1319,63 @@ int ptrt_query_radiance(ptrt_ctx *c, const float *origins, const float *directio
     pt::RadianceOut *o = reinterpret_cast<pt::RadianceOut *>(out);
     return full ? dispatch_radiance<true>(c, geom, pmode, K, lds, origins, directions, rng_states, rays, o)
                 : dispatch_radiance<false>(c, geom, pmode, K, lds, origins, directions, rng_states, rays, o);
+}
+
+int ptrt_query_probes(ptrt_ctx *c, const float *d_positions, int n_probes, const float *d_directions, int n_dirs,
+                      uint32_t *d_rng_states, int samples, int max_depth, float max_distance, ptrt_probe *d_out) {
+    static_assert(sizeof(pt::ProbeOut) == sizeof(ptrt_probe) && sizeof(ptrt_probe) == 128, "ProbeOut must mirror ptrt_probe");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: bad context");
+    if (n_probes < 0 || n_dirs < 1 || !d_positions || !d_directions || !d_rng_states || !d_out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: bad argument (n_probes %d, n_dirs %d, positions %p, directions %p, rng_states %p, out %p)",
+                    n_probes, n_dirs, (const void *)d_positions, (const void *)d_directions, (const void *)d_rng_states, (const void *)d_out);
+    if (samples < 1 || max_depth < 1 || samples > 32767 || max_depth > 32767) // (ptrt_render's range)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: samples=%d max_depth=%d (1..32767)", samples, max_depth);
+    if (!(max_distance > 0.0f) || !std::isfinite(max_distance))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: max_distance=%g (positive and finite)", (double)max_distance);
+    if (!c->have_geometry || !c->have_materials)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_probes: %s not uploaded", c->have_geometry ? "materials" : "geometry");
+    if (c->n_materials < c->n_meshes)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_probes: %d materials for %d meshes", c->n_materials, c->n_meshes);
+    if (n_probes == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    // byte counts in size_t: n_probes * n_dirs rays is below 2^62 and fits; times 24 bytes of state it need not
+    const size_t probes = (size_t)n_probes, ndirs = (size_t)n_dirs, rays = probes * ndirs;
+    if (rays > SIZE_MAX / 24)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: %d probes x %d directions: the states' byte count overflows", n_probes, n_dirs);
+    const char *bad = !device_span(c, d_positions, probes * 12)                  ? "positions"
+                      : !device_span(c, d_directions, ndirs * 12)                ? "directions"
+                      : !device_span(c, d_rng_states, rays * 24)                 ? "rng_states"
+                      : !device_span(c, d_out, probes * sizeof(ptrt_probe))      ? "out"
+                                                                                 : nullptr;
+    if (bad)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: %s is not %zu bytes of device memory on device %d", bad,
+                    bad[0] == 'p' ? probes * 12 : bad[0] == 'd' ? ndirs * 12 : bad[0] == 'r' ? rays * 24 : probes * sizeof(ptrt_probe),
+                    c->device);
+    pt::KParams K = make_params(c);
+    K.spp = samples;
+    K.max_depth = max_depth;
+    // (the context's own per-pixel buffers are no business of the query's)
+    K.rng = nullptr;
+    K.accum = K.normal = K.depth = nullptr;
+    K.object_id = nullptr;
+    K.rgb8 = nullptr;
+    const int geom = pick_geom(c);
+    const int pmode = pair_mode(c, geom, false);
+    const bool full = c->mats_full || c->force_full;
+    const size_t lds = trace_lds_bytes(c, geom, pmode);
+    // a path frame that follows is ordered behind the query on the stream (option "pipeline"), as behind ptrt_query_radiance
+    c->touched = true;
+    c->query_pmode = pmode;
+    c->pm1_lane_groups_eff = pmode == 1 ? K.pm1_groups : 0;
+    if (pmode == 3)
+        if (int rc = refresh_tlas_heads(c, false))
+            return rc;
+    pt::ProbeOut *o = reinterpret_cast<pt::ProbeOut *>(d_out);
+    return full ? dispatch_probes<true>(c, geom, pmode, K, lds, d_positions, n_probes, d_directions, n_dirs, d_rng_states, max_distance, o)
+                : dispatch_probes<false>(c, geom, pmode, K, lds, d_positions, n_probes, d_directions, n_dirs, d_rng_states, max_distance, o);
 }
 
 int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins, float *d_directions) {

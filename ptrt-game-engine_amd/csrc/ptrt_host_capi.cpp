@@ -401,6 +401,13 @@ int hs_query_radiance(void *s, const void *d_origins, const void *d_dirs, void *
                                                   static_cast<ptrt_radiance *>(d_out)));
     return 0;
 }
+int hs_query_probes(void *s, const void *d_positions, int n_probes, const void *d_dirs, int n_dirs, void *d_rng_states, int samples,
+                    int max_depth, float max_distance, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryProbes(static_cast<const float *>(d_positions), n_probes, static_cast<const float *>(d_dirs),
+                                                n_dirs, static_cast<uint32_t *>(d_rng_states), samples, max_depth, max_distance,
+                                                static_cast<ptrt_probe *>(d_out)));
+    return 0;
+}
 int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
     HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;

@@ -1061,6 +1061,18 @@ class Scene {
                                   max_depth > 0 ? max_depth : perfSettings.maxBounceDepth, d_out),
               "Radiance query failed");
     }
+    // Light probes (ptrt_query_probes): probe p sends n_dirs rays from d_positions[p] along the shared d_dirs, ray (p, k) with
+    // generator state p * n_dirs + k (advanced in place); d_out gets one 128-byte ptrt_probe per probe -- radiance on the nine
+    // spherical harmonics of bands 0-2, mean hit distance (clamped to max_distance), its square and the hit fraction, all means
+    // over the directions.  Commits what queryRadiance commits.  max_depth <= 0: the frame's bounce depth.
+    void queryProbes(const float *d_positions, int n_probes, const float *d_dirs, int n_dirs, uint32_t *d_rng_states, int samples,
+                     int max_depth, float max_distance, ptrt_probe *d_out) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_query_probes(ctx, d_positions, n_probes, d_dirs, n_dirs, d_rng_states, samples,
+                                max_depth > 0 ? max_depth : perfSettings.maxBounceDepth, max_distance, d_out),
+              "Probe query failed");
+    }
     // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
     // tile rows * width * 3 floats each, in the order of the colour buffer.
     void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {

@@ -117,6 +117,12 @@ class Radiance(C.Structure):
     _fields_ = [("radiance", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("object_id", C.c_int32)]
 
 
+class Probe(C.Structure):
+    """`ptrt_probe`: one light probe's answer from ptrt_query_probes."""
+    _fields_ = [("sh", (C.c_float * 3) * 9), ("mean_distance", C.c_float), ("mean_distance_sq", C.c_float),
+                ("hit_fraction", C.c_float), ("reserved", C.c_float * 2)]
+
+
 class Stats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64),
                 ("shadow_rays_walked", C.c_uint64)]
@@ -128,6 +134,9 @@ HIT_DTYPE = np.dtype([("hit", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("norma
 assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
 RADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("object_id", "<i4")])
 assert RADIANCE_DTYPE.itemsize == C.sizeof(Radiance) == 32
+PROBE_DTYPE = np.dtype([("sh", "<f4", (9, 3)), ("mean_distance", "<f4"), ("mean_distance_sq", "<f4"), ("hit_fraction", "<f4"),
+                        ("reserved", "<f4", 2)])
+assert PROBE_DTYPE.itemsize == C.sizeof(Probe) == 128
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
@@ -168,6 +177,7 @@ _sig("ptrt_trace_rays", C.c_int, _vp, _fp, _fp, C.c_int, _vp)
 _sig("ptrt_render_wireframe", C.c_int, _vp, C.c_float, _vp, C.c_int)
 _sig("ptrt_query_rays", C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp)
 _sig("ptrt_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("ptrt_query_probes", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
@@ -293,6 +303,7 @@ _sig("hs_render_wireframe_to_host", C.c_int, _vp, _vp, C.c_float)
 _sig("hs_query_closest", C.c_int, _vp, _vp, _vp, C.c_int, _vp)
 _sig("hs_query_occluded", C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp)
 _sig("hs_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("hs_query_probes", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -385,6 +396,19 @@ def radiance_fields(records):
     for name, (a, b, is_f) in RADIANCE_COLUMNS.items():
         col = (records if is_f else i)[:, a:b]
         out[name] = col[:, 0] if b - a == 1 else col
+    return out
+
+
+# columns of the (n, 32) float32 rows of Scene.query_probes: the fields of ptrt_probe / PROBE_DTYPE
+PROBE_COLUMNS = dict(sh=(0, 27), mean_distance=(27, 28), mean_distance_sq=(28, 29), hit_fraction=(29, 30), reserved=(30, 32))
+
+
+def probe_fields(probes):
+    """Named views of query_probes's (n, 32) float32 tensor: sh as (n, 9, 3) -- coefficient, colour channel --, scalars as (n,)."""
+    out = {}
+    for name, (a, b) in PROBE_COLUMNS.items():
+        col = probes[:, a:b]
+        out[name] = col.reshape(-1, 9, 3) if name == "sh" else col[:, 0] if b - a == 1 else col
     return out
 
 
@@ -945,6 +969,39 @@ class Scene:
             0 if max_depth is None else int(max_depth), _vp(out.data_ptr()))))
         return out
 
+    def query_probes(self, positions, directions, rng_states, samples=1, max_depth=None, max_distance=1e30, out=None):
+        """Light probes: probe p sends one ray from positions[p] along every direction (one set for all probes, used as given,
+        not normalised), ray (p, k) with generator state p * k_dirs + k, `samples` paths of `max_depth` bounces each (None: the
+        scene's bounce depth).  torch tensors on this scene's device, contiguous, read in place: positions (n, 3) and
+        directions (k, 3) float32, rng_states (n * k, 6) int32 (or uint32) ADVANCED IN PLACE.  Returns an (n, 32) float32
+        tensor, one 128-byte `ptrt_probe` per row (`probe_fields` names the columns): the means over the directions of
+        Y_i(d) * radiance for the nine spherical harmonics of bands 0-2 (columns 3 * i + channel), of the first-hit distance
+        clamped to `max_distance` (27), of its square (28), and the fraction of rays that hit (29); `out` takes such a tensor
+        to write into.  `ptrt_amd.probes` has direction sets, grids and the irradiance reconstruction.  No synchronisation."""
+        self._device_tensor("query_probes: positions", positions, 3, "torch.float32")
+        self._device_tensor("query_probes: directions", directions, 3, "torch.float32")
+        self._device_tensor("query_probes: rng_states", rng_states, 6, "torch.int32|torch.uint32")
+        n, k = positions.shape[0], directions.shape[0]
+        if k < 1:
+            raise ValueError("query_probes: no directions")
+        if rng_states.shape[0] != n * k:
+            raise ValueError(f"query_probes: {n} probes x {k} directions need {n * k} states, got {rng_states.shape[0]}")
+        if n >= 2 ** 31 or k >= 2 ** 31:
+            raise ValueError(f"query_probes: {n} probes x {k} directions (at most 2^31 - 1 of each per call)")
+        import torch
+        if out is None:
+            out = torch.empty((n, 32), dtype=torch.float32, device=positions.device)
+        else:
+            self._device_tensor("query_probes: out", out, 32, "torch.float32")
+            if out.shape[0] != n:
+                raise ValueError(f"query_probes: out has {out.shape[0]} rows for {n} probes")
+        if n == 0:
+            return out
+        self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_probes(
+            self._h, _vp(positions.data_ptr()), n, _vp(directions.data_ptr()), k, _vp(rng_states.data_ptr()), int(samples),
+            0 if max_depth is None else int(max_depth), float(max_distance), _vp(out.data_ptr()))))
+        return out
+
     def camera_rays(self, frame, sample=0):
         """(origins, directions): (rows * width, 3) float32 tensors on this scene's device holding the primary rays
         render_to_device gives sample `sample` of frame `frame`, in the order of `read(BUF_ACCUM)` (ptrt_camera_rays; pinhole
@@ -1053,4 +1110,4 @@ class TileFarm:
             pass
 
 
-from . import cameras, scenes  # noqa: E402,F401
+from . import cameras, probes, scenes  # noqa: E402,F401
