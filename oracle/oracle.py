@@ -108,6 +108,39 @@ def scatter_n(mats, items):
     return out
 
 
+RADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("object_id", "<i4")])
+# PathVertexLog of ptrt_oracle.cpp: one vertex of a path.  Fields a vertex did not reach stay 0 (light_index -1).
+PATH_LOG_DTYPE = np.dtype([
+    ("visited", "<i4"), ("state_before", "<u4", 6), ("ray_origin", "<f4", 3), ("ray_dir", "<f4", 3), ("ray_specular", "<i4"),
+    ("hit", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("mesh_index", "<i4"), ("front_face", "<i4"),
+    ("throughput_before", "<f4", 3), ("throughput_absorbed", "<f4", 3), ("throughput_after", "<f4", 3),
+    ("emission_added", "<i4"), ("light_sampled", "<i4"), ("light_index", "<i4"), ("L", "<f4", 3), ("pdf_sample", "<f4"),
+    ("light_dist", "<f4"), ("shadowed", "<i4"), ("contribution", "<f4", 3), ("pdf_brdf", "<f4"), ("w", "<f4"),
+    ("scatter_ok", "<i4"), ("scatter_dir", "<f4", 3), ("attenuation", "<f4", 3), ("scatter_specular", "<i4"),
+    ("roulette", "<i4"), ("p", "<f4"), ("u", "<f4"), ("survived", "<i4"), ("accumulated", "<f4", 3),
+    ("state_after", "<u4", 6)])
+lib.oracle_trace_paths.argtypes = [C.c_void_p, _fp, _fp, _up, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+lib.oracle_trace_paths.restype = C.c_int
+lib.oracle_path_log_bytes.restype = C.c_int
+assert RADIANCE_DTYPE.itemsize == 32 and PATH_LOG_DTYPE.itemsize == lib.oracle_path_log_bytes()
+
+
+def trace_paths(scene_desc_ptr, origins, directions, states, samples=1, max_depth=4, log=False):
+    """tracePath for a caller's rays, the sample loop of ptrt_query_radiance: `states` (n, 6) uint32 advance IN PLACE.
+    Returns (n,) RADIANCE_DTYPE records, and with `log` an (n, samples, max_depth) PATH_LOG_DTYPE array beside them."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    assert d.shape[0] == n and states.shape == (n, 6) and states.dtype == np.uint32 and states.flags.c_contiguous
+    out = np.zeros(n, RADIANCE_DTYPE)
+    lg = np.zeros((n, samples, max_depth), PATH_LOG_DTYPE) if log else None
+    rc = lib.oracle_trace_paths(C.cast(scene_desc_ptr, C.c_void_p), _f(o), _f(d), _u(states), n, samples, max_depth,
+                                out.ctypes.data_as(C.c_void_p), lg.ctypes.data_as(C.c_void_p) if log else None)
+    if rc != 0:
+        raise RuntimeError(f"oracle_trace_paths failed ({rc}); -2 means the CPU lacks FMA")
+    return (out, lg) if log else out
+
+
 def render(scene_desc_ptr, width, height, spp, max_depth, frame_count, blue_noise, rng, tile_y0=0, tile_rows=0,
            threads=1):
     """path_trace_kernel on the CPU.  `rng` (rows*W,6) uint32 is advanced in place.

@@ -968,9 +968,45 @@ float material_pdf(const HitInfo &hit, const MaterialProps &mat, const V3 &V, co
 // ---------------------------------------------------------------------------
 // next-event estimation (path_logic.cuh:305-393)
 // ---------------------------------------------------------------------------
+// One vertex of a path as oracle_trace_paths logs it: 4-byte fields only, mirrored by oracle.py PATH_LOG_DTYPE.  Fields a
+// vertex did not reach stay 0 (light_index -1).
+struct PathVertexLog {
+    int32_t visited;
+    uint32_t state_before[6];
+    float ray_origin[3], ray_dir[3];
+    int32_t ray_specular;
+    int32_t hit;
+    float t, point[3], normal[3];
+    int32_t mesh_index, front_face;
+    float throughput_before[3], throughput_absorbed[3], throughput_after[3];
+    int32_t emission_added;
+    int32_t light_sampled, light_index;
+    float L[3], pdf_sample, light_dist;
+    int32_t shadowed;
+    float contribution[3], pdf_brdf, w;
+    int32_t scatter_ok;
+    float scatter_dir[3], attenuation[3];
+    int32_t scatter_specular;
+    int32_t roulette;
+    float p, u;
+    int32_t survived;
+    float accumulated[3];
+    uint32_t state_after[6];
+};
+inline void log3(float *o, const V3 &v) {
+    o[0] = v.x;
+    o[1] = v.y;
+    o[2] = v.z;
+}
+inline void log_state(uint32_t *o, const Xorwow &s) {
+    o[0] = s.d;
+    for (int k = 0; k < 5; ++k)
+        o[1 + k] = s.v[k];
+}
+
 V3 sample_direct_lighting_with_mat(const HitInfo &hit, const MaterialProps &mat, const Ray &ray_in,
                                    const ptrt_scene_desc &S, Xorwow &rng, V3 &out_L, float &out_pdf,
-                                   Counters &cnt) {
+                                   Counters &cnt, PathVertexLog *lg = nullptr) {
     const int nLights = S.light_count;
     if (nLights == 0) {
         out_L = V3(0.0f);
@@ -1040,6 +1076,15 @@ V3 sample_direct_lighting_with_mat(const HitInfo &hit, const MaterialProps &mat,
             direct_light = bsdf * light_radiance * attenuation / pdf_sample;
             direct_light = clamp_vector_soft(direct_light, 500.0f); // MAX_NEE_CONTRIBUTION
         }
+    }
+    if (lg) {
+        lg->light_sampled = 1;
+        lg->light_index = light_index;
+        log3(lg->L, L);
+        lg->pdf_sample = pdf_sample;
+        lg->light_dist = light_dist;
+        lg->shadowed = inShadow ? 1 : 0;
+        log3(lg->contribution, direct_light);
     }
     return direct_light;
 }
@@ -1271,13 +1316,32 @@ bool material_scatter(const HitInfo &hit, const MaterialProps &mat, const Ray &r
 // the integrator (path_logic.cuh:782-899)
 // ---------------------------------------------------------------------------
 V3 tracePath(Ray ray, const ptrt_scene_desc &S, Xorwow &rng, int max_depth, V3 &out_first_normal,
-             float &out_first_depth, int &out_first_objectId, Counters &cnt) {
+             float &out_first_depth, int &out_first_objectId, Counters &cnt, PathVertexLog *log = nullptr) {
     V3 accumulated_color(0.0f);
     V3 throughput(1.0f);
     bool prev_was_specular = true;
     const V3 skyTop = S.sky_top, skyBottom = S.sky_bottom;
     for (int bounce = 0; bounce < max_depth; ++bounce) {
+        PathVertexLog *lg = log ? log + bounce : nullptr;
         HitInfo hit = traceRay(ray, S, cnt);
+        if (lg) {
+            lg->visited = 1;
+            lg->light_index = -1;
+            log_state(lg->state_before, rng);
+            log_state(lg->state_after, rng);
+            log3(lg->ray_origin, ray.orig);
+            log3(lg->ray_dir, ray.dir);
+            lg->ray_specular = ray.spec ? 1 : 0;
+            lg->hit = hit.hit ? 1 : 0;
+            lg->t = hit.t;
+            log3(lg->point, hit.point);
+            log3(lg->normal, hit.normal);
+            lg->mesh_index = hit.mesh_index;
+            lg->front_face = hit.front_face ? 1 : 0;
+            log3(lg->throughput_before, throughput);
+            log3(lg->throughput_absorbed, throughput);
+            log3(lg->throughput_after, throughput);
+        }
         if (bounce == 0) {
             if (!hit.hit) {
                 out_first_normal = V3(0.0f);
@@ -1292,6 +1356,8 @@ V3 tracePath(Ray ray, const ptrt_scene_desc &S, Xorwow &rng, int max_depth, V3 &
         if (!hit.hit) {
             V3 sky = sampleSky(ray, skyTop, skyBottom, S.use_sky != 0, EnvMap{S.env_rgba, S.env_width, S.env_height});
             accumulated_color = accumulated_color + throughput * sky;
+            if (lg)
+                log3(lg->accumulated, accumulated_color);
             break;
         }
         MaterialProps mat;
@@ -1302,37 +1368,70 @@ V3 tracePath(Ray ray, const ptrt_scene_desc &S, Xorwow &rng, int max_depth, V3 &
             V3 absorption(-dm_log(T_unit.x), -dm_log(T_unit.y), -dm_log(T_unit.z));
             throughput = throughput * beerLambert(absorption, hit.t);
         }
+        if (lg)
+            log3(lg->throughput_absorbed, throughput);
         V3 emission = mat.emission;
         if (emission.x > 0.0f || emission.y > 0.0f || emission.z > 0.0f) {
-            if (bounce == 0 || prev_was_specular)
+            if (bounce == 0 || prev_was_specular) {
                 accumulated_color = accumulated_color + throughput * emission;
+                if (lg)
+                    lg->emission_added = 1;
+            }
         }
         if (!ray.spec) {
             V3 L_nee;
             float pdf_nee;
-            V3 brdf_nee = sample_direct_lighting_with_mat(hit, mat, ray, S, rng, L_nee, pdf_nee, cnt);
+            V3 brdf_nee = sample_direct_lighting_with_mat(hit, mat, ray, S, rng, L_nee, pdf_nee, cnt, lg);
             if (brdf_nee.x > 0.0f || brdf_nee.y > 0.0f || brdf_nee.z > 0.0f) {
                 if (pdf_nee > 0.0f) {
                     float pdf_brdf = material_pdf(hit, mat, V, L_nee);
                     float w = mis_weight(pdf_nee, pdf_brdf);
                     accumulated_color = accumulated_color + throughput * brdf_nee * w;
+                    if (lg) {
+                        lg->pdf_brdf = pdf_brdf;
+                        lg->w = w;
+                    }
                 }
             }
+        }
+        if (lg) {
+            log3(lg->accumulated, accumulated_color);
+            log_state(lg->state_after, rng);
         }
         V3 scatter_dir, attenuation;
         bool is_specular;
         float pdf_brdf;
-        if (!material_scatter(hit, mat, ray, rng, scatter_dir, attenuation, is_specular, pdf_brdf))
+        const bool scattered = material_scatter(hit, mat, ray, rng, scatter_dir, attenuation, is_specular, pdf_brdf);
+        if (lg) {
+            log_state(lg->state_after, rng);
+            lg->scatter_ok = scattered ? 1 : 0;
+            if (scattered) {
+                log3(lg->scatter_dir, scatter_dir);
+                log3(lg->attenuation, attenuation);
+                lg->scatter_specular = is_specular ? 1 : 0;
+            }
+        }
+        if (!scattered)
             break;
         prev_was_specular = is_specular;
         if (bounce >= 2) { // RUSSIAN_ROULETTE_START_BOUNCE, path_logic.cuh:24
             float p = dm_max(0.05f, dm_min(0.95f, dm_max(throughput.x, dm_max(throughput.y, throughput.z))));
-            if (xorwow_uniform(rng) > p)
+            const float u_rr = xorwow_uniform(rng);
+            if (lg) {
+                log_state(lg->state_after, rng);
+                lg->roulette = 1;
+                lg->p = p;
+                lg->u = u_rr;
+                lg->survived = u_rr > p ? 0 : 1;
+            }
+            if (u_rr > p)
                 break;
             throughput = throughput / p;
         }
         throughput = throughput * attenuation;
         throughput = clamp_vector_soft(throughput, 50.0f); // MAX_BOUNCE_WEIGHT
+        if (lg)
+            log3(lg->throughput_after, throughput);
         V3 offset_origin;
         if (dot(scatter_dir, hit.normal) > 0.0f)
             offset_origin = hit.point + hit.normal * 1e-4f;
@@ -1749,6 +1848,60 @@ void oracle_eval_bsdf_n(const ptrt_materials *mats, int n, const float *items11,
                          out4 + (size_t)i * 4 + 3);
     }
 }
+
+/* tracePath for a caller's rays: the sample loop of ptrt_query_radiance as include/ptrt.h words it -- per ray `samples` paths
+ * from the ray's own generator state (n*6 words {d,v0..v4}, advanced IN PLACE), each path's radiance already soft-clamped by
+ * tracePath, summed in order from +0.0f and divided by (float)samples; depth, normal and object id are the first hit of sample 0.
+ * out_records: n ptrt_radiance.  log (optional): n*samples*max_depth PathVertexLog, zeroed here, vertex (ray, sample, bounce). */
+int oracle_trace_paths(const ptrt_scene_desc *scene, const float *origins, const float *directions, uint32_t *states, int n,
+                       int samples, int max_depth, ptrt_radiance *out_records, void *log) {
+    if (!scene || !origins || !directions || !states || !out_records || n < 0 || samples < 1 || max_depth < 1)
+        return -1;
+    if (!oracle_has_fma())
+        return -2;
+    PathVertexLog *lg = (PathVertexLog *)log;
+    if (lg)
+        memset(lg, 0, sizeof(PathVertexLog) * (size_t)n * samples * max_depth);
+    Counters cnt;
+    for (int i = 0; i < n; ++i) {
+        Xorwow rng;
+        rng.d = states[(size_t)i * 6];
+        for (int k = 0; k < 5; ++k)
+            rng.v[k] = states[(size_t)i * 6 + 1 + k];
+        ptrt_radiance &r = out_records[i];
+        V3 sum(0.0f), first_normal(0.0f);
+        float first_depth = 1e30f;
+        int first_id = -1;
+        if (scene->materials.count > 0) {
+            for (int s = 0; s < samples; ++s) {
+                const Ray ray(V3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]),
+                              V3(directions[i * 3], directions[i * 3 + 1], directions[i * 3 + 2]), true);
+                V3 nrm;
+                float depth = 0.0f;
+                int id = -1;
+                V3 c = tracePath(ray, *scene, rng, max_depth, nrm, depth, id, cnt,
+                                 lg ? lg + ((size_t)i * samples + s) * max_depth : nullptr);
+                sum = sum + c;
+                if (s == 0) {
+                    first_normal = nrm;
+                    first_depth = depth;
+                    first_id = id;
+                }
+            }
+        }
+        const V3 mean = sum / (float)samples;
+        r.radiance[0] = mean.x; r.radiance[1] = mean.y; r.radiance[2] = mean.z;
+        r.depth = first_depth;
+        r.normal[0] = first_normal.x; r.normal[1] = first_normal.y; r.normal[2] = first_normal.z;
+        r.object_id = first_id;
+        states[(size_t)i * 6] = rng.d;
+        for (int k = 0; k < 5; ++k)
+            states[(size_t)i * 6 + 1 + k] = rng.v[k];
+    }
+    return 0;
+}
+
+int oracle_path_log_bytes(void) { return (int)sizeof(PathVertexLog); }
 
 void oracle_scatter_n(const ptrt_materials *mats, int n, const float *items14, float *out14) {
     for (int i = 0; i < n; ++i) {
