@@ -88,13 +88,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
             Rng rng = {0, 0, 0, 0, 0, 0};
             if (live) {
                 d0 = mk3(dirs[k * 3], dirs[k * 3 + 1], dirs[k * 3 + 2]);
-                const uint32_t *st = rng_states + i * 6; // canonical order {d, v0..v4}
-                rng.d = st[0];
-                rng.v0 = st[1];
-                rng.v1 = st[2];
-                rng.v2 = st[3];
-                rng.v3 = st[4];
-                rng.v4 = st[5];
+                load_rng_state(rng, rng_states + i * 6);
             }
             float depth = 1e30f;
             int object_id = -1;
@@ -102,13 +96,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
             const f3 sum = trace_chunk_samples<GEOM, FULL, PMODE>(kp0, PL, stk, cyc, lane, live, o0, d0, rng, first);
             f3 mean = mk3(0.0f);
             if (live) {
-                uint32_t *st = rng_states + i * 6;
-                st[0] = rng.d;
-                st[1] = rng.v0;
-                st[2] = rng.v1;
-                st[3] = rng.v2;
-                st[4] = rng.v3;
-                st[5] = rng.v4;
+                store_rng_state(rng_states + i * 6, rng);
                 mean = sum / (float)kparams(kp0).spp; // ptrt_radiance.radiance of this ray
             }
             // the chunk's 30 terms, one quantity at a time; lane q picks up the chunk's sum of quantity q

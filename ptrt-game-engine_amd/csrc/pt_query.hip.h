@@ -84,7 +84,8 @@ __global__ __launch_bounds__(64) void ray_query_kernel(const KParams K, const fl
     CycleAcc cyc;
     PairLds PL{};
     if (PMODE == 1) {
-        // path_trace_kernel's PMODE 1 staging: the leaf's triangle packets (PAIR_PAD float4 apart per mesh), mesh table, heads
+        // the staging of stage_pair_lds (pt_render.hip.h), which this block has to agree with: the leaf's triangle packets
+        // (PAIR_PAD float4 apart per mesh), mesh table, heads
         PL = carve_pair_lds((void *)lds_raw, K.pair_tri_slots, K.pair_meshes);
         const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
         for (int i = 0; i < K.pair_meshes; ++i) {

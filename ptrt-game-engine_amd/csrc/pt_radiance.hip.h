@@ -234,43 +234,23 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
     return sum;
 }
 
-// ray_query_kernel's LDS carve and staging by PMODE (pt_query.hip.h), for the two kernels below; the caller synchronises.
-template <int PMODE> PT_DEV PairLds stage_pair_lds(const KParams &K, uint2 *lds_raw, const int lane) {
-    PairLds PL{};
-    if (PMODE == 1) {
-        // ray_query_kernel's staging: the leaf's triangle packets (PAIR_PAD float4 apart per mesh), mesh table, heads
-        PL = carve_pair_lds((void *)lds_raw, K.pair_tri_slots, K.pair_meshes);
-        const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = 0; i < K.pair_meshes; ++i) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const int2 leaf = K.leaves[~__float_as_int(K.mesh_recs[m * MESH_REC_F4].w)];
-            for (int k = lane; k < leaf.y * 3; k += 64)
-                PL.tris[leaf.x * 3 + i * PAIR_PAD + k] = K.tris[leaf.x * 3 + k];
-        }
-        for (int i = lane; i < K.pair_meshes; i += 64) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
-            PL.meshbox[2 * i + 1] = hb;
-            const int2 leaf = K.leaves[~mh.root_ref];
-            PL.meshtab[i] = make_int4(leaf.x, leaf.y, mh.flags, m);
-        }
-    } else if (PMODE) {
-        PL = carve_pair_lds((void *)lds_raw, 0, PMODE == 3 ? 0 : K.pair_meshes, K.stack_entries, PMODE == 3 ? K.tlas_max_leaf : 0,
-                            PMODE == 3 ? K.tlas_depth : 0);
-        const int2 lf = PMODE == 3 ? make_int2(0, 0) : K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = lane; PMODE != 3 && i < K.pair_meshes; i += 64) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8));
-            PL.meshbox[2 * i + 1] = hb;
-        }
-    }
-    return PL;
+// A ray's generator state in the caller's array: six words in the canonical order {d, v0..v4}, read before the ray's paths
+// and written back advanced behind them (radiance_query_kernel, probe_query_kernel).
+PT_DEV void load_rng_state(Rng &rng, const uint32_t *st) {
+    rng.d = st[0];
+    rng.v0 = st[1];
+    rng.v1 = st[2];
+    rng.v2 = st[3];
+    rng.v3 = st[4];
+    rng.v4 = st[5];
+}
+PT_DEV void store_rng_state(uint32_t *st, const Rng &rng) {
+    st[0] = rng.d;
+    st[1] = rng.v0;
+    st[2] = rng.v1;
+    st[3] = rng.v2;
+    st[4] = rng.v3;
+    st[5] = rng.v4;
 }
 
 // Waves per SIMD the kernel is built for (its register budget: 512 / waves, in steps of 8): the most at which the pair variants
@@ -305,24 +285,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
         if (live) {
             o0 = mk3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]);
             d0 = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
-            const uint32_t *st = rng_states + i * 6; // canonical order {d, v0..v4}
-            rng.d = st[0];
-            rng.v0 = st[1];
-            rng.v1 = st[2];
-            rng.v2 = st[3];
-            rng.v3 = st[4];
-            rng.v4 = st[5];
+            load_rng_state(rng, rng_states + i * 6);
         }
         const FirstHitToRecord first{out, i};
         const f3 sum = trace_chunk_samples<GEOM, FULL, PMODE>(kp0, PL, stk, cyc, lane, live, o0, d0, rng, first);
         if (live) {
-            uint32_t *st = rng_states + i * 6;
-            st[0] = rng.d;
-            st[1] = rng.v0;
-            st[2] = rng.v1;
-            st[3] = rng.v2;
-            st[4] = rng.v3;
-            st[5] = rng.v4;
+            store_rng_state(rng_states + i * 6, rng);
             const f3 mean = sum / (float)kparams(kp0).spp;
             RadianceOut *r = out + i;
             r->radiance[0] = mean.x;

@@ -113,6 +113,51 @@ PT_DEV PairLds carve_pair_lds(void *base, int tri_slots, int meshes, int stack_e
     return l;
 }
 
+// What a one-wave workgroup of a device query stages into LDS once, before its grid-stride loop, over the carve above (host:
+// pair_lds_bytes), for radiance_query_kernel and probe_query_kernel:
+//   PMODE 1   the single leaf's triangle packets (PAIR_PAD float4 apart per mesh), the mesh table and the mesh heads;
+//   PMODE 2   the mesh heads of the single-leaf TLAS (the BLAS stacks are carved, nothing of them is staged);
+//   PMODE 3   nothing: the carve only (TLAS stacks, one leaf per ray), the heads are read from memory;
+//   PMODE 0   nothing at all (an empty PairLds: the lanes' stacks start at the base of the LDS).
+// The caller sets `cyc` / `stat_bounce` and synchronises.  ray_query_kernel (pt_query.hip.h) states the same staging in its own
+// body and has to agree with this; path_trace_kernel stages for itself (carve_pm1, workgroup-wide).
+template <int PMODE> PT_DEV PairLds stage_pair_lds(const KParams &K, uint2 *lds_raw, const int lane) {
+    PairLds PL{};
+    if (PMODE == 1) {
+        PL = carve_pair_lds((void *)lds_raw, K.pair_tri_slots, K.pair_meshes);
+        const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
+        for (int i = 0; i < K.pair_meshes; ++i) {
+            const int m = K.tlas_mesh_ids[lf.x + i];
+            const int2 leaf = K.leaves[~__float_as_int(K.mesh_recs[m * MESH_REC_F4].w)];
+            for (int k = lane; k < leaf.y * 3; k += 64)
+                PL.tris[leaf.x * 3 + i * PAIR_PAD + k] = K.tris[leaf.x * 3 + k];
+        }
+        for (int i = lane; i < K.pair_meshes; i += 64) {
+            const int m = K.tlas_mesh_ids[lf.x + i];
+            const MeshHead mh = load_mesh_head(K, m);
+            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
+            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
+            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
+            PL.meshbox[2 * i + 1] = hb;
+            const int2 leaf = K.leaves[~mh.root_ref];
+            PL.meshtab[i] = make_int4(leaf.x, leaf.y, mh.flags, m);
+        }
+    } else if (PMODE) {
+        PL = carve_pair_lds((void *)lds_raw, 0, PMODE == 3 ? 0 : K.pair_meshes, K.stack_entries, PMODE == 3 ? K.tlas_max_leaf : 0,
+                            PMODE == 3 ? K.tlas_depth : 0);
+        const int2 lf = PMODE == 3 ? make_int2(0, 0) : K.tlas_leaves[~K.tlas_root_ref];
+        for (int i = lane; PMODE != 3 && i < K.pair_meshes; i += 64) {
+            const int m = K.tlas_mesh_ids[lf.x + i];
+            const MeshHead mh = load_mesh_head(K, m);
+            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
+            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
+            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8));
+            PL.meshbox[2 * i + 1] = hb;
+        }
+    }
+    return PL;
+}
+
 // PMODE 1 (every BLAS one leaf, the scene's triangles in LDS).  A workgroup of WG waves = WG neighbouring tiles shares ONE copy
 // of what is read-only -- triangle packets, mesh table, mesh heads, jitter table, light and material records -- and each
 // wave has its own lists behind it: the rays' minima / flags, the pair list, the lanes' blue-noise values, the ray totals.

@@ -1110,321 +1110,9 @@ int ptrt_write_rng(ptrt_ctx *c, const uint32_t *states, size_t bytes) {
 
 } // extern "C"
 
-// ray_query_kernel (pt_query.hip.h) over n rays in device memory, on the context's stream.  The traversal is the path kernel's
-// for this scene and these options: pair_mode(c, geom, false), the (ray, mesh) pair walk wherever [B] / [D] use one, one ray
-// per lane where they do not.  A persistent grid: about one 64-thread workgroup per wave slot of the chip.
-template <int GEOM, int PMODE, int KIND>
-int run_query(ptrt_ctx *c, const pt::KParams &K, size_t lds, const float *o, const float *d, const float *tmax, size_t n, void *out) {
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt::ray_query_kernel<GEOM, PMODE, KIND>, 64, lds));
-    const size_t chunks = (n + 63) / 64, slots = (size_t)(c->n_cus > 0 ? c->n_cus : 1) * (size_t)(per_cu > 0 ? per_cu : 1);
-    const unsigned grid = (unsigned)(chunks < slots ? chunks : slots);
-    hipLaunchKernelGGL((pt::ray_query_kernel<GEOM, PMODE, KIND>), dim3(grid), dim3(64), lds, c->stream, K, o, d, tmax, n, out);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
-}
-template <int KIND>
-int dispatch_query(ptrt_ctx *c, int geom, int pmode, const pt::KParams &K, size_t lds, const float *o, const float *d,
-                   const float *tmax, size_t n, void *out) {
-    switch (pmode ? pmode : -geom) { // PMODE 1..3 (the pair walks do not depend on GEOM: one instantiation each), else PMODE 0 by GEOM
-    case 1: return run_query<0, 1, KIND>(c, K, lds, o, d, tmax, n, out);
-    case 2: return run_query<1, 2, KIND>(c, K, lds, o, d, tmax, n, out);
-    case 3: return run_query<2, 3, KIND>(c, K, lds, o, d, tmax, n, out);
-    case 0: return run_query<0, 0, KIND>(c, K, lds, o, d, tmax, n, out);
-    case -1: return run_query<1, 0, KIND>(c, K, lds, o, d, tmax, n, out);
-    default: return run_query<2, 0, KIND>(c, K, lds, o, d, tmax, n, out);
-    }
-}
-int launch_query(ptrt_ctx *c, int kind, const float *o, const float *d, const float *tmax, size_t n, void *out) {
-    const pt::KParams K = make_params(c);
-    const int geom = pick_geom(c);
-    const int pmode = pair_mode(c, geom, false);
-    c->query_pmode = pmode;
-    c->pm1_lane_groups_eff = pmode == 1 ? K.pm1_groups : 0;
-    const size_t lds = trace_lds_bytes(c, geom, pmode);
-    if (pmode == 3)
-        if (int rc = refresh_tlas_heads(c, false))
-            return rc;
-    return kind == PTRT_QUERY_CLOSEST ? dispatch_query<pt::QUERY_CLOSEST>(c, geom, pmode, K, lds, o, d, tmax, n, out)
-                                      : dispatch_query<pt::QUERY_OCCLUDED>(c, geom, pmode, K, lds, o, d, tmax, n, out);
-}
+#include "ptrt_query.hip.h"
 
 extern "C" {
-
-int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, int n, ptrt_hit *out) {
-    static_assert(sizeof(pt::HitOut) == sizeof(ptrt_hit), "HitOut must mirror ptrt_hit");
-    if (!ctx_live(c) || !origins || !directions || !out || n < 0)
-        return fail(c, PTRT_E_INVALID, "ptrt_trace_rays: bad argument");
-    if (!c->have_geometry)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_trace_rays: geometry not uploaded");
-    if (n == 0)
-        return PTRT_OK;
-    if (int rc = set_device(c))
-        return rc;
-    // host staging around the CLOSEST query of ptrt_query_rays
-    DeviceTemp<float> d_o, d_d;
-    DeviceTemp<pt::HitOut> d_h;
-    HIP_TRY(c, d_o.alloc((size_t)n * 3));
-    HIP_TRY(c, d_d.alloc((size_t)n * 3));
-    HIP_TRY(c, d_h.alloc((size_t)n));
-    HIP_TRY(c, hipMemcpyAsync(d_o.p, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_d.p, directions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    if (int rc = launch_query(c, PTRT_QUERY_CLOSEST, d_o.p, d_d.p, nullptr, (size_t)n, d_h.p))
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, d_h.p, (size_t)n * sizeof(pt::HitOut), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PTRT_OK;
-}
-
-int ptrt_query_rays(ptrt_ctx *c, int kind, const float *origins, const float *directions, const float *tmax, int n, void *out) {
-    if (!ctx_live(c, false))
-        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: bad context");
-    if (kind != PTRT_QUERY_CLOSEST && kind != PTRT_QUERY_OCCLUDED)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: kind %d (PTRT_QUERY_CLOSEST or PTRT_QUERY_OCCLUDED)", kind);
-    if (n < 0 || !origins || !directions || !out)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: bad argument (n %d, origins %p, directions %p, out %p)", n,
-                    (const void *)origins, (const void *)directions, out);
-    if (kind == PTRT_QUERY_OCCLUDED && !tmax)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: PTRT_QUERY_OCCLUDED needs tmax");
-    if (kind == PTRT_QUERY_CLOSEST && tmax)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: PTRT_QUERY_CLOSEST takes no tmax (pass NULL)");
-    if (!c->have_geometry)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_query_rays: geometry not uploaded");
-    if (n == 0)
-        return PTRT_OK;
-    if (int rc = set_device(c))
-        return rc;
-    const size_t rays = (size_t)n, rec = kind == PTRT_QUERY_CLOSEST ? sizeof(pt::HitOut) : sizeof(int32_t);
-    const char *bad = !device_span(c, origins, rays * 12)                        ? "origins"
-                      : !device_span(c, directions, rays * 12)                   ? "directions"
-                      : (tmax && !device_span(c, tmax, rays * sizeof(float)))    ? "tmax"
-                      : !device_span(c, out, rays * rec)                         ? "out"
-                                                                                 : nullptr;
-    if (bad)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: %s is not %zu bytes of device memory on device %d", bad,
-                    rays * (bad[0] == 't' ? sizeof(float) : bad[0] == 'o' && bad[1] == 'u' ? rec : 12), c->device);
-    // a path frame that follows is ordered behind the query on the stream, as behind the wireframe view (option "pipeline")
-    c->touched = true;
-    return launch_query(c, kind, origins, directions, tmax, rays, out);
-}
-
-} // extern "C"
-
-// radiance_query_kernel (pt_radiance.hip.h) over n rays and generator states in device memory, on the context's stream: the
-// launch of run_query -- the same traversal mode, LDS size and persistent grid -- with the materials a frame would use
-// (plan_frame's `full`).
-template <int GEOM, bool FULL, int PMODE>
-int run_radiance(ptrt_ctx *c, const pt::KParams &K, size_t lds, const float *o, const float *d, uint32_t *rng, size_t n,
-                 pt::RadianceOut *out) {
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt::radiance_query_kernel<GEOM, FULL, PMODE>, 64, lds));
-    if (c->persist > 0) // option "persist": persistent waves per CU
-        per_cu = c->persist;
-    const size_t chunks = (n + 63) / 64, slots = (size_t)(c->n_cus > 0 ? c->n_cus : 1) * (size_t)(per_cu > 0 ? per_cu : 1);
-    const unsigned grid = (unsigned)(chunks < slots ? chunks : slots);
-    hipLaunchKernelGGL((pt::radiance_query_kernel<GEOM, FULL, PMODE>), dim3(grid), dim3(64), lds, c->stream, K, o, d, rng, n, out);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
-}
-template <bool FULL>
-int dispatch_radiance(ptrt_ctx *c, int geom, int pmode, const pt::KParams &K, size_t lds, const float *o, const float *d,
-                      uint32_t *rng, size_t n, pt::RadianceOut *out) {
-    switch (pmode ? pmode : -geom) { // (as dispatch_query)
-    case 1: return run_radiance<0, FULL, 1>(c, K, lds, o, d, rng, n, out);
-    case 2: return run_radiance<1, FULL, 2>(c, K, lds, o, d, rng, n, out);
-    case 3: return run_radiance<2, FULL, 3>(c, K, lds, o, d, rng, n, out);
-    case 0: return run_radiance<0, FULL, 0>(c, K, lds, o, d, rng, n, out);
-    case -1: return run_radiance<1, FULL, 0>(c, K, lds, o, d, rng, n, out);
-    default: return run_radiance<2, FULL, 0>(c, K, lds, o, d, rng, n, out);
-    }
-}
-
-// probe_query_kernel (pt_probe.hip.h) over n_probes probes of n_dirs rays each: run_radiance's launch with the grid striding
-// over probes, one wave per probe.
-template <int GEOM, bool FULL, int PMODE>
-int run_probes(ptrt_ctx *c, const pt::KParams &K, size_t lds, const float *pos, int n_probes, const float *d, int n_dirs,
-               uint32_t *rng, float max_distance, pt::ProbeOut *out) {
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt::probe_query_kernel<GEOM, FULL, PMODE>, 64, lds));
-    if (c->persist > 0) // option "persist": persistent waves per CU
-        per_cu = c->persist;
-    const size_t slots = (size_t)(c->n_cus > 0 ? c->n_cus : 1) * (size_t)(per_cu > 0 ? per_cu : 1);
-    const unsigned grid = (unsigned)((size_t)n_probes < slots ? (size_t)n_probes : slots);
-    hipLaunchKernelGGL((pt::probe_query_kernel<GEOM, FULL, PMODE>), dim3(grid), dim3(64), lds, c->stream, K, pos, n_probes, d, n_dirs,
-                       rng, max_distance, out);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
-}
-template <bool FULL>
-int dispatch_probes(ptrt_ctx *c, int geom, int pmode, const pt::KParams &K, size_t lds, const float *pos, int n_probes,
-                    const float *d, int n_dirs, uint32_t *rng, float max_distance, pt::ProbeOut *out) {
-    switch (pmode ? pmode : -geom) { // (as dispatch_radiance)
-    case 1: return run_probes<0, FULL, 1>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
-    case 2: return run_probes<1, FULL, 2>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
-    case 3: return run_probes<2, FULL, 3>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
-    case 0: return run_probes<0, FULL, 0>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
-    case -1: return run_probes<1, FULL, 0>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
-    default: return run_probes<2, FULL, 0>(c, K, lds, pos, n_probes, d, n_dirs, rng, max_distance, out);
-    }
-}
-
-extern "C" {
-
-int ptrt_query_radiance(ptrt_ctx *c, const float *origins, const float *directions, uint32_t *rng_states, int n, int samples,
-                        int max_depth, ptrt_radiance *out) {
-    static_assert(sizeof(pt::RadianceOut) == sizeof(ptrt_radiance) && sizeof(ptrt_radiance) == 32, "RadianceOut must mirror ptrt_radiance");
-    if (!ctx_live(c, false))
-        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: bad context");
-    if (n < 0 || !origins || !directions || !rng_states || !out)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: bad argument (n %d, origins %p, directions %p, rng_states %p, out %p)", n,
-                    (const void *)origins, (const void *)directions, (const void *)rng_states, (const void *)out);
-    if (samples < 1 || max_depth < 1 || samples > 32767 || max_depth > 32767) // (ptrt_render's range)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: samples=%d max_depth=%d (1..32767)", samples, max_depth);
-    if (!c->have_geometry || !c->have_materials)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_query_radiance: %s not uploaded", c->have_geometry ? "materials" : "geometry");
-    if (c->n_materials < c->n_meshes)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_query_radiance: %d materials for %d meshes", c->n_materials, c->n_meshes);
-    if (n == 0)
-        return PTRT_OK;
-    if (int rc = set_device(c))
-        return rc;
-    const size_t rays = (size_t)n;
-    const char *bad = !device_span(c, origins, rays * 12)                      ? "origins"
-                      : !device_span(c, directions, rays * 12)                 ? "directions"
-                      : !device_span(c, rng_states, rays * 24)                 ? "rng_states"
-                      : !device_span(c, out, rays * sizeof(ptrt_radiance))     ? "out"
-                                                                               : nullptr;
-    if (bad)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: %s is not %zu bytes of device memory on device %d", bad,
-                    rays * (bad[0] == 'r' ? 24 : bad[0] == 'o' && bad[1] == 'u' ? sizeof(ptrt_radiance) : 12), c->device);
-    pt::KParams K = make_params(c);
-    K.spp = samples;
-    K.max_depth = max_depth;
-    // (the context's own per-pixel buffers are no business of the query's)
-    K.rng = nullptr;
-    K.accum = K.normal = K.depth = nullptr;
-    K.object_id = nullptr;
-    K.rgb8 = nullptr;
-    const int geom = pick_geom(c);
-    const int pmode = pair_mode(c, geom, false);
-    const bool full = c->mats_full || c->force_full;
-    const size_t lds = trace_lds_bytes(c, geom, pmode);
-    // a path frame that follows is ordered behind the query on the stream (option "pipeline"), as behind ptrt_query_rays
-    c->touched = true;
-    c->query_pmode = pmode;
-    c->pm1_lane_groups_eff = pmode == 1 ? K.pm1_groups : 0;
-    if (pmode == 3)
-        if (int rc = refresh_tlas_heads(c, false))
-            return rc;
-    pt::RadianceOut *o = reinterpret_cast<pt::RadianceOut *>(out);
-    return full ? dispatch_radiance<true>(c, geom, pmode, K, lds, origins, directions, rng_states, rays, o)
-                : dispatch_radiance<false>(c, geom, pmode, K, lds, origins, directions, rng_states, rays, o);
-}
-
-int ptrt_query_probes(ptrt_ctx *c, const float *d_positions, int n_probes, const float *d_directions, int n_dirs,
-                      uint32_t *d_rng_states, int samples, int max_depth, float max_distance, ptrt_probe *d_out) {
-    static_assert(sizeof(pt::ProbeOut) == sizeof(ptrt_probe) && sizeof(ptrt_probe) == 128, "ProbeOut must mirror ptrt_probe");
-    if (!ctx_live(c, false))
-        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: bad context");
-    if (n_probes < 0 || n_dirs < 1 || !d_positions || !d_directions || !d_rng_states || !d_out)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: bad argument (n_probes %d, n_dirs %d, positions %p, directions %p, rng_states %p, out %p)",
-                    n_probes, n_dirs, (const void *)d_positions, (const void *)d_directions, (const void *)d_rng_states, (const void *)d_out);
-    if (samples < 1 || max_depth < 1 || samples > 32767 || max_depth > 32767) // (ptrt_render's range)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: samples=%d max_depth=%d (1..32767)", samples, max_depth);
-    if (!(max_distance > 0.0f) || !std::isfinite(max_distance))
-        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: max_distance=%g (positive and finite)", (double)max_distance);
-    if (!c->have_geometry || !c->have_materials)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_query_probes: %s not uploaded", c->have_geometry ? "materials" : "geometry");
-    if (c->n_materials < c->n_meshes)
-        return fail(c, PTRT_E_NOT_READY, "ptrt_query_probes: %d materials for %d meshes", c->n_materials, c->n_meshes);
-    if (n_probes == 0)
-        return PTRT_OK;
-    if (int rc = set_device(c))
-        return rc;
-    // byte counts in size_t: n_probes * n_dirs rays is below 2^62 and fits; times 24 bytes of state it need not
-    const size_t probes = (size_t)n_probes, ndirs = (size_t)n_dirs, rays = probes * ndirs;
-    if (rays > SIZE_MAX / 24)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: %d probes x %d directions: the states' byte count overflows", n_probes, n_dirs);
-    const char *bad = !device_span(c, d_positions, probes * 12)                  ? "positions"
-                      : !device_span(c, d_directions, ndirs * 12)                ? "directions"
-                      : !device_span(c, d_rng_states, rays * 24)                 ? "rng_states"
-                      : !device_span(c, d_out, probes * sizeof(ptrt_probe))      ? "out"
-                                                                                 : nullptr;
-    if (bad)
-        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: %s is not %zu bytes of device memory on device %d", bad,
-                    bad[0] == 'p' ? probes * 12 : bad[0] == 'd' ? ndirs * 12 : bad[0] == 'r' ? rays * 24 : probes * sizeof(ptrt_probe),
-                    c->device);
-    pt::KParams K = make_params(c);
-    K.spp = samples;
-    K.max_depth = max_depth;
-    // (the context's own per-pixel buffers are no business of the query's)
-    K.rng = nullptr;
-    K.accum = K.normal = K.depth = nullptr;
-    K.object_id = nullptr;
-    K.rgb8 = nullptr;
-    const int geom = pick_geom(c);
-    const int pmode = pair_mode(c, geom, false);
-    const bool full = c->mats_full || c->force_full;
-    const size_t lds = trace_lds_bytes(c, geom, pmode);
-    // a path frame that follows is ordered behind the query on the stream (option "pipeline"), as behind ptrt_query_radiance
-    c->touched = true;
-    c->query_pmode = pmode;
-    c->pm1_lane_groups_eff = pmode == 1 ? K.pm1_groups : 0;
-    if (pmode == 3)
-        if (int rc = refresh_tlas_heads(c, false))
-            return rc;
-    pt::ProbeOut *o = reinterpret_cast<pt::ProbeOut *>(d_out);
-    return full ? dispatch_probes<true>(c, geom, pmode, K, lds, d_positions, n_probes, d_directions, n_dirs, d_rng_states, max_distance, o)
-                : dispatch_probes<false>(c, geom, pmode, K, lds, d_positions, n_probes, d_directions, n_dirs, d_rng_states, max_distance, o);
-}
-
-int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins, float *d_directions) {
-    if (!ctx_live(c, false))
-        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: bad context");
-    if (frame_index < 0 || sample < 0 || frame_index > INT_MAX - sample)
-        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: frame_index=%d sample=%d", frame_index, sample);
-    if (!d_origins || !d_directions)
-        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: a target is NULL");
-    if (c->cam.lens_radius > 0.0f)
-        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: a thin lens (lens_radius %g): the lens sample of a primary ray is drawn "
-                                       "from the pixel's generator stream", (double)c->cam.lens_radius);
-    if (int rc = set_device(c))
-        return rc;
-    pt::KParams K = make_params(c);
-    K.frame_count = frame_index + sample;
-    const size_t rays = (size_t)K.rows * K.width;
-    const char *bad = !device_span(c, d_origins, rays * 12) ? "d_origins" : !device_span(c, d_directions, rays * 12) ? "d_directions" : nullptr;
-    if (bad)
-        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: %s is not %zu bytes of device memory on device %d", bad, rays * 12, c->device);
-    c->touched = true;
-    hipLaunchKernelGGL(pt::camera_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, c->stream, K, d_origins, d_directions);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
-}
-
-int ptrt_init_rng_states(ptrt_ctx *c, unsigned long long seed, unsigned long long first_subsequence, int n, uint32_t *d_states) {
-    if (!ctx_live(c, false))
-        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: bad context");
-    if (n < 0 || !d_states)
-        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: bad argument (n %d, d_states %p)", n, (const void *)d_states);
-    if (n == 0)
-        return PTRT_OK;
-    const unsigned long long last = first_subsequence + (unsigned long long)(n - 1);
-    if (last < first_subsequence)
-        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: subsequence numbers beyond 2^64");
-    if (int rc = set_device(c))
-        return rc;
-    if (!device_span(c, d_states, (size_t)n * 24))
-        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: d_states is not %zu bytes of device memory on device %d", (size_t)n * 24, c->device);
-    if (int rc = ensure_jump(c, last, "ptrt_init_rng_states"))
-        return rc;
-    const XorwowSeed s = xorwow_seed(seed);
-    c->touched = true;
-    hipLaunchKernelGGL(pt::rng_states_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream, d_states, (size_t)n,
-                       first_subsequence, s.d, s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], c->d_jump, c->n_jump);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
-}
 
 int ptrt_render_wireframe(ptrt_ctx *c, float thickness, void *out_rgb8, int out_is_device) {
     if (!ctx_live(c)) // (marks the context touched: a pipelined path frame that follows waits for the stream, and so for this)

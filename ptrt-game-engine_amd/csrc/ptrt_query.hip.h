@@ -1,0 +1,286 @@
+// ptrt_query.hip.h -- the device queries of the C ABI: closest hit and occlusion (ptrt_trace_rays, ptrt_query_rays), path-traced
+// radiance (ptrt_query_radiance), light probes (ptrt_query_probes) and the two kernels that let a caller start where a frame
+// starts (ptrt_camera_rays, ptrt_init_rng_states).  What the three traversing queries share is decided once each: the traversal
+// (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
+// check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
+// refresh_tlas_heads) and the helpers every entry point shares.
+#pragma once
+
+#include <initializer_list>
+#include <type_traits>
+
+namespace {
+
+// What a query decides about its trace.  The traversal is the path kernel's for this scene and these options (pair_mode
+// without the merged mode): the (ray, mesh) pair walk wherever phases [B] / [D] use one, one ray per lane where they do not
+// (DESIGN.md 3.15); the LDS is that traversal's; `full` is the material model a frame would use (plan_frame's).
+struct QueryPlan {
+    pt::KParams K;
+    int geom = 0, pmode = 0;
+    bool full = false;
+    size_t lds = 0;
+};
+// `shading`: a query that runs the path loop, `samples` times to `max_depth` bounces.  A path frame that follows is ordered
+// behind the query on the stream, as behind the wireframe view (option "pipeline"): `touched`.
+int plan_query(ptrt_ctx *c, bool shading, int samples, int max_depth, QueryPlan &P) {
+    P.K = make_params(c);
+    if (shading) {
+        P.K.spp = samples;
+        P.K.max_depth = max_depth;
+        // (the context's own per-pixel buffers are no business of the query's)
+        P.K.rng = nullptr;
+        P.K.accum = P.K.normal = P.K.depth = nullptr;
+        P.K.object_id = nullptr;
+        P.K.rgb8 = nullptr;
+    }
+    const int geom = P.geom = pick_geom(c);
+    P.pmode = pair_mode(c, geom, false);
+    P.full = c->mats_full || c->force_full;
+    P.lds = trace_lds_bytes(c, geom, P.pmode);
+    c->touched = true;
+    c->query_pmode = P.pmode;
+    c->pm1_lane_groups_eff = P.pmode == 1 ? P.K.pm1_groups : 0;
+    return P.pmode == 3 ? refresh_tlas_heads(c, false) : PTRT_OK;
+}
+
+// f(GEOM, PMODE) with both as compile-time constants (std::integral_constant): the kernel variant of a traversal.  The pair
+// walks do not depend on GEOM, one instantiation each; PMODE 0 goes by GEOM.  A wrong arm would pick a kernel built for another
+// tree shape.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F> int with_variant(int geom, int pmode, F &&f) {
+    switch (pmode ? pmode : -geom) {
+    case 1: return f(int_c<0>{}, int_c<1>{});
+    case 2: return f(int_c<1>{}, int_c<2>{});
+    case 3: return f(int_c<2>{}, int_c<3>{});
+    case 0: return f(int_c<0>{}, int_c<0>{});
+    case -1: return f(int_c<1>{}, int_c<0>{});
+    default: return f(int_c<2>{}, int_c<0>{});
+    }
+}
+
+// A persistent grid of one-wave workgroups: about one per wave slot of the chip, and no more than there are `units` of work for
+// the grid-stride loop (chunks of 64 rays, or probes).  `honour_persist`: option "persist" (persistent waves per CU) overrides
+// the occupancy the runtime reports -- the shading queries, not the ray queries (include/ptrt.h).
+template <class Kernel, class... Args>
+int launch_persistent(ptrt_ctx *c, Kernel kernel, size_t lds, size_t units, bool honour_persist, const Args &...args) {
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds));
+    if (honour_persist && c->persist > 0)
+        per_cu = c->persist;
+    const size_t slots = (size_t)(c->n_cus > 0 ? c->n_cus : 1) * (size_t)(per_cu > 0 ? per_cu : 1);
+    const unsigned grid = (unsigned)(units < slots ? units : slots);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, c->stream, args...);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+// Every span is `bytes` of device memory on the context's device (device_span), or the first that is not is refused by name.
+struct Span {
+    const char *name;
+    const void *p;
+    size_t bytes;
+};
+int check_spans(ptrt_ctx *c, const char *fn, std::initializer_list<Span> spans) {
+    for (const Span &s : spans)
+        if (!device_span(c, s.p, s.bytes))
+            return fail(c, PTRT_E_INVALID, "%s: %s is not %zu bytes of device memory on device %d", fn, s.name, s.bytes, c->device);
+    return PTRT_OK;
+}
+
+// What a shading query asks of its path lengths (ptrt_render's range) and of the scene.  `max_distance`: the probes' distance
+// clamp, refused between the two as ptrt_query_probes always has; NULL for a query without one.
+int check_shading_query(ptrt_ctx *c, const char *fn, int samples, int max_depth, const float *max_distance) {
+    if (samples < 1 || max_depth < 1 || samples > 32767 || max_depth > 32767)
+        return fail(c, PTRT_E_INVALID, "%s: samples=%d max_depth=%d (1..32767)", fn, samples, max_depth);
+    if (max_distance && (!(*max_distance > 0.0f) || !std::isfinite(*max_distance)))
+        return fail(c, PTRT_E_INVALID, "%s: max_distance=%g (positive and finite)", fn, (double)*max_distance);
+    if (!c->have_geometry || !c->have_materials)
+        return fail(c, PTRT_E_NOT_READY, "%s: %s not uploaded", fn, c->have_geometry ? "materials" : "geometry");
+    if (c->n_materials < c->n_meshes)
+        return fail(c, PTRT_E_NOT_READY, "%s: %d materials for %d meshes", fn, c->n_materials, c->n_meshes);
+    return PTRT_OK;
+}
+
+// ray_query_kernel (pt_query.hip.h) over n rays in device memory, on the context's stream.
+int launch_ray_query(ptrt_ctx *c, int kind, const float *o, const float *d, const float *tmax, size_t n, void *out) {
+    QueryPlan P;
+    if (int rc = plan_query(c, false, 0, 0, P))
+        return rc;
+    auto launch = [&](auto KIND) {
+        return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+            return launch_persistent(c, pt::ray_query_kernel<G, PM, KIND>, P.lds, (n + 63) / 64, false, P.K, o, d, tmax, n, out);
+        });
+    };
+    return kind == PTRT_QUERY_CLOSEST ? launch(int_c<pt::QUERY_CLOSEST>{}) : launch(int_c<pt::QUERY_OCCLUDED>{});
+}
+
+} // namespace
+
+extern "C" {
+
+int ptrt_trace_rays(ptrt_ctx *c, const float *origins, const float *directions, int n, ptrt_hit *out) {
+    static_assert(sizeof(pt::HitOut) == sizeof(ptrt_hit), "HitOut must mirror ptrt_hit");
+    if (!ctx_live(c) || !origins || !directions || !out || n < 0)
+        return fail(c, PTRT_E_INVALID, "ptrt_trace_rays: bad argument");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_trace_rays: geometry not uploaded");
+    if (n == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    // host staging around the CLOSEST query of ptrt_query_rays
+    DeviceTemp<float> d_o, d_d;
+    DeviceTemp<pt::HitOut> d_h;
+    HIP_TRY(c, d_o.alloc((size_t)n * 3));
+    HIP_TRY(c, d_d.alloc((size_t)n * 3));
+    HIP_TRY(c, d_h.alloc((size_t)n));
+    HIP_TRY(c, hipMemcpyAsync(d_o.p, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_d.p, directions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    if (int rc = launch_ray_query(c, PTRT_QUERY_CLOSEST, d_o.p, d_d.p, nullptr, (size_t)n, d_h.p))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, d_h.p, (size_t)n * sizeof(pt::HitOut), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PTRT_OK;
+}
+
+int ptrt_query_rays(ptrt_ctx *c, int kind, const float *origins, const float *directions, const float *tmax, int n, void *out) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: bad context");
+    if (kind != PTRT_QUERY_CLOSEST && kind != PTRT_QUERY_OCCLUDED)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: kind %d (PTRT_QUERY_CLOSEST or PTRT_QUERY_OCCLUDED)", kind);
+    if (n < 0 || !origins || !directions || !out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: bad argument (n %d, origins %p, directions %p, out %p)", n,
+                    (const void *)origins, (const void *)directions, out);
+    if (kind == PTRT_QUERY_OCCLUDED && !tmax)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: PTRT_QUERY_OCCLUDED needs tmax");
+    if (kind == PTRT_QUERY_CLOSEST && tmax)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_rays: PTRT_QUERY_CLOSEST takes no tmax (pass NULL)");
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_rays: geometry not uploaded");
+    if (n == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const size_t rays = (size_t)n;
+    const Span so{"origins", origins, rays * 12}, sd{"directions", directions, rays * 12}, st{"tmax", tmax, rays * sizeof(float)},
+        sout{"out", out, rays * (kind == PTRT_QUERY_CLOSEST ? sizeof(pt::HitOut) : sizeof(int32_t))};
+    if (int rc = tmax ? check_spans(c, "ptrt_query_rays", {so, sd, st, sout}) : check_spans(c, "ptrt_query_rays", {so, sd, sout}))
+        return rc;
+    return launch_ray_query(c, kind, origins, directions, tmax, rays, out);
+}
+
+int ptrt_query_radiance(ptrt_ctx *c, const float *origins, const float *directions, uint32_t *rng_states, int n, int samples,
+                        int max_depth, ptrt_radiance *out) {
+    static_assert(sizeof(pt::RadianceOut) == sizeof(ptrt_radiance) && sizeof(ptrt_radiance) == 32, "RadianceOut must mirror ptrt_radiance");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: bad context");
+    if (n < 0 || !origins || !directions || !rng_states || !out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_radiance: bad argument (n %d, origins %p, directions %p, rng_states %p, out %p)", n,
+                    (const void *)origins, (const void *)directions, (const void *)rng_states, (const void *)out);
+    if (int rc = check_shading_query(c, "ptrt_query_radiance", samples, max_depth, nullptr))
+        return rc;
+    if (n == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const size_t rays = (size_t)n;
+    if (int rc = check_spans(c, "ptrt_query_radiance", {{"origins", origins, rays * 12}, {"directions", directions, rays * 12},
+                                                        {"rng_states", rng_states, rays * 24}, {"out", out, rays * sizeof(ptrt_radiance)}}))
+        return rc;
+    QueryPlan P;
+    if (int rc = plan_query(c, true, samples, max_depth, P))
+        return rc;
+    // radiance_query_kernel (pt_radiance.hip.h) over the n rays and their generator states
+    pt::RadianceOut *o = reinterpret_cast<pt::RadianceOut *>(out);
+    auto launch = [&](auto FULL) {
+        return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+            return launch_persistent(c, pt::radiance_query_kernel<G, FULL, PM>, P.lds, (rays + 63) / 64, true, P.K, origins, directions,
+                                     rng_states, rays, o);
+        });
+    };
+    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+}
+
+int ptrt_query_probes(ptrt_ctx *c, const float *d_positions, int n_probes, const float *d_directions, int n_dirs,
+                      uint32_t *d_rng_states, int samples, int max_depth, float max_distance, ptrt_probe *d_out) {
+    static_assert(sizeof(pt::ProbeOut) == sizeof(ptrt_probe) && sizeof(ptrt_probe) == 128, "ProbeOut must mirror ptrt_probe");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: bad context");
+    if (n_probes < 0 || n_dirs < 1 || !d_positions || !d_directions || !d_rng_states || !d_out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: bad argument (n_probes %d, n_dirs %d, positions %p, directions %p, rng_states %p, out %p)",
+                    n_probes, n_dirs, (const void *)d_positions, (const void *)d_directions, (const void *)d_rng_states, (const void *)d_out);
+    if (int rc = check_shading_query(c, "ptrt_query_probes", samples, max_depth, &max_distance))
+        return rc;
+    if (n_probes == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    // byte counts in size_t: n_probes * n_dirs rays is below 2^62 and fits; times 24 bytes of state it need not
+    const size_t probes = (size_t)n_probes, ndirs = (size_t)n_dirs, rays = probes * ndirs;
+    if (rays > SIZE_MAX / 24)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probes: %d probes x %d directions: the states' byte count overflows", n_probes, n_dirs);
+    if (int rc = check_spans(c, "ptrt_query_probes", {{"positions", d_positions, probes * 12}, {"directions", d_directions, ndirs * 12},
+                                                      {"rng_states", d_rng_states, rays * 24}, {"out", d_out, probes * sizeof(ptrt_probe)}}))
+        return rc;
+    QueryPlan P;
+    if (int rc = plan_query(c, true, samples, max_depth, P))
+        return rc;
+    // probe_query_kernel (pt_probe.hip.h): the grid strides over probes, one wave per probe
+    pt::ProbeOut *o = reinterpret_cast<pt::ProbeOut *>(d_out);
+    auto launch = [&](auto FULL) {
+        return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+            return launch_persistent(c, pt::probe_query_kernel<G, FULL, PM>, P.lds, probes, true, P.K, d_positions, n_probes, d_directions,
+                                     n_dirs, d_rng_states, max_distance, o);
+        });
+    };
+    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+}
+
+int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins, float *d_directions) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: bad context");
+    if (frame_index < 0 || sample < 0 || frame_index > INT_MAX - sample)
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: frame_index=%d sample=%d", frame_index, sample);
+    if (!d_origins || !d_directions)
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: a target is NULL");
+    if (c->cam.lens_radius > 0.0f)
+        return fail(c, PTRT_E_INVALID, "ptrt_camera_rays: a thin lens (lens_radius %g): the lens sample of a primary ray is drawn "
+                                       "from the pixel's generator stream", (double)c->cam.lens_radius);
+    if (int rc = set_device(c))
+        return rc;
+    pt::KParams K = make_params(c);
+    K.frame_count = frame_index + sample;
+    const size_t rays = (size_t)K.rows * K.width;
+    if (int rc = check_spans(c, "ptrt_camera_rays", {{"d_origins", d_origins, rays * 12}, {"d_directions", d_directions, rays * 12}}))
+        return rc;
+    c->touched = true;
+    hipLaunchKernelGGL(pt::camera_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, c->stream, K, d_origins, d_directions);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_init_rng_states(ptrt_ctx *c, unsigned long long seed, unsigned long long first_subsequence, int n, uint32_t *d_states) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: bad context");
+    if (n < 0 || !d_states)
+        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: bad argument (n %d, d_states %p)", n, (const void *)d_states);
+    if (n == 0)
+        return PTRT_OK;
+    const unsigned long long last = first_subsequence + (unsigned long long)(n - 1);
+    if (last < first_subsequence)
+        return fail(c, PTRT_E_INVALID, "ptrt_init_rng_states: subsequence numbers beyond 2^64");
+    if (int rc = set_device(c))
+        return rc;
+    if (int rc = check_spans(c, "ptrt_init_rng_states", {{"d_states", d_states, (size_t)n * 24}}))
+        return rc;
+    if (int rc = ensure_jump(c, last, "ptrt_init_rng_states"))
+        return rc;
+    const XorwowSeed s = xorwow_seed(seed);
+    c->touched = true;
+    hipLaunchKernelGGL(pt::rng_states_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream, d_states, (size_t)n,
+                       first_subsequence, s.d, s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], c->d_jump, c->n_jump);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+} // extern "C"

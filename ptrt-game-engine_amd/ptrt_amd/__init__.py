@@ -635,16 +635,8 @@ class Scene:
         if not tensor.is_contiguous() or tensor.dim() != 2 or tensor.shape[1] * tensor.element_size() != rec:
             raise ValueError(f"set_instance_transforms_device: needs a contiguous (count, {rec} bytes) tensor, got "
                              f"{tuple(tensor.shape)} of {tensor.dtype}")
-        self._order_behind_torch(tensor)
-        self._cchk(lib.ptrt_set_instance_transforms_device(self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr())))
-
-    def _order_behind_torch(self, tensor):
-        """the context's stream waits for what torch's current stream holds now"""
-        import torch
-        cur = torch.cuda.current_stream(tensor.device)
-        ctx_stream = torch.cuda.ExternalStream(self.get_option("stream"), device=tensor.device)
-        if ctx_stream.cuda_stream != cur.cuda_stream:
-            ctx_stream.wait_stream(cur)
+        self._enqueue_between_streams(tensor.device, lambda: self._cchk(lib.ptrt_set_instance_transforms_device(
+            self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr()))), back=False)
 
     def set_instance_poses_device(self, first, tensor):
         """`ptrt_set_instance_poses_device`: meshes first .. first + count - 1 take their has_transform bit and matrices from the
@@ -660,8 +652,8 @@ class Scene:
         if not tensor.is_contiguous() or tensor.dim() != 2 or tensor.shape[1] != 9 or tensor.dtype != torch.float32:
             raise ValueError(f"set_instance_poses_device: needs a contiguous (count, 9) float32 tensor, got "
                              f"{tuple(tensor.shape)} of {tensor.dtype}")
-        self._order_behind_torch(tensor)
-        self._cchk(lib.ptrt_set_instance_poses_device(self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr())))
+        self._enqueue_between_streams(tensor.device, lambda: self._cchk(lib.ptrt_set_instance_poses_device(
+            self.ctx, int(first), int(tensor.shape[0]), _vp(tensor.data_ptr()))), back=False)
 
     def read_instance_transforms(self, first=0, count=None):
         """The has_transform bits and matrices the device's mesh records hold now (ptrt_read_instance_transforms; synchronises):
@@ -899,20 +891,10 @@ class Scene:
         out = torch.empty((n, 16) if closest else (n,), dtype=torch.int32, device=dev)
         if n == 0:
             return out
-        # stream order both ways, by events: the context's stream waits for what torch enqueued before the call (the rays),
-        # torch's current stream for the query (whoever reads the answer)
-        cur = torch.cuda.current_stream(dev)
-        ctx_stream = torch.cuda.ExternalStream(self.get_option("stream"), device=dev)
-        other = ctx_stream.cuda_stream != cur.cuda_stream
-        if other:
-            ctx_stream.wait_stream(cur)
         p = [_vp(a.data_ptr()) for a in arrays]
-        if closest:
-            self._chk(lib.hs_query_closest(self._h, p[0], p[1], n, _vp(out.data_ptr())))
-        else:
-            self._chk(lib.hs_query_occluded(self._h, p[0], p[1], p[2], n, _vp(out.data_ptr())))
-        if other:
-            cur.wait_stream(ctx_stream)
+        self._enqueue_between_streams(dev, lambda: self._chk(
+            lib.hs_query_closest(self._h, p[0], p[1], n, _vp(out.data_ptr())) if closest else
+            lib.hs_query_occluded(self._h, p[0], p[1], p[2], n, _vp(out.data_ptr()))))
         return out
 
     # ---- path-traced radiance for caller-supplied rays (ptrt_query_radiance through Scene::queryRadiance) ----
@@ -927,9 +909,10 @@ class Scene:
         if not a.is_contiguous():
             raise ValueError(f"{what}: tensors must be contiguous")
 
-    def _enqueue_between_streams(self, dev, call):
-        """`call()` enqueues on the context's stream: that stream waits for what torch's current stream holds, torch's
-        current stream for the call (the convention of query_closest)"""
+    def _enqueue_between_streams(self, dev, call, back=True):
+        """`call()` enqueues on the context's stream.  Stream order by events, both ways: the context's stream waits for what
+        torch enqueued on its current stream before the call (the inputs), and torch's current stream waits for the call
+        (whoever reads the answer there).  `back=False`: the first half only, for a call that leaves nothing to read."""
         import torch
         cur = torch.cuda.current_stream(dev)
         ctx_stream = torch.cuda.ExternalStream(self.get_option("stream"), device=dev)
@@ -937,7 +920,7 @@ class Scene:
         if other:
             ctx_stream.wait_stream(cur)
         call()
-        if other:
+        if other and back:
             cur.wait_stream(ctx_stream)
 
     def query_radiance(self, origins, directions, rng_states, samples=1, max_depth=None, out=None):
