@@ -21,9 +21,11 @@
 //     is just big enough to fill the chip (persistent waves).
 //
 // Per pixel the random numbers are drawn in the reference's order and every float is combined in the
-// reference's order (the code between the traces is phases [A], [C], [E] of path_trace_kernel), so
-// the bits are the megakernel's and the oracle's: tests/test_async_gpu.py.
+// reference's order (the code between the traces is phases [A], [C], [E] of path_trace_kernel, the
+// vertex of tracePath through the functions of pt_path.hip.h), so the bits are the megakernel's and
+// the oracle's: tests/test_async_gpu.py.
 #pragma once
+#include "pt_path.hip.h"
 #include "pt_wavefront.hip.h"
 
 namespace pt {
@@ -141,20 +143,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                             K.depth[idx] = 1e30f;
                             K.object_id[idx] = -1;
                         }
-                        if (K.use_sky) {
-                            if (K.env) {
-                                const float phi = det_atan2(rd.z, rd.x);
-                                const float theta = det_acos(max_(-1.0f, min_(1.0f, rd.y)));
-                                const float u = (phi + PI_F) * (1.0f / TWO_PI_F);
-                                const float v = theta * (1.0f / PI_F);
-                                acc = acc + throughput * tex2d_env(K.env, K.env_w, K.env_h, u, v);
-                            } else {
-                                const float t = 0.5f * (rd.y + 1.0f);
-                                acc = acc + throughput * lerp(K.sky_bottom, K.sky_top, t);
-                            }
-                        } else {
-                            acc = acc + throughput * mk3(0.0f);
-                        }
+                        add_miss_radiance(K, rd, throughput, acc);
                         end_path = true;
                     } else {
                         run_e = true;
@@ -167,61 +156,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                             K.object_id[idx] = h.mesh;
                         }
                         const float4 m0 = K.materials[h.mesh * 6 + 0], m2 = K.materials[h.mesh * 6 + 2];
-                        if (!hit.front_face) {
-                            const f3 T_unit = mk3(max_(1e-6f, m0.x), max_(1e-6f, m0.y), max_(1e-6f, m0.z));
-                            const f3 absorption = mk3(-det_log(T_unit.x), -det_log(T_unit.y), -det_log(T_unit.z));
-                            throughput = throughput * beerLambert(absorption, hit.t);
-                        }
-                        if (m2.x > 0.0f || m2.y > 0.0f || m2.z > 0.0f) {
-                            if (bounce == 0 || prev_was_specular)
-                                acc = acc + throughput * mk3(m2.x, m2.y, m2.z);
-                        }
+                        absorb_and_emit(m0, m2, hit, bounce == 0 || prev_was_specular, throughput, acc);
                         if (!ray_spec && K.n_lights > 0) {
-                            float r = rng_uniform(rng);
-                            r = min_(r, 0.99999994f);
-                            const int light_index = (int)(r * (float)K.n_lights);
-                            const LightRec light = load_light(K.lights, light_index);
-                            const float pdf_pick = 1.0f / (float)K.n_lights;
-                            float attenuation = 1.0f;
-                            float light_dist = 1e30f;
-                            const f3 light_radiance = light.color * light.intensity;
-                            if (light.type == 1) {
-                                L = -light.direction;
-                                pdf_sample = pdf_pick;
-                            } else {
-                                const f3 toLight = light.position - hit.point;
-                                const float light_dist_sq = dot(toLight, toLight);
-                                light_dist = sqrt_ieee(light_dist_sq);
-                                if (light.radius <= 0.0f) {
-                                    L = toLight / light_dist;
-                                    pdf_sample = pdf_pick;
-                                } else {
-                                    float sin_theta_max_sq = (light.radius * light.radius) / light_dist_sq;
-                                    sin_theta_max_sq = min_(sin_theta_max_sq, 0.9999f);
-                                    const float cos_theta_max = sqrt_ieee(1.0f - sin_theta_max_sq);
-                                    L = sample_cone_direction(rng, toLight / light_dist, cos_theta_max);
-                                    const float solid_angle = TWO_PI_F * (1.0f - cos_theta_max);
-                                    pdf_sample = (solid_angle > 1e-6f) ? (pdf_pick / solid_angle) : pdf_pick;
-                                }
-                                attenuation = attenuate(light_dist, light.range);
-                                if (light.type == 2) {
-                                    const float theta = dot(L, -light.direction);
-                                    const float epsilon = light.inner - light.outer;
-                                    float spotIntensity;
-                                    if (epsilon <= 1e-6f)
-                                        spotIntensity = (theta >= light.outer) ? 1.0f : 0.0f;
-                                    else
-                                        spotIntensity = clampf((theta - light.outer) / epsilon, 0.0f, 1.0f);
-                                    attenuation *= spotIntensity;
-                                }
-                            }
-                            const f3 shadow_offset = dot(hit.normal, L) > 0.0f ? hit.normal * 1e-4f : -hit.normal * 1e-4f;
-                            light_scale = light_radiance;
-                            light_att = attenuation;
+                            const LightRec light = load_light(K.lights, pick_light(rng, K.n_lights));
+                            // this lane's next ray is its shadow ray (origin and length straight into ro, tm); [E] follows
+                            // when that is finished
+                            sample_light(light, K.n_lights, hit, rng, L, pdf_sample, light_scale, light_att, ro, tm);
                             ++n_shadow;
-                            // this lane's next ray is its shadow ray; [E] follows when that is finished
-                            ro = hit.point + shadow_offset;
-                            tm = light_dist - 1e-3f;
                             anyq = true;
                             newray = true;
                             run_e = false;
@@ -230,47 +171,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                 }
                 if (run_e) { // ---- [E] (path_logic.cuh:357-381, 843-896)
                     const Material mat = load_material(K.materials, hmesh);
-                    const f3 V = -rd;
-                    if (want_shadow && !found) {
-                        const f3 bsdf = evaluateBSDF<FULL>(hit, mat, L, V);
-                        if (pdf_sample > 0.0f) {
-                            f3 direct = bsdf * light_scale * light_att / pdf_sample;
-                            direct = clamp_vector_soft(direct, 500.0f);
-                            if (direct.x > 0.0f || direct.y > 0.0f || direct.z > 0.0f) {
-                                const float pdf_brdf = material_pdf<FULL>(hit, mat, V, L);
-                                const float wgt = mis_weight(pdf_sample, pdf_brdf);
-                                acc = acc + throughput * direct * wgt;
-                            }
-                        }
+                    if (want_shadow && !found) { // the late [C2]: the sample's value once it is known to be visible
+                        f3 c;
+                        if (light_sample_value<FULL>(hit, mat, L, -rd, pdf_sample, light_scale, light_att, throughput, c))
+                            acc = acc + c;
                     }
-                    f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
-                    bool is_specular = false;
-                    if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular)) {
+                    if (!scatter_and_continue<FULL>(hit, mat, rng, K.max_depth, ro, rd, throughput, bounce, ray_spec, prev_was_specular))
                         end_path = true;
-                    } else {
-                        prev_was_specular = is_specular;
-                        bool killed = false;
-                        if (bounce >= 2) {
-                            const float p = max_(0.05f, min_(0.95f, max_(throughput.x, max_(throughput.y, throughput.z))));
-                            if (rng_uniform(rng) > p)
-                                killed = true;
-                            else
-                                throughput = throughput / p;
-                        }
-                        if (killed) {
-                            end_path = true;
-                        } else {
-                            throughput = throughput * att;
-                            throughput = clamp_vector_soft(throughput, 50.0f);
-                            const f3 off = hit.normal * 1e-4f;
-                            ro = (dot(scatter_dir, hit.normal) > 0.0f) ? (hit.point + off) : (hit.point - off);
-                            rd = scatter_dir;
-                            ray_spec = is_specular;
-                            ++bounce;
-                            if (bounce >= K.max_depth)
-                                end_path = true;
-                        }
-                    }
                     if (!end_path) {
                         anyq = false;
                         newray = true;

@@ -7,6 +7,9 @@
 //        (reference: path_trace_kernel scene_kernels.cuh:122-194 -> tracePath
 //        path_logic.cuh:782-899 -> traceRay intersection.cuh:526-605, and
 //        tonemap_kernel scene.cuh:2004-2047)
+//        Its shading phases [C]-[E] are tracePath's body written for that kernel's registers; the other
+//        loops over paths (pt_wavefront, pt_async, pt_radiance / pt_probe) share one statement of the same
+//        vertex, pt_path.hip.h, which needs LightRec, Surface, Material and Rng from here.
 //   xorwow_init_kernel            init_curand_kernel (scene_kernels.cuh:26-35)
 //   trace_rays_kernel             trace_single_ray_kernel (scene_kernels.cuh:38-49), batched
 //

@@ -11,11 +11,12 @@
 //
 // The frame is ray_query_kernel's (pt_query.hip.h): a persistent grid of one-wave workgroups, a grid-stride loop over chunks of
 // 64 rays, dead lanes of the tail chunk taking part in the wave's collectives, size_t indices, the same LDS carve and staging,
-// the same traversal by PMODE.  Per chunk the 64 lanes run the path loop in lock step -- closest hit, the shading of tracePath
-// stated operation by operation as phases [C], [C2], [D], [E] of path_trace_kernel and wf_shade_path state it, the light
-// sample's shadow ray, the scatter -- until no lane has a path left, then the next sample.  No lane refill, no staged shading
-// inputs, no counters: a lane whose path has ended idles until the chunk's longest path is done.
+// the same traversal by PMODE.  Per chunk the 64 lanes run the path loop in lock step -- closest hit, the vertex of tracePath
+// through the functions of pt_path.hip.h in the phases [C], [C2], [D], [E] of path_trace_kernel, the light sample's shadow ray
+// between its value and its addition, the scatter -- until no lane has a path left, then the next sample.  No lane refill, no
+// staged shading inputs, no counters: a lane whose path has ended idles until the chunk's longest path is done.
 #pragma once
+#include "pt_path.hip.h"
 #include "pt_query.hip.h"
 
 namespace pt {
@@ -78,20 +79,7 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
                 if (h.mesh < 0) {
                     if (s == 0 && bounce == 0) // first hit of the first sample (scene_kernels.cuh:181-193): HitInfo() defaults
                         first(1e30f, mk3(0.0f), -1);
-                    if (KC.use_sky) { // sampleSky (render_utils.cuh:115-137): gradient, or the equirect map
-                        if (KC.env) {
-                            const float phi = det_atan2(rd.z, rd.x);
-                            const float theta = det_acos(max_(-1.0f, min_(1.0f, rd.y)));
-                            const float u = (phi + PI_F) * (1.0f / TWO_PI_F);
-                            const float v = theta * (1.0f / PI_F);
-                            acc = acc + throughput * tex2d_env(KC.env, KC.env_w, KC.env_h, u, v);
-                        } else {
-                            const float t = 0.5f * (rd.y + 1.0f);
-                            acc = acc + throughput * lerp(KC.sky_bottom, KC.sky_top, t);
-                        }
-                    } else {
-                        acc = acc + throughput * mk3(0.0f);
-                    }
+                    add_miss_radiance(KC, rd, throughput, acc);
                     end_path = true;
                 } else {
                     shaded = true;
@@ -99,62 +87,11 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
                     if (s == 0 && bounce == 0)
                         first(hit.t, hit.normal, h.mesh);
                     const float4 m0 = KC.materials[h.mesh * 6 + 0], m2 = KC.materials[h.mesh * 6 + 2];
-                    if (!hit.front_face) { // Beer-Lambert on back faces (path_logic.cuh:823-829)
-                        const f3 T_unit = mk3(max_(1e-6f, m0.x), max_(1e-6f, m0.y), max_(1e-6f, m0.z));
-                        const f3 absorption = mk3(-det_log(T_unit.x), -det_log(T_unit.y), -det_log(T_unit.z));
-                        throughput = throughput * beerLambert(absorption, hit.t);
-                    }
-                    if (m2.x > 0.0f || m2.y > 0.0f || m2.z > 0.0f) {
-                        if (bounce == 0 || prev_was_specular)
-                            acc = acc + throughput * mk3(m2.x, m2.y, m2.z);
-                    }
+                    absorb_and_emit(m0, m2, hit, bounce == 0 || prev_was_specular, throughput, acc);
                     // light sample of next-event estimation (path_logic.cuh:305-382, 840)
                     if (!ray_spec && KC.n_lights > 0) {
-                        float r = rng_uniform(rng);
-                        r = min_(r, 0.99999994f);
-                        const int light_index = (int)(r * (float)KC.n_lights);
-                        const LightRec light = load_light(KC.lights, light_index);
-                        const float pdf_pick = 1.0f / (float)KC.n_lights;
-                        float attenuation = 1.0f;
-                        float light_dist = 1e30f;
-                        const f3 light_radiance = light.color * light.intensity;
-                        if (light.type == 1) {
-                            L = -light.direction;
-                            pdf_sample = pdf_pick;
-                        } else {
-                            const f3 toLight = light.position - hit.point;
-                            const float light_dist_sq = dot(toLight, toLight);
-                            light_dist = sqrt_ieee(light_dist_sq);
-                            if (light.radius <= 0.0f) {
-                                L = toLight / light_dist;
-                                pdf_sample = pdf_pick;
-                            } else {
-                                float sin_theta_max_sq = (light.radius * light.radius) / light_dist_sq;
-                                sin_theta_max_sq = min_(sin_theta_max_sq, 0.9999f);
-                                const float cos_theta_max = sqrt_ieee(1.0f - sin_theta_max_sq);
-                                L = sample_cone_direction(rng, toLight / light_dist, cos_theta_max);
-                                const float solid_angle = TWO_PI_F * (1.0f - cos_theta_max);
-                                pdf_sample = (solid_angle > 1e-6f) ? (pdf_pick / solid_angle) : pdf_pick;
-                            }
-                            attenuation = attenuate(light_dist, light.range);
-                            if (light.type == 2) {
-                                const float theta = dot(L, -light.direction);
-                                const float epsilon = light.inner - light.outer;
-                                float spotIntensity;
-                                if (epsilon <= 1e-6f)
-                                    spotIntensity = (theta >= light.outer) ? 1.0f : 0.0f;
-                                else
-                                    spotIntensity = clampf((theta - light.outer) / epsilon, 0.0f, 1.0f);
-                                attenuation *= spotIntensity;
-                            }
-                        }
-                        const f3 shadow_offset = dot(hit.normal, L) > 0.0f ? hit.normal * 1e-4f : -hit.normal * 1e-4f;
-                        shadow_o = hit.point + shadow_offset;
-                        shadow_tmax = light_dist - 1e-3f;
-                        // bsdf * light_radiance * attenuation / pdf: the last three factors are kept apart so the product is
-                        // formed in the reference's order
-                        light_scale = light_radiance;
-                        light_att = attenuation;
+                        const LightRec light = load_light(KC.lights, pick_light(rng, KC.n_lights));
+                        sample_light(light, KC.n_lights, hit, rng, L, pdf_sample, light_scale, light_att, shadow_o, shadow_tmax);
                         want_shadow = true;
                     }
                 }
@@ -167,18 +104,7 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
             f3 lit_now = mk3(0.0f);
             if (want_shadow) {
                 const Material mat = load_material(KC2.materials, h.mesh);
-                const f3 V = -rd;
-                const f3 bsdf = evaluateBSDF<FULL>(hit, mat, L, V);
-                if (pdf_sample > 0.0f) {
-                    f3 direct = bsdf * light_scale * light_att / pdf_sample;
-                    direct = clamp_vector_soft(direct, 500.0f);
-                    if (direct.x > 0.0f || direct.y > 0.0f || direct.z > 0.0f) {
-                        const float pdf_brdf = material_pdf<FULL>(hit, mat, V, L);
-                        const float wgt = mis_weight(pdf_sample, pdf_brdf);
-                        lit_now = throughput * direct * wgt;
-                        lit = true;
-                    }
-                }
+                lit = light_sample_value<FULL>(hit, mat, L, -rd, pdf_sample, light_scale, light_att, throughput, lit_now);
             }
             // ---- [D] shadow rays, all lanes that have one together (bvh_any_hit_tlas); the contribution is added once its
             // visibility is known and before anything else touches the path's radiance
@@ -195,34 +121,8 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
             const KParams &KE = kparams(kp0);
             if (shaded) {
                 const Material mat = load_material(KE.materials, h.mesh);
-                f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
-                bool is_specular = false;
-                if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular)) {
+                if (!scatter_and_continue<FULL>(hit, mat, rng, KE.max_depth, ro, rd, throughput, bounce, ray_spec, prev_was_specular))
                     end_path = true;
-                } else {
-                    prev_was_specular = is_specular;
-                    bool killed = false;
-                    if (bounce >= 2) { // Russian roulette (path_logic.cuh:871-880)
-                        const float p = max_(0.05f, min_(0.95f, max_(throughput.x, max_(throughput.y, throughput.z))));
-                        if (rng_uniform(rng) > p)
-                            killed = true;
-                        else
-                            throughput = throughput / p;
-                    }
-                    if (killed) {
-                        end_path = true;
-                    } else {
-                        throughput = throughput * att;
-                        throughput = clamp_vector_soft(throughput, 50.0f);
-                        const f3 off = hit.normal * 1e-4f;
-                        ro = (dot(scatter_dir, hit.normal) > 0.0f) ? (hit.point + off) : (hit.point - off);
-                        rd = scatter_dir;
-                        ray_spec = is_specular;
-                        ++bounce;
-                        if (bounce >= KE.max_depth)
-                            end_path = true;
-                    }
-                }
             }
             if (act && end_path) { // the sample is complete (scene_kernels.cuh:170-171)
                 acc = clamp_vector_soft(acc, 100.0f);

@@ -2353,7 +2353,7 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         phase_prio<PMODE, 2, 1>();
         const KParams &KC = kparams(kp0);
         const unsigned long long t_pc = TS_NOW();
-        // ---- [C] first half of the shading
+        // ---- [C] first half of the shading ([C]-[E] are the vertex pt_path.hip.h states for the other loops: a change here is a change there)
         bool end_path = false, shaded = false, want_shadow = false;
         Surface hit;
         hit.point = hit.normal = mk3(0.0f);

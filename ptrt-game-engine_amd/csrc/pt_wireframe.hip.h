@@ -10,6 +10,7 @@
 // the arithmetic is the one tests/wireframe_restatement.py restates on the CPU.
 #pragma once
 #include "pt_kernels.hip.h"
+#include "pt_path.hip.h"
 
 namespace pt {
 
@@ -80,16 +81,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GEOM == 2 ? 
         }
     }
     if (!edge && K.use_sky) { // sampleSky (render_utils.cuh:115-137), as the path kernel restates it at a miss
-        if (K.env) {
-            const float phi = det_atan2(rd.z, rd.x);
-            const float theta = det_acos(max_(-1.0f, min_(1.0f, rd.y)));
-            const float u = (phi + PI_F) * (1.0f / TWO_PI_F);
-            const float v = theta * (1.0f / PI_F);
-            c = tex2d_env(K.env, K.env_w, K.env_h, u, v);
-        } else {
-            const float tt = 0.5f * (rd.y + 1.0f);
-            c = lerp(K.sky_bottom, K.sky_top, tt);
-        }
+        c = sample_sky(K, rd);
     }
     c = c / (c + mk3(1.0f));
     const f3 rgb = clampv(mk3(wire_gamma(c.x), wire_gamma(c.y), wire_gamma(c.z)), 0.0f, 1.0f) * 255.99f;

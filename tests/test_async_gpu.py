@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from common import assert_frames_equal, bits, render_both
+from test_wavefront_gpu import light_lab_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -105,3 +106,14 @@ def test_equals_megakernel_at_scale(P, blue_noise):
         assert b["stats"]["shadow_rays_walked"] == b["stats"]["shadow_rays"] >= a["stats"]["shadow_rays_walked"]
         strip = lambda d: {k: v for k, v in d.items() if k != "shadow_rays_walked"}
         assert strip(a["stats"]) == strip(b["stats"])
+
+
+@pytest.mark.parametrize("sky", ["off", "gradient", "env"])
+def test_every_light_type_and_sky_equals_megakernel(P, sky):
+    """The light lab of tests/path_truth.py under its light set G (directional, point and spot lights, with and without a radius,
+    soft and hard edges) and every kind of sky: every buffer and the generator states the megakernel's."""
+    mega, lanes, m = light_lab_frame(P, sky, "async_lanes")
+    assert m == 2
+    assert mega["accum"].any() and (mega["object_id"] < 0).any() and (mega["object_id"] >= 0).any()
+    for k in ("accum", "normal", "depth", "object_id", "rgb8", "rng"):
+        assert np.array_equal(bits(mega[k]), bits(lanes[k])), k

@@ -5,6 +5,7 @@ the oracle would be slow."""
 import numpy as np
 import pytest
 
+import path_truth as PT
 from common import assert_frames_equal, bits, render_both
 
 pytestmark = pytest.mark.gpu
@@ -108,3 +109,57 @@ def test_equals_megakernel_at_scale(P, blue_noise):
             for k in ("accum", "normal", "depth", "object_id", "rgb8", "rng"):
                 assert np.array_equal(bits(a[k]), bits(b[k])), k
             assert a["stats"] == b["stats"]
+
+
+def light_lab_frame(P, sky, option):
+    """One 64x64 frame, 2 spp, 4 bounces, of the light lab of tests/path_truth.py under its light set G -- a directional light,
+    point lights without and with a radius, spots with a soft and with a hard edge (inner == outer), one of them with a radius,
+    two of range 2 -- and sky `sky` of PT.SKIES: the megakernel's buffers and generator states, then those with `option` on and
+    the render mode that took."""
+    out = []
+    for on in (0, 1):
+        s = P.Scene(64, 64)
+        PT.light_lab(P, s)
+        s.setCamera((0.0, 3.5, 10.0), (0.0, 0.0, 0.0), (0, 1, 0), 45.0)
+        for L in PT.LIGHT_SETS["G"]:
+            kw = dict(intensity=L["intensity"])
+            if L["type"] != PT.LIGHT_DIRECTIONAL:
+                kw.update(range=L["range"], radius=L.get("radius", 0.0))
+            if L["type"] == PT.LIGHT_DIRECTIONAL:
+                s.addDirectionalLight(L["direction"], L["color"], **kw)
+            elif L["type"] == PT.LIGHT_POINT:
+                s.addPointLight(L["position"], L["color"], **kw)
+            else:  # (the scene takes the cone's angles and keeps their cosines: equal angles, equal cosines)
+                s.addSpotLight(L["position"], L["direction"], L["color"], inner=float(np.arccos(L["inner"])),
+                               outer=float(np.arccos(L["outer"])), **kw)
+        w = PT.SKIES[sky]()
+        if w.use:
+            s.setSkyGradient(tuple(w.top), tuple(w.bottom))
+            if w.env is not None:
+                s.setEnvironmentMap(w.env)
+        else:
+            s.disableSky()
+        s.setPerfSamplesPerPixel(2)
+        s.setMaxBounceDepth(4)
+        s.setDenoiserEnabled(False)
+        s.setBloomEnabled(False)
+        s.initBlueNoise()
+        s.uploadToGPU()
+        s.set_option(option, on)
+        rgb = s.render_to_host()
+        out.append(dict(accum=s.read(P.BUF_ACCUM), normal=s.read(P.BUF_NORMAL), depth=s.read(P.BUF_DEPTH),
+                        object_id=s.read(P.BUF_OBJECT_ID), rgb8=rgb, rng=s.read(P.BUF_RNG)))
+        m = mode(P, s)
+        s.close()
+    return out[0], out[1], m
+
+
+@pytest.mark.parametrize("sky", ["off", "gradient", "env"])
+def test_every_light_type_and_sky_equals_megakernel(P, sky):
+    """Cornell and showcase have point lights with a radius only, and no sky but the gradient: the light lab under light set G
+    through the stages, every buffer and the generator states the megakernel's."""
+    mega, staged, m = light_lab_frame(P, sky, "wavefront")
+    assert m == 1
+    assert mega["accum"].any() and (mega["object_id"] < 0).any() and (mega["object_id"] >= 0).any()
+    for k in ("accum", "normal", "depth", "object_id", "rgb8", "rng"):
+        assert np.array_equal(bits(mega[k]), bits(staged[k])), k
