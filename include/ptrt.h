@@ -768,6 +768,20 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         (default) and 1: on when pm1_full_leaf is; 0: the 2^sh rule.  Closest-hit traces of a scene with an
  *                         instanced mesh keep one lane per pair.  The batched ray queries share the loops.  ptrt_get_option
  *                         "pm1_lane_groups_eff" says what the last frame or ray query did.
+ *   plain_leaf -1|0|1     PMODE 1 and 2 (the traversals that build their (ray, mesh) pair lists with build_pairs over a single-leaf
+ *                         TLAS; PMODE 4 builds its merged list with root tests of its own and does not read it): when no mesh of
+ *                         the leaf has a transform and every mesh's root box lies inside the TLAS root box (fp32, component by
+ *                         component; derived by ptrt_upload_geometry, ptrt_plain_leaf says it without a device), the pair
+ *                         builder leaves out the TLAS root-box test -- a ray that misses the root passes no mesh's test, the slab
+ *                         arithmetic is monotone -- and PMODE 1's pair batches the instance flag test and the t / dirScale
+ *                         quotient of the merge.  Same pair list, same bits.  -1 (default) and 1: on where the
+ *                         upload derived it (1 never forces it); 0: never.  Whatever lets the device move a box or a transform
+ *                         unseen by the host -- ptrt_refit, ptrt_build_bvh, ptrt_refit_tlas, ptrt_reorder_tlas,
+ *                         ptrt_update_instances, ptrt_set_instance_transforms_device, ptrt_set_instance_poses_device -- turns it
+ *                         off until the next ptrt_upload_geometry.  ptrt_get_option "plain_leaf_eff" says what the last frame or
+ *                         query did (0 as well under another traversal mode, PMODE 4 among them).  The value travels with a
+ *                         launch's arguments: a frame recorded into a caller's hipGraph keeps the value from when it was captured,
+ *                         as it keeps pair_split and the transform flag -- record again after any of the calls above.
  *   tile_run 0..64        the one-tile-per-workgroup kernels' workgroup -> tile map.  Consecutive workgroups go to the eight XCDs in
  *                         turn; with n > 0, of every 8 n consecutive tiles XCD x renders tiles [x n, (x + 1) n) -- neighbours,
  *                         whose rays walk the same part of the trees, share an L2 -- instead of every eighth tile.  8 (default):
@@ -810,6 +824,12 @@ int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
 int ptrt_pm1_plan(int leaf_triangles, int32_t *out_g63, int32_t *out_take63, int32_t *out_mul63, int32_t *out_cost63,
                   int32_t *out_model2);
 int ptrt_pm1_div_mul(int g);
+
+/* What ptrt_upload_geometry derives for option "plain_leaf" from the same arrays; needs no device and no context.  1: the TLAS
+ * root is a single leaf, no mesh of it has a transform, and node 0's box of every mesh of the leaf lies inside the TLAS root
+ * box (fp32 compares, a NaN fails); 0: not so; -1: a missing array.  ABI 6, additions only. */
+int ptrt_plain_leaf(const ptrt_mesh_desc *meshes, int mesh_count, const ptrt_bvh_node *tlas_nodes, int tlas_node_count,
+                    const int32_t *tlas_mesh_indices, int tlas_index_count);
 
 /* Render on a caller-owned HIP stream (a `hipStream_t` passed as void*; NULL returns to the
  * context's own stream).  Lets a host that already orders work on a stream (a GL-interop map,

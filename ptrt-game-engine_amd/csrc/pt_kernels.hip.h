@@ -130,6 +130,10 @@ struct KParams {
     int ticket_tiles;    // lane-refill variant: consecutive tiles per ticket (>= 1)
     unsigned int *queue; // lane-refill variant: {next ticket of the launch's tile queue, waves that have left}; zero between launches
     unsigned long long *counters; // COUNTER_WORDS per slot: {extension, shadow, paths, zero-valued light samples} or nullptr
+    // PMODE 1, 2: no mesh of the leaf is instanced and every mesh box lies inside the TLAS root box (plain_leaf.h): build_pairs
+    // leaves out the root test, the PMODE 1 pair batches the instance arithmetic.  PMODE 4 (trace_merged,
+    // build_pairs_merged) does not read it.  Last, so that no other argument moved.
+    int plain_leaf;
 };
 constexpr int COUNTER_WORDS = 4;
 

@@ -291,6 +291,8 @@ struct CycleAcc {
             atomicAdd(&g_trav_stats[slot], (unsigned long long)__builtin_popcountll(ts_m));                                 \
     } while (0)
 // calls of build_pairs by the rays they carry behind the TLAS root test: [0..3] closest hit with 0, 1..16, 17..32, 33..64, [4..7] any hit
+// (with K.plain_leaf there is no root test and the live rays are counted as they come: set option plain_leaf to 0 for the
+// histograms DESIGN.md 3.18 and 3.20 quote)
 #define TS_RHIST(any, cond)                                                                                              \
     do {                                                                                                                 \
         const int ts_r = __builtin_popcountll(__builtin_amdgcn_ballot_w64(cond));                                        \
@@ -472,7 +474,11 @@ template <bool ANY, bool DENSE = false>
 PT_DEV int build_pairs(const KParams &K, const PairLds &L, int lane, bool alive, f3 o, f3 d, float tMax) {
     const RayO w = make_ray(o, d);
     float tE;
-    alive = alive && slab(tlas_bmin(K), tlas_bmax(K), w, ANY ? tMax : T_FAR, tE);
+    // (K.plain_leaf: every mesh box lies inside the root box and is tested with this same ray, so a ray that misses the root
+    // passes no mesh test below -- the list is the same without the root test and the two loads of its box, DESIGN.md 3.24.
+    // In the dense builder such a ray takes a rank and appends nothing.)
+    if (!K.plain_leaf)
+        alive = alive && slab(tlas_bmin(K), tlas_bmax(K), w, ANY ? tMax : T_FAR, tE);
     if (ANY)
         L.occ[DENSE ? lane_here(lane) : lane] = 0u;
     else
@@ -524,6 +530,14 @@ template <int GEN = 0> PT_DEV void pair_ray_from(const KParams &K, const int4 mt
         o = lo;
         d = normalize(ld);
     }
+}
+
+// world-space distance of a pair's best hit for the merge key: the local distance over the instance's direction scale.  Behind
+// an empty asm statement so that the quotient stays on the side of the wave-uniform branch its caller takes (without it the
+// division is speculated and issued whether or not any mesh is instanced).
+PT_DEV float pair_world_t(int flags, float tb, float dirScale) {
+    asm volatile("");
+    return (flags & 1) ? tb / dirScale : tb;
 }
 
 // PMODE 1, option "pm1_full_leaf": may this batch's triangle loop leave out the partial-leaf handling?  Wave-uniform.  The
@@ -589,8 +603,10 @@ PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool 
         // (every lane executes the shuffles: a source lane must be active for ds_bpermute)
         f3 po = mk3(__shfl(o.x, r), __shfl(o.y, r), __shfl(o.z, r));
         f3 pd = mk3(__shfl(d.x, r), __shfl(d.y, r), __shfl(d.z, r));
-        float dirScale;
-        pair_ray_from<false>(K, mt, po, pd, dirScale);
+        // (K.plain_leaf: no mesh of the leaf is instanced -- no flag test here, no quotient in the merge key below)
+        float dirScale = 1.0f;
+        if (!K.plain_leaf)
+            pair_ray_from<false>(K, mt, po, pd, dirScale);
         RayO pr;
         pr.o = po;
         pr.d = pd;
@@ -634,7 +650,9 @@ PT_DEV Hit closest_hit_pairs(const KParams &K, const PairLds &L, int lane, bool 
             }
         }
         if (valid && bi >= 0) {
-            const float tw = (mt.z & 1) ? tb / dirScale : tb;
+            float tw = tb;
+            if (!K.plain_leaf)
+                tw = pair_world_t(mt.z, tb, dirScale);
             const unsigned long long key =
                 ((unsigned long long)__float_as_uint(tw) << 32) | ((unsigned long long)(uint32_t)oi << 16) | (uint32_t)bi;
             __hip_atomic_fetch_min(&L.best[r], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -692,14 +710,16 @@ PT_DEV bool any_hit_pairs(const KParams &K, const PairLds &L, int lane, bool ali
         // (every lane executes the shuffles: a source lane must be active for ds_bpermute)
         f3 po = mk3(__shfl(o.x, r), __shfl(o.y, r), __shfl(o.z, r));
         f3 pd = mk3(__shfl(d.x, r), __shfl(d.y, r), __shfl(d.z, r));
-        float dirScale;
-        pair_ray_from<false>(K, mt, po, pd, dirScale);
+        float dirScale = 1.0f;
+        float tm = tmaxv[r];
+        if (!K.plain_leaf) { // (as in closest_hit_pairs)
+            pair_ray_from<false>(K, mt, po, pd, dirScale);
+            if (mt.z & 1)
+                tm = tm * dirScale;
+        }
         RayO pr;
         pr.o = po;
         pr.d = pd;
-        float tm = tmaxv[r];
-        if (mt.z & 1)
-            tm = tm * dirScale;
         bool found = false;
         const int iters = B.iters;
         take = B.take;

@@ -7,6 +7,7 @@
 // scene, launch on the context's stream, time kernels with HIP events.
 // There is no CPU rendering path in this library.
 #include "../../include/ptrt.h"
+#include "plain_leaf.h"
 #include "pt_build.hip.h"
 #include "pt_denoise.hip.h"
 #include "pt_post.hip.h"
@@ -137,6 +138,9 @@ struct ptrt_ctx {
     bool pair_leaf_uniform = false; // every leaf has exactly pair_max_leaf triangles
     pt::Pm1Plan pm1_plan{};         // ... then: the sub-batches of a pair-list tail (pm1_plan.h), built at upload
     bool pm1_plan_ok = false;
+    // single-leaf TLAS, no instanced mesh, every mesh box inside the root box (plain_leaf.h): derived by a full upload, cleared by
+    // whatever moves a box or sets a transform without the host seeing the result
+    bool plain_leaf_ok = false;
     int tlas_max_leaf = 0, tlas_depth = 0;
     bool have_geometry = false, have_materials = false;
 
@@ -201,6 +205,8 @@ struct ptrt_ctx {
     int pm1_full_leaf_eff = 0;       // ... the last frame (0 as well when another traversal mode rendered it)
     int pm1_lane_groups = -1;        // option "pm1_lane_groups": -1 (default) and 1: on where pm1_full_leaf is in effect, 0 the 2^sh rule (make_params)
     int pm1_lane_groups_eff = 0;     // ... the last frame or ray query (0 as well when another traversal mode ran it)
+    int plain_leaf = -1;             // option "plain_leaf": -1 (default) and 1: on where the upload derived it (plain_leaf_ok), 0 never (make_params)
+    int plain_leaf_eff = 0;          // ... the last frame or query (0 as well when a traversal mode without the pair builder ran it)
     int tile_run = 8;                // option "tile_run": of every 8 * run consecutive tiles XCD x renders a run of neighbours (path_trace_kernel); 0: tile k on workgroup k
     int ticket_tiles = 1;            // option "ticket_tiles": consecutive tiles per ticket of the queue
     int persist = 0, n_cus = 0;      // option "persist": persistent waves per CU (0 = the variant's occupancy): lane refill and the radiance query
@@ -440,6 +446,7 @@ pt::KParams make_params(ptrt_ctx *c) {
     K.pm1_groups = (c->pm1_lane_groups != 0 && K.pm1_full_leaf && c->pm1_plan_ok) ? 1 : 0;
     if (K.pm1_groups)
         K.pm1_plan = c->pm1_plan;
+    K.plain_leaf = (c->plain_leaf != 0 && c->plain_leaf_ok && c->tlas_single_leaf && !c->any_transform) ? 1 : 0;
     K.fetch_min = c->fetch_min > 0 ? c->fetch_min : 64; // 0 = refill only when the whole wave is idle: batches of 64
     K.pair_cap = merged_pair_cap(c);
     K.n_nodes = c->n_nodes;

@@ -7,6 +7,7 @@
 #include "../host/ptrt/farm.hpp"
 #include "../host/ptrt/view.hpp"
 #include "pm1_plan.h"
+#include "plain_leaf.h"
 
 #include <chrono>
 #include <cstring>
@@ -91,6 +92,14 @@ int ptrt_pm1_plan(int leaf_triangles, int32_t *out_g63, int32_t *out_take63, int
     return ok ? 1 : 0;
 }
 int ptrt_pm1_div_mul(int g) { return (g >= 1 && g <= 64 && pt::pm1_div_exact(g)) ? (int)pt::pm1_div_mul(g) : 0; }
+
+// include/ptrt.h: what ptrt_upload_geometry derives for option "plain_leaf" from the same arrays (plain_leaf.h), without a device
+int ptrt_plain_leaf(const ptrt_mesh_desc *meshes, int mesh_count, const ptrt_bvh_node *tlas_nodes, int tlas_node_count,
+                    const int32_t *tlas_mesh_indices, int tlas_index_count) {
+    if (!meshes || mesh_count <= 0 || !tlas_nodes || tlas_node_count <= 0 || !tlas_mesh_indices || tlas_index_count <= 0)
+        return -1;
+    return pt::plain_leaf_scene(meshes, mesh_count, tlas_nodes, tlas_node_count, tlas_mesh_indices, tlas_index_count) ? 1 : 0;
+}
 
 void hs_material_default(float *out27) { to_floats(Material(), out27); }
 // Material(albedo, roughness, metallic) constructor (material_lib.cuh:91-104)

@@ -65,6 +65,7 @@ const Option OPTIONS[] = {
     {"pm1_dense_roots", &ptrt_ctx::pm1_dense_roots, OPT_TRISTATE}, // PMODE 1: root-box tests of a half-empty wave dealt over all lanes
     {"pm1_full_leaf", &ptrt_ctx::pm1_full_leaf, OPT_TRISTATE}, // PMODE 1: triangle loops without partial-leaf handling when every leaf is full (0: never)
     {"pm1_lane_groups", &ptrt_ctx::pm1_lane_groups, OPT_TRISTATE}, // PMODE 1: a pair-list tail's lanes per pair from the leaf's divisors, by the upload's plan (0: the 2^sh rule)
+    {"plain_leaf", &ptrt_ctx::plain_leaf, OPT_TRISTATE}, // PMODE 1, 2: no TLAS root test, no instance arithmetic per pair batch, where the upload found the leaf plain (0: never; 1 does not force it)
     {"tile_run", &ptrt_ctx::tile_run, OPT_REJECT, 0, 64}, // 0 (tile k on workgroup k) or the tiles per XCD and run, 1..64
     {"ticket_tiles", &ptrt_ctx::ticket_tiles, OPT_CLAMP, 1, 16},
     {"refill", &ptrt_ctx::refill, OPT_CLAMP, 0, 2},
@@ -88,6 +89,7 @@ const Option OPTIONS[] = {
     {"pm1_dense_roots_eff", &ptrt_ctx::pm1_dense_roots_eff, OPT_READ_ONLY},
     {"pm1_full_leaf_eff", &ptrt_ctx::pm1_full_leaf_eff, OPT_READ_ONLY},
     {"pm1_lane_groups_eff", &ptrt_ctx::pm1_lane_groups_eff, OPT_READ_ONLY}, // ... of the last frame or ray query, whichever came last
+    {"plain_leaf_eff", &ptrt_ctx::plain_leaf_eff, OPT_READ_ONLY}, // ... of the last frame or query, whichever came last
     {"refilled", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->refill_eff ? 1 : 0; }},
     {"split_eff", &ptrt_ctx::split_eff, OPT_READ_ONLY},
     {"pipelined", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->pipelined_last ? 1 : 0; }},

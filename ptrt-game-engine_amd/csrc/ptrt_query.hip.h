@@ -40,6 +40,7 @@ int plan_query(ptrt_ctx *c, bool shading, int samples, int max_depth, QueryPlan 
     c->touched = true;
     c->query_pmode = P.pmode;
     c->pm1_lane_groups_eff = P.pmode == 1 ? P.K.pm1_groups : 0;
+    c->plain_leaf_eff = (P.pmode == 1 || P.pmode == 2) ? P.K.plain_leaf : 0;
     return P.pmode == 3 ? refresh_tlas_heads(c, false) : PTRT_OK;
 }
 

@@ -540,6 +540,8 @@ int plan_frame(ptrt_ctx *c, pt::KParams &K, int spp, int max_depth, FramePlan &P
     c->pm1_dense_roots_eff = K.pm1_dense;
     c->pm1_full_leaf_eff = pmode == 1 ? K.pm1_full_leaf : 0;
     c->pm1_lane_groups_eff = pmode == 1 ? K.pm1_groups : 0;
+    // (PMODE 4's trace_merged runs its own root tests ahead of build_pairs_merged and does not read the flag)
+    c->plain_leaf_eff = (pmode == 1 || pmode == 2) ? K.plain_leaf : 0;
     // (round 2: the merged loop was at its best WITHOUT shadow-ray subtree stealing, 3.98 vs 4.17 ms on the showcase frame -- its
     // yields served ten shadow pairs at the price of sixty closest-hit walks; with the closest-hit walks stolen from as well the
     // yields pay for both kinds: 3.19 ms with, 3.49 without)
