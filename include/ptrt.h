@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms, + ptrt_query_radiance / ptrt_camera_rays / ptrt_init_rng_states, + ptrt_query_probes (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
+#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms, + ptrt_query_radiance / ptrt_camera_rays / ptrt_init_rng_states, + ptrt_query_probes, + ptrt_lds_layout (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
 
 enum {
     PTRT_OK = 0,
@@ -830,6 +830,51 @@ int ptrt_pm1_div_mul(int g);
  * box (fp32 compares, a NaN fails); 0: not so; -1: a missing array.  ABI 6, additions only. */
 int ptrt_plain_leaf(const ptrt_mesh_desc *meshes, int mesh_count, const ptrt_bvh_node *tlas_nodes, int tlas_node_count,
                     const int32_t *tlas_mesh_indices, int tlas_index_count);
+
+/* The dynamic LDS of a launch shape as the device carves it and the host counts it (csrc/lds_layout.h; DESIGN.md 2, "LDS
+ * layouts"); needs no device and no context.  `shape`: a one-wave pair workgroup in PMODE 1 (as the device queries use it), 2,
+ * 3 or 4; the PMODE 1 megakernel's workgroup of one or two waves, with what it stages from the budget of the occupancy its
+ * kernel is built for; PMODE 2 in four-wave workgroups (option lds_nodes); the lock-step stacks of PMODE 0 (`stack_entries`
+ * as launched: 0 where every BLAS is one leaf); the asynchronous-lane kernel; the wavefront trace stage.  A shape reads the
+ * parameters it depends on and ignores the others.  Writes the regions in use -- at most max_regions of them -- one record per
+ * region and wave (wave -1: one copy per workgroup): byte offset from the workgroup's base, size, the alignment of what is
+ * stored there, and for a region that BY DESIGN lies inside others the first and last region id of the span that holds it
+ * (-1: none; all other regions are pairwise disjoint).  info: the launch's byte count (0: PMODE 1 over every budget), the
+ * waves, the PMODE 1 decisions (KParams lds_flags / lds_extra / lds_wave / lds_wave_bytes, tiles per workgroup), PMODE 4's pair
+ * capacity between its clamps, and the largest leaf whose (lane, triangle) tests the leaf-pair list holds.  Returns the number
+ * of regions in use, -1 for a bad argument.  ptrt_lds_region_name: a region id's name (NULL outside).  ABI 6, additions only. */
+enum {
+    PTRT_LDS_LOCKSTEP = 0,
+    PTRT_LDS_PAIR1 = 1,
+    PTRT_LDS_PAIR2 = 2,
+    PTRT_LDS_PAIR3 = 3,
+    PTRT_LDS_PAIR4 = 4,
+    PTRT_LDS_PM1_WG = 5,
+    PTRT_LDS_NODES = 6,
+    PTRT_LDS_ASYNC = 7,
+    PTRT_LDS_WAVEFRONT = 8
+};
+typedef struct ptrt_lds_params {
+    int32_t meshes, tri_slots;     /* meshes of the single TLAS leaf; triangle slots staged (PMODE 1) */
+    int32_t stack_entries;         /* BLAS stack entries per lane */
+    int32_t tlas_leaf, tlas_depth; /* PMODE 3: largest TLAS leaf, TLAS stack entries per lane */
+    int32_t lights;
+    int32_t full, stage, lds_pad, pm1_wg, sample_sync; /* PMODE 1 megakernel: full materials, options stage / lds_pad / pm1_wg, samples in step */
+} ptrt_lds_params;
+typedef struct ptrt_lds_region {
+    int32_t id, wave;
+    int64_t offset, bytes;
+    int32_t align, in_first, in_last;
+} ptrt_lds_region;
+typedef struct ptrt_lds_info {
+    int64_t total;
+    int32_t waves;
+    int32_t lds_flags, lds_extra, lds_wave, lds_wave_bytes, wg;
+    int32_t pair_cap, pair_cap_lo, pair_cap_hi;
+    int32_t max_leaf;
+} ptrt_lds_info;
+int ptrt_lds_layout(int shape, const ptrt_lds_params *params, ptrt_lds_region *regions, int max_regions, ptrt_lds_info *info);
+const char *ptrt_lds_region_name(int id);
 
 /* Render on a caller-owned HIP stream (a `hipStream_t` passed as void*; NULL returns to the
  * context's own stream).  Lets a host that already orders work on a stream (a GL-interop map,

@@ -36,7 +36,6 @@ struct AsyncParams {
     int shade_min; // lanes that must wait for the shading block before it runs while others still trace
     int leaf_min;  // the node loop stops once this many lanes wait at a leaf (64 = classic while-while: all of them)
 };
-constexpr int AS_RING = 128;
 
 template <bool FULL>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER_EU, 8))) void path_trace_async_kernel(
@@ -44,9 +43,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
     LdsStack stk{lds_raw + lane};
-    uint32_t *ring = (uint32_t *)(lds_raw + K.stack_entries * 64);
-    unsigned long long *lkey = (unsigned long long *)(ring + AS_RING); // 64 merge keys of the leaf phase
-    unsigned char *owner = (unsigned char *)(lkey + 64);               // 64 * 17 rounded up: lane of each test
+    const lds::Layout Y = lds::async_layout(K.stack_entries);
+    uint32_t *ring = lds_at<uint32_t>(lds_raw, Y, lds::RING);
+    unsigned long long *lkey = lds_at<unsigned long long>(lds_raw, Y, lds::LKEY); // 64 merge keys of the leaf phase
+    unsigned char *owner = lds_at<unsigned char>(lds_raw, Y, lds::OWNER);         // lane of each test
     int ring_head = 0, ring_n = 0; // wave-uniform
     bool pool_empty = false;
     const int2 tl = K.tlas_leaves[~K.tlas_root_ref];

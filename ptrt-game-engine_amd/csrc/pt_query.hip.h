@@ -9,8 +9,8 @@
 // Two ways to walk, both the path kernel's own and both exact (the equivalences in pt_kernels.hip.h / pt_render.hip.h):
 //   PMODE 0          one ray per lane, closest_hit<GEOM> / any_hit<GEOM> with the LDS stack of the lane;
 //   PMODE 1, 2, 3    the wave-level (ray, mesh) pair traversal of phases [B] / [D] of path_trace_kernel, over the same LDS
-//                    carve (carve_pair_lds): PMODE 1 stages the triangle packets of a single-leaf scene, 2 the mesh heads of a
-//                    single-leaf TLAS, 3 walks a real TLAS in rounds.
+//                    carve and staging (stage_pair_lds): PMODE 1 stages the triangle packets of a single-leaf scene, 2 the mesh
+//                    heads of a single-leaf TLAS, 3 walks a real TLAS in rounds.
 // The host picks the mode with pair_mode(c, geom, false) -- the path kernel's choice for the same scene and options.
 //
 // The grid is persistent: about one 64-thread workgroup per wave slot of the chip, each taking chunks of 64 rays with a
@@ -73,7 +73,6 @@ PT_DEV void winner_uv(const KParams &K, Hit &h, f3 o, f3 d) {
     tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), r, T_FAR, t, h.u, h.v);
 }
 
-// LDS bytes: PMODE 0 the lanes' stacks (GEOM > 0), else pair_lds_bytes of the host (ptrt_render.hip.h), which this carve fits.
 template <int GEOM, int PMODE, int KIND>
 __global__ __launch_bounds__(64) void ray_query_kernel(const KParams K, const float *__restrict__ origins,
                                                        const float *__restrict__ dirs, const float *__restrict__ tmax,
@@ -82,41 +81,7 @@ __global__ __launch_bounds__(64) void ray_query_kernel(const KParams K, const fl
     const int lane = threadIdx.x;
     LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL{};
-    if (PMODE == 1) {
-        // the staging of stage_pair_lds (pt_render.hip.h), which this block has to agree with: the leaf's triangle packets
-        // (PAIR_PAD float4 apart per mesh), mesh table, heads
-        PL = carve_pair_lds((void *)lds_raw, K.pair_tri_slots, K.pair_meshes);
-        const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = 0; i < K.pair_meshes; ++i) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const int2 leaf = K.leaves[~__float_as_int(K.mesh_recs[m * MESH_REC_F4].w)];
-            for (int k = lane; k < leaf.y * 3; k += 64)
-                PL.tris[leaf.x * 3 + i * PAIR_PAD + k] = K.tris[leaf.x * 3 + k];
-        }
-        for (int i = lane; i < K.pair_meshes; i += 64) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
-            PL.meshbox[2 * i + 1] = hb;
-            const int2 leaf = K.leaves[~mh.root_ref];
-            PL.meshtab[i] = make_int4(leaf.x, leaf.y, mh.flags, m);
-        }
-    } else if (PMODE) {
-        PL = carve_pair_lds((void *)lds_raw, 0, PMODE == 3 ? 0 : K.pair_meshes, K.stack_entries, PMODE == 3 ? K.tlas_max_leaf : 0,
-                            PMODE == 3 ? K.tlas_depth : 0);
-        const int2 lf = PMODE == 3 ? make_int2(0, 0) : K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = lane; PMODE != 3 && i < K.pair_meshes; i += 64) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8));
-            PL.meshbox[2 * i + 1] = hb;
-        }
-    }
+    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
     PL.cyc = &cyc;
     PL.stat_bounce = 0;
     __syncthreads();

@@ -35,191 +35,176 @@
 //  * PMODE 0: lock-step fall-backs (and the A/B baseline of the tests).
 #pragma once
 #include "pt_kernels.hip.h"
+#include "lds_layout.h"
 
 namespace pt {
 
 struct CycleAcc;
+// A wave's pointers into its workgroup's LDS; which regions a launch shape has, where and how large: lds_layout.h.
 struct PairLds {
     CycleAcc *cyc;            // (stats build: the kernel's cycle accumulator)
     int stat_bounce;          // (stats build: bounce of the rays of this traversal -- wave-uniform with the samples in step)
-    float4 *tris;             // pair_tri_slots * 3
+    float4 *tris;             // PMODE 1: the leaf's triangle packets
     int4 *meshtab;            // per mesh order: {first slot, count, flags, mesh id}
     float4 *meshbox;          // per mesh order: {bmin, root ref}, {bmax, flags}: the mesh record's head, staged once
     const float4 *topnodes;   // WG = 4 variant: the first TOP_NODES nodes of every mesh of the leaf, [order][node][4], or NULL
-    uint32_t *pairs;          // 64 * pair_meshes
-    unsigned long long *best; // 64
-    uint32_t *occ;            // 64
+    uint32_t *pairs;          // the (ray, mesh) pair list: 16-bit entries {lane, mesh order << 6}
+    unsigned long long *best; // the rays' minima {t bits, mesh order, leaf index}; the any-hit traversals keep a plane of ray limits in its first half
+    uint32_t *occ;            // the any-hit flags
     uint2 *stack;             // PMODE 2: [entry][lane] BLAS traversal stack
     // PMODE 2, (lane, triangle) pair compaction of the leaf phase (leaf_pairs)
-    int *leafx;               // PMODE 3: 64: first TLAS index of the leaf each ray is at
+    int *leafx;               // PMODE 3: first TLAS index of the leaf each ray is at
     uint2 *tstack;            // PMODE 3: [entry][lane] TLAS traversal stack
-    unsigned long long *lkey; // 64: {t bits, index in leaf} min per lane
-    unsigned char *owner;     // 64 * 17 rounded up: lane of each test
+    unsigned long long *lkey; // {t bits, index in leaf} min per lane
+    unsigned char *owner;     // lane of each test
     // shading inputs staged behind the lists (KParams::lds_extra; one-wave workgroups of PMODE >= 1), else NULL
-    const float2 *jit;        // 16: TAA jitter table
-    const float2 *bn;         // 64: the lanes' blue-noise values
+    const float2 *jit;        // TAA jitter table
+    const float2 *bn;         // the lanes' blue-noise values
     const float4 *lights;     // the scene's light records (4 float4 each) when at most LDS_LIGHTS of them
     const float4 *mats;       // PMODE 1: material records (6 float4) of the leaf's meshes by mesh order
     unsigned long long *dirty; // PMODE 2, closest-hit stealing: bit r = ray r has to be traced again without it (run_closest_queue); or NULL
     unsigned long long *count; // one-wave workgroups: [0] {extension rays, shadow rays << 32} of the wave so far, [1] light
                                // samples whose value was exactly zero (counted in [0], not walked)
 };
-constexpr int LDS_LIGHTS = 8;
-constexpr int LDS_EXTRA_FIXED = 16 * 8 + 64 * 8; // jitter table + blue-noise values
-constexpr int LEAF_PAIR_BYTES = 512 + 1088; // lkey + owner (64 lanes x 17 tests)
-// PMODE 3: TLAS leaves a ray may have in one fill of the pair list (a power of two <= 4) and the pairs that end a fill
-#ifndef PT_TLAS_SLOTS
-#define PT_TLAS_SLOTS 1
-#endif
-constexpr int TLAS_SLOTS = PT_TLAS_SLOTS;
-constexpr int TLAS_FILL_TARGET = 64;
-constexpr int PAIR_PAD = 2; // float4 of padding in front of each mesh's packets in LDS (bank spreading)
-PT_DEV PairLds carve_pair_lds(void *base, int tri_slots, int meshes, int stack_entries = 0, int tlas_leaf = 0,
-                              int tlas_depth = 0, int pair_cap = 0) {
+template <class T> PT_DEV T *lds_at(void *base, const lds::Layout &Y, int id, int wave = 0) { return (T *)((char *)base + Y.at(id, wave)); }
+// The carves below form their pointers one from the last, in layout order, each `off(this) - off(last)` further: the distance of
+// two regions then reaches the compiler as the size between them -- a constant for the minima, the flags and the pair list, which
+// it folds into the LDS instructions' offset fields.  Measured: with every pointer formed from the base instead,
+// path_trace_kernel<0,false,1,1,true> holds one more address live across its loop and spills a VGPR (16 B of scratch).
+struct LdsCursor {
+    char *p;       // the workgroup's base, or a wave's part (Layout::part)
+    size_t at = 0;
+    template <class T> PT_DEV T *to(const lds::Region &r) {
+        p += r.off - at;
+        at = r.off;
+        return (T *)p;
+    }
+};
+
+// A one-wave pair workgroup (lds::pair_layout; host: pair_lds_bytes): a device query in PMODE 1, 2, 3 or the megakernel in
+// PMODE 2, 3, 4.  Behind PMODE 1 the layout tells the shape by K.pair_cap and K.tlas_max_leaf, run-time values, and this carve
+// walks it region by region in layout order, each pointer the last one's region further (the regions the layout puts one behind
+// the other have no gaps): that is the statement path_trace_kernel<1,true,4,1,false> compiles from to the instructions it had
+// before the layouts had a header -- the showcase frame's kernel answers to any other with 0.4 - 0.9 % (lds_layout.h).
+template <int PMODE> PT_DEV PairLds carve_pair_lds(void *base, const KParams &K) {
+    const lds::Layout Y = lds::pair_layout(PMODE, K.pair_meshes, K.pair_tri_slots, K.stack_entries, K.tlas_max_leaf, K.tlas_depth,
+                                           K.pair_cap);
     PairLds l{};
     char *p = (char *)base;
-    l.tris = (float4 *)p;
-    p += tri_slots ? ((size_t)tri_slots * 48 + (size_t)meshes * PAIR_PAD * 16) : 0;
-    l.meshtab = (int4 *)p; // (PMODE 1 only: {first slot, count, flags, mesh id}; the other modes read the staged heads)
-    p += tri_slots ? (size_t)meshes * 16 : 0;
-    l.meshbox = (float4 *)p;
-    p += (size_t)meshes * 32;
-    l.best = (unsigned long long *)p;
-    // the any-hit traversals use the first half of `best` as a plane of ray limits; their blocked flags take the second
-    // (PMODE 4 walks both kinds of ray at once and keeps its flags apart)
-    l.occ = (uint32_t *)(p + 256);
-    p += tlas_leaf ? 512 * TLAS_SLOTS : 512; // (PMODE 3: one minimum per ray and leaf slot)
-    l.pairs = (uint32_t *)p;
-    // 16-bit entries {lane, mesh order << 6}; PMODE 3 holds one TLAS leaf per ray at a time
-    // (PMODE 4 keeps the pairs of both ray kinds in one list of pair_cap 16-bit entries)
-    p += pair_cap ? (size_t)pair_cap * 2 : tlas_leaf ? ((size_t)tlas_leaf * 64 + TLAS_FILL_TARGET) * 2 : (size_t)meshes * 128;
-    if (pair_cap) {
-        l.occ = (uint32_t *)p;
-        p += 256;
+    auto take = [&p](const lds::Region &r) {
+        char *at = p;
+        p += r.bytes;
+        return at;
+    };
+    l.tris = (float4 *)take(Y.r[lds::TRIS]);
+    l.meshtab = (int4 *)take(Y.r[lds::MESHTAB]);
+    l.meshbox = (float4 *)take(Y.r[lds::MESHBOX]);
+    l.best = (unsigned long long *)take(Y.r[lds::BEST]);
+    l.occ = (uint32_t *)((char *)l.best + Y.r[lds::LIMITS].bytes); // (in the minima, behind the limits ...
+    l.pairs = (uint32_t *)take(Y.r[lds::PAIRS]);
+    if (Y.r[lds::OCC].in_first < 0) // ... unless the shape has flags of their own)
+        l.occ = (uint32_t *)take(Y.r[lds::OCC]);
+    if (PMODE == 1) {
+        l.count = lds_at<unsigned long long>(base, Y, lds::COUNT);
+        return l;
     }
-    l.stack = (uint2 *)p;
-    p += (size_t)stack_entries * 512;
-    l.tstack = (uint2 *)p;
-    p += (size_t)tlas_depth * 512;
-    l.leafx = (int *)p;
-    p += tlas_leaf ? 256 * TLAS_SLOTS : 0;
-    l.lkey = (unsigned long long *)p;
-    p += 512;
-    l.owner = (unsigned char *)p;
-    p += LEAF_PAIR_BYTES - 512;
-    // the wave's ray totals (path_trace_kernel): PMODE 1 keeps them in the spare bytes behind its last mesh's packets
-    l.count = tri_slots ? (unsigned long long *)(l.tris + tri_slots * 3 + (meshes - 1) * PAIR_PAD) : (unsigned long long *)p;
-    l.dirty = tri_slots ? nullptr : (unsigned long long *)p + 2;
+    l.stack = (uint2 *)take(Y.r[lds::STACK]);
+    l.tstack = (uint2 *)take(Y.r[lds::TSTACK]);
+    l.leafx = (int *)take(Y.r[lds::LEAFX]);
+    l.lkey = (unsigned long long *)take(Y.r[lds::LKEY]);
+    l.owner = (unsigned char *)take(Y.r[lds::OWNER]);
+    l.count = (unsigned long long *)take(Y.r[lds::COUNT]);
+    l.dirty = (unsigned long long *)take(Y.r[lds::DIRTY]);
     return l;
 }
 
-// What a one-wave workgroup of a device query stages into LDS once, before its grid-stride loop, over the carve above (host:
-// pair_lds_bytes), for radiance_query_kernel and probe_query_kernel:
-//   PMODE 1   the single leaf's triangle packets (PAIR_PAD float4 apart per mesh), the mesh table and the mesh heads;
-//   PMODE 2   the mesh heads of the single-leaf TLAS (the BLAS stacks are carved, nothing of them is staged);
-//   PMODE 3   nothing: the carve only (TLAS stacks, one leaf per ray), the heads are read from memory;
-//   PMODE 0   nothing at all (an empty PairLds: the lanes' stacks start at the base of the LDS).
-// The caller sets `cyc` / `stat_bounce` and synchronises.  ray_query_kernel (pt_query.hip.h) states the same staging in its own
-// body and has to agree with this; path_trace_kernel stages for itself (carve_pm1, workgroup-wide).
+// The heads of the single TLAS leaf's meshes, by mesh order, into L.meshbox -- and with TABLE (PMODE 1) their table entries
+// into L.meshtab.  `tid` / `threads`: the thread in its workgroup and the workgroup's size.
+template <bool TABLE> PT_DEV void stage_mesh_heads(const KParams &K, const PairLds &L, int tid, int threads) {
+    const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
+    for (int i = tid; i < K.pair_meshes; i += threads) {
+        const int m = K.tlas_mesh_ids[lf.x + i];
+        const MeshHead mh = load_mesh_head(K, m);
+        L.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
+        float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
+        hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
+        L.meshbox[2 * i + 1] = hb;
+        if (TABLE) {
+            const int2 leaf = K.leaves[~mh.root_ref];
+            L.meshtab[i] = make_int4(leaf.x, leaf.y, mh.flags, m);
+        }
+    }
+}
+// PMODE 1: the triangle packets of every mesh of the leaf into L.tris.  Mesh i's packets start PAIR_PAD * i float4 later than
+// in the arena: with 48-B packets the per-mesh blocks would otherwise sit a multiple of 16 banks apart and lanes working on
+// different meshes would collide on ds_read_b128.
+PT_DEV void stage_leaf_tris(const KParams &K, const PairLds &L, int tid, int threads) {
+    const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
+    for (int i = 0; i < K.pair_meshes; ++i) {
+        const int m = K.tlas_mesh_ids[lf.x + i];
+        const int2 leaf = K.leaves[~__float_as_int(K.mesh_recs[m * MESH_REC_F4].w)];
+        for (int k = tid; k < leaf.y * 3; k += threads)
+            L.tris[leaf.x * 3 + i * PAIR_PAD + k] = K.tris[leaf.x * 3 + k];
+    }
+}
+
+// What a one-wave workgroup stages into LDS once, before its loop, over the carve above -- ray_query_kernel,
+// radiance_query_kernel, probe_query_kernel, and path_trace_kernel in PMODE 2, 3, 4:
+//   PMODE 1      the single leaf's triangle packets, the mesh table and the mesh heads;
+//   PMODE 2, 4   the mesh heads of the single-leaf TLAS (the BLAS stacks are carved, nothing of them is staged);
+//   PMODE 3      nothing: the carve only (TLAS stacks, one leaf per ray), the heads are read from memory;
+//   PMODE 0      nothing at all (an empty PairLds: the lanes' stacks start at the base of the LDS).
+// The caller sets `cyc` / `stat_bounce` and synchronises.  path_trace_kernel in PMODE 1 and with WG = 4 carves for its
+// workgroup (carve_pm1, carve_pair_lds_wg) and calls the two staging functions itself.
 template <int PMODE> PT_DEV PairLds stage_pair_lds(const KParams &K, uint2 *lds_raw, const int lane) {
     PairLds PL{};
-    if (PMODE == 1) {
-        PL = carve_pair_lds((void *)lds_raw, K.pair_tri_slots, K.pair_meshes);
-        const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = 0; i < K.pair_meshes; ++i) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const int2 leaf = K.leaves[~__float_as_int(K.mesh_recs[m * MESH_REC_F4].w)];
-            for (int k = lane; k < leaf.y * 3; k += 64)
-                PL.tris[leaf.x * 3 + i * PAIR_PAD + k] = K.tris[leaf.x * 3 + k];
-        }
-        for (int i = lane; i < K.pair_meshes; i += 64) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
-            PL.meshbox[2 * i + 1] = hb;
-            const int2 leaf = K.leaves[~mh.root_ref];
-            PL.meshtab[i] = make_int4(leaf.x, leaf.y, mh.flags, m);
-        }
-    } else if (PMODE) {
-        PL = carve_pair_lds((void *)lds_raw, 0, PMODE == 3 ? 0 : K.pair_meshes, K.stack_entries, PMODE == 3 ? K.tlas_max_leaf : 0,
-                            PMODE == 3 ? K.tlas_depth : 0);
-        const int2 lf = PMODE == 3 ? make_int2(0, 0) : K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = lane; PMODE != 3 && i < K.pair_meshes; i += 64) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8));
-            PL.meshbox[2 * i + 1] = hb;
-        }
+    if (PMODE) {
+        PL = carve_pair_lds<PMODE>((void *)lds_raw, K);
+        if (PMODE == 1)
+            stage_leaf_tris(K, PL, lane, 64);
+        if (PMODE != 3)
+            stage_mesh_heads<PMODE == 1>(K, PL, lane, 64);
     }
     return PL;
 }
 
-// PMODE 1 (every BLAS one leaf, the scene's triangles in LDS).  A workgroup of WG waves = WG neighbouring tiles shares ONE copy
-// of what is read-only -- triangle packets, mesh table, mesh heads, jitter table, light and material records -- and each
-// wave has its own lists behind it: the rays' minima / flags, the pair list, the lanes' blue-noise values, the ray totals.
-// Layout (host: pm1_layout in ptrt_render.hip.h): [tris + pads | meshtab | meshbox] [lds_extra: jit | lights | mats]
-// [lds_wave + wave * lds_wave_bytes: best 512 | pairs 128 * meshes | bn 512 (if staged) | count 16].
-// PMODE 1, per wave: the minima (512 B) and the pair list behind them are scratch of the traversal phases [B] / [D]; the
-// lane-refill kernel parks a finished pixel's six generator words there across [R] (6 x 256 B), so the list is never
-// smaller than what is left of that after the minima
-__host__ __device__ constexpr size_t pm1_pair_bytes(int meshes) { return (size_t)meshes * 128 > 1024 ? (size_t)meshes * 128 : 1024; }
-PT_DEV PairLds carve_pm1(void *base, const KParams &K, int wave) {
+// PMODE 1 megakernel, a workgroup of WG waves (lds::pm1_layout; what is staged where is the host's decision, pm1_layout in
+// ptrt_render.hip.h, read here out of KParams).  The minima and the pair list are scratch of the traversal phases [B] / [D].
+template <bool FULL, int WG> PT_DEV PairLds carve_pm1(void *base, const KParams &K, int wave) {
+    const lds::Layout Y = lds::pm1_layout(K.pair_meshes, K.pair_tri_slots, K.n_lights, FULL, WG,
+                                          lds::Pm1Staging{K.lds_extra, K.lds_flags, K.lds_wave, K.lds_wave_bytes}, 0);
     PairLds l{};
-    char *p = (char *)base;
-    const int meshes = K.pair_meshes;
-    l.tris = (float4 *)p;
-    p += (size_t)K.pair_tri_slots * 48 + (size_t)meshes * PAIR_PAD * 16;
-    l.meshtab = (int4 *)p;
-    p += (size_t)meshes * 16;
-    l.meshbox = (float4 *)p;
-    char *x = (char *)base + K.lds_extra;
-    l.jit = (const float2 *)x;
-    l.lights = (const float4 *)(x + 16 * 8);
-    l.mats = l.lights + ((K.lds_flags & 1) ? K.n_lights * 4 : 0);
-    char *w = (char *)base + K.lds_wave + wave * K.lds_wave_bytes;
-    l.best = (unsigned long long *)w;
-    l.occ = (uint32_t *)(w + 256); // (the any-hit flags take the second half of the minima's words)
-    l.pairs = (uint32_t *)(w + 512);
-    w += 512 + pm1_pair_bytes(meshes);
-    l.bn = (const float2 *)w;
-    w += (K.lds_flags & 8) ? 64 * 8 : 0;
-    l.count = (unsigned long long *)w;
+    LdsCursor c{(char *)base};
+    l.tris = c.to<float4>(Y.r[lds::TRIS]);
+    l.meshtab = c.to<int4>(Y.r[lds::MESHTAB]);
+    l.meshbox = c.to<float4>(Y.r[lds::MESHBOX]);
+    LdsCursor x{(char *)base};
+    l.jit = x.to<const float2>(Y.r[lds::JIT]);
+    l.lights = x.to<const float4>(Y.r[lds::LIGHTS]);
+    l.mats = x.to<const float4>(Y.r[lds::MATS]);
+    LdsCursor w{(char *)base + Y.part(lds::BEST, wave)};
+    l.best = w.to<unsigned long long>(Y.r[lds::BEST]);
+    l.occ = w.to<uint32_t>(Y.r[lds::OCC]);
+    l.pairs = w.to<uint32_t>(Y.r[lds::PAIRS]);
+    l.bn = w.to<const float2>(Y.r[lds::BN]);
+    l.count = w.to<unsigned long long>(Y.r[lds::COUNT]);
     return l;
 }
 
-// PMODE 2 in 256-thread workgroups (path_trace_kernel<.., WG = 4>): mesh table, mesh heads and the top levels of every
-// BLAS are ONE copy per workgroup at the base of its LDS; behind them each wave has its own lists and stacks.
-PT_DEV size_t shared_lds_bytes(int meshes) { return (size_t)meshes * (32 + TOP_NODES * 64); }
-PT_DEV size_t wave_lds_bytes(int meshes, int stack_entries) {
-    return 512 + (size_t)meshes * 128 + 256 + (size_t)stack_entries * 512 + LEAF_PAIR_BYTES;
-}
+// PMODE 2 in 256-thread workgroups (path_trace_kernel<.., WG = 4>; lds::nodes_layout).
 PT_DEV PairLds carve_pair_lds_wg(void *base, int wave, int meshes, int stack_entries) {
+    const lds::Layout Y = lds::nodes_layout(meshes, stack_entries, TOP_NODES);
     PairLds l{};
-    char *p = (char *)base;
-    l.meshtab = nullptr;
-    l.meshbox = (float4 *)p;
-    p += (size_t)meshes * 32;
-    l.topnodes = (const float4 *)p;
-    p += (size_t)meshes * TOP_NODES * 64;
-    p += (size_t)wave * wave_lds_bytes(meshes, stack_entries);
-    l.best = (unsigned long long *)p;
-    p += 512;
-    l.pairs = (uint32_t *)p;
-    p += (size_t)meshes * 128;
-    l.occ = (uint32_t *)p;
-    p += 256;
-    l.stack = (uint2 *)p;
-    p += (size_t)stack_entries * 512;
-    l.lkey = (unsigned long long *)p;
-    p += 512;
-    l.owner = (unsigned char *)p;
-    l.tris = nullptr;
-    l.tstack = nullptr;
-    l.leafx = nullptr;
+    LdsCursor c{(char *)base};
+    l.meshbox = c.to<float4>(Y.r[lds::MESHBOX]);
+    l.topnodes = c.to<const float4>(Y.r[lds::TOPNODES]);
+    LdsCursor w{(char *)base + Y.part(lds::BEST, wave)};
+    l.best = w.to<unsigned long long>(Y.r[lds::BEST]);
+    l.pairs = w.to<uint32_t>(Y.r[lds::PAIRS]);
+    l.occ = w.to<uint32_t>(Y.r[lds::OCC]);
+    l.stack = w.to<uint2>(Y.r[lds::STACK]);
+    l.lkey = w.to<unsigned long long>(Y.r[lds::LKEY]);
+    l.owner = w.to<unsigned char>(Y.r[lds::OWNER]);
     return l;
 }
 
@@ -1937,38 +1922,14 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
     PairLds PL{};
     constexpr bool MERGED = (PMODE == 4);
     if (PMODE == 1) {
-        PL = carve_pm1((void *)lds_raw, K, wave);
-        const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
-        // mesh i's packets start PAIR_PAD * i float4 later than in the arena: with 48-B packets the per-mesh blocks would
-        // otherwise sit a multiple of 16 banks apart and lanes working on different meshes would collide on ds_read_b128
-        for (int i = 0; i < K.pair_meshes; ++i) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const int2 leaf = K.leaves[~__float_as_int(K.mesh_recs[m * MESH_REC_F4].w)];
-            for (int k = threadIdx.x; k < leaf.y * 3; k += 64 * WG)
-                PL.tris[leaf.x * 3 + i * PAIR_PAD + k] = K.tris[leaf.x * 3 + k];
-        }
-        for (int i = threadIdx.x; i < K.pair_meshes; i += 64 * WG) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
-            PL.meshbox[2 * i + 1] = hb;
-            const int2 leaf = K.leaves[~mh.root_ref];
-            PL.meshtab[i] = make_int4(leaf.x, leaf.y, mh.flags, m);
-        }
+        PL = carve_pm1<FULL, WG>((void *)lds_raw, K, wave);
+        stage_leaf_tris(K, PL, threadIdx.x, 64 * WG);
+        stage_mesh_heads<true>(K, PL, threadIdx.x, 64 * WG);
         // (the barrier follows the shading inputs, below)
     } else if (WG > 1) {
         PL = carve_pair_lds_wg((void *)lds_raw, wave, K.pair_meshes, K.stack_entries);
+        stage_mesh_heads<false>(K, PL, threadIdx.x, 64 * WG);
         const int2 lf = K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = threadIdx.x; i < K.pair_meshes; i += 64 * WG) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8));
-            PL.meshbox[2 * i + 1] = hb;
-        }
         // the first TOP_NODES nodes of each tree (its top TOP_LEVELS levels: the host numbers them in level order)
         float4 *top = const_cast<float4 *>(PL.topnodes);
         for (int i = threadIdx.x; i < K.pair_meshes * TOP_NODES * 4; i += 64 * WG) {
@@ -1982,17 +1943,7 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         if (K.top_off)
             PL.topnodes = nullptr;
     } else if (PMODE) {
-        PL = carve_pair_lds((void *)lds_raw, 0, PMODE == 3 ? 0 : K.pair_meshes, K.stack_entries,
-                            PMODE == 3 ? K.tlas_max_leaf : 0, PMODE == 3 ? K.tlas_depth : 0, MERGED ? K.pair_cap : 0);
-        const int2 lf = PMODE == 3 ? make_int2(0, 0) : K.tlas_leaves[~K.tlas_root_ref];
-        for (int i = lane; PMODE != 3 && i < K.pair_meshes; i += 64) {
-            const int m = K.tlas_mesh_ids[lf.x + i];
-            const MeshHead mh = load_mesh_head(K, m);
-            PL.meshbox[2 * i] = K.mesh_recs[m * MESH_REC_F4 + 0];
-            float4 hb = K.mesh_recs[m * MESH_REC_F4 + 1];
-            hb.w = __int_as_float((mh.flags & 0xff) | (m << 8)); // (flags and mesh id in one word: staged_mesh_head)
-            PL.meshbox[2 * i + 1] = hb;
-        }
+        PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
         __syncthreads();
     }
     // STREAM (one-wave workgroups; instantiated for PMODE 1): the launch is a grid of PERSISTENT waves and a lane that has

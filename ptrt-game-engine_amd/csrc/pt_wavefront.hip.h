@@ -54,7 +54,6 @@ struct WfParams {
 };
 constexpr uint32_t WF_SPEC = 1u << 16, WF_PREV_SPEC = 1u << 17, WF_EXT = 1u << 18, WF_SHADOW = 1u << 19,
                    WF_ENDED = 1u << 20, WF_DONE = 1u << 21, WF_PVALID = 1u << 22;
-constexpr int WF_RING = 256; // ring entries per wave (u32): < 64 waiting + at most 128 from one chunk
 
 // ---------------------------------------------------------------------------------------------
 // trace: persistent waves, per-lane refill.  Preconditions (checked by the host): single-leaf TLAS
@@ -65,10 +64,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         return;
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    const int per_wave = K.stack_entries * 64 + WF_RING / 2; // in uint2
-    uint2 *wbase = lds_raw + (size_t)wib * per_wave;
-    LdsStack stk{wbase + lane};
-    uint32_t *ring = (uint32_t *)(wbase + K.stack_entries * 64);
+    const lds::Layout Y = lds::wavefront_layout(K.stack_entries);
+    LdsStack stk{lds_at<uint2>(lds_raw, Y, lds::STACK, wib) + lane};
+    uint32_t *ring = lds_at<uint32_t>(lds_raw, Y, lds::RING, wib);
     const int NW = gridDim.x * 4;
     const int n_chunks = (W.n_items + 63) >> 6;
     int chunk = blockIdx.x * 4 + wib;

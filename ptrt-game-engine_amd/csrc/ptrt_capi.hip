@@ -450,9 +450,9 @@ pt::KParams make_params(ptrt_ctx *c) {
     K.fetch_min = c->fetch_min > 0 ? c->fetch_min : 64; // 0 = refill only when the whole wave is idle: batches of 64
     K.pair_cap = merged_pair_cap(c);
     K.n_nodes = c->n_nodes;
-    // the compacted leaf phase lists up to 64 x (largest leaf) tests in LEAF_PAIR_BYTES - 512 bytes of LDS: the reference
+    // the compacted leaf phase lists up to 64 x (largest leaf) tests in its owner list (lds_layout.h): the reference
     // builder's leaves (<= 17 triangles) fit; a scene built with a larger leaf target walks its leaves lane by lane
-    K.leaf_pairs = (c->leaf_pairs && (size_t)c->pair_max_leaf * 64 <= (size_t)pt::LEAF_PAIR_BYTES - 512) ? 1 : 0;
+    K.leaf_pairs = (c->leaf_pairs && pt::leaf_pairs_fit(c->pair_max_leaf)) ? 1 : 0;
     K.leaf_min = c->leaf_min;
     K.steal = c->steal;
     K.csteal = c->csteal;
@@ -555,6 +555,69 @@ bool device_span(ptrt_ctx *c, const void *p, size_t bytes) {
 extern "C" {
 
 int ptrt_abi_version(void) { return PTRT_ABI_VERSION; }
+
+// include/ptrt.h: the LDS layout of a launch shape (lds_layout.h) with the budgets plan_frame uses, without a device
+int ptrt_lds_layout(int shape, const ptrt_lds_params *p, ptrt_lds_region *regions, int max_regions, ptrt_lds_info *info) {
+    namespace lds = pt::lds;
+    if (!p || !info || max_regions < 0 || (max_regions > 0 && !regions) || p->meshes < 0 || p->tri_slots < 0 || p->stack_entries < 0 ||
+        p->tlas_leaf < 0 || p->tlas_depth < 0 || p->lights < 0 || p->lds_pad < 0)
+        return -1;
+    *info = ptrt_lds_info{};
+    lds::Layout Y;
+    switch (shape) {
+    case PTRT_LDS_LOCKSTEP: Y = lds::lockstep_layout(p->stack_entries); break;
+    case PTRT_LDS_PAIR4:
+        info->pair_cap = lds::merged_pair_cap(p->meshes, p->stack_entries, MERGED_LDS_BUDGET);
+        info->pair_cap_lo = lds::merged_cap_lo(p->meshes);
+        info->pair_cap_hi = lds::merged_cap_hi(p->meshes);
+        [[fallthrough]];
+    case PTRT_LDS_PAIR1:
+    case PTRT_LDS_PAIR2:
+    case PTRT_LDS_PAIR3:
+        if (shape != PTRT_LDS_PAIR3 && p->meshes < 1)
+            return -1;
+        Y = lds::pair_layout(shape, p->meshes, p->tri_slots, p->stack_entries, p->tlas_leaf, p->tlas_depth, info->pair_cap);
+        break;
+    case PTRT_LDS_PM1_WG: {
+        if (p->meshes < 1)
+            return -1;
+        const bool full = p->full != 0;
+        const lds::Pm1Choice P = pm1_choice(p->meshes, p->tri_slots, p->lights, full, p->stage, p->sample_sync, p->lds_pad, p->pm1_wg);
+        info->lds_extra = P.s.lds_extra;
+        info->lds_flags = P.s.lds_flags;
+        info->lds_wave = P.s.lds_wave;
+        info->lds_wave_bytes = P.s.lds_wave_bytes;
+        info->wg = P.wg;
+        if (P.total)
+            Y = lds::pm1_layout(p->meshes, p->tri_slots, p->lights, full, P.wg, P.s, p->lds_pad);
+        break;
+    }
+    case PTRT_LDS_NODES: Y = lds::nodes_layout(p->meshes, p->stack_entries, pt::TOP_NODES); break;
+    case PTRT_LDS_ASYNC: Y = lds::async_layout(p->stack_entries); break;
+    case PTRT_LDS_WAVEFRONT: Y = lds::wavefront_layout(p->stack_entries); break;
+    default: return -1;
+    }
+    info->total = (int64_t)Y.total;
+    info->waves = Y.waves;
+    info->max_leaf = pt::LEAF_PAIR_TESTS;
+    int n = 0;
+    for (int id = 0; id < lds::N_REGIONS; ++id)
+        for (int w = 0; w < (id >= lds::FIRST_WAVE ? Y.waves : 1); ++w) {
+            const lds::Region &r = Y.r[id];
+            if (!r.bytes)
+                continue;
+            if (n < max_regions)
+                regions[n] = ptrt_lds_region{id, id >= lds::FIRST_WAVE ? w : -1, (int64_t)Y.at(id, w), (int64_t)r.bytes, r.align, r.in_first, r.in_last};
+            ++n;
+        }
+    return n;
+}
+const char *ptrt_lds_region_name(int id) {
+    static const char *const names[pt::lds::N_REGIONS] = {"tris", "meshtab", "meshbox", "topnodes", "jit", "lights", "mats", "best",
+                                                           "pairs", "occ", "stack", "tstack", "leafx", "lkey", "owner", "bn",
+                                                           "count", "dirty", "ring", "tail", "limits", "dense_owner", "park"};
+    return id >= 0 && id < pt::lds::N_REGIONS ? names[id] : nullptr;
+}
 
 const char *ptrt_last_error(const ptrt_ctx *ctx) {
     if (ctx && ctx_live(const_cast<ptrt_ctx *>(ctx), false))
@@ -1152,7 +1215,7 @@ int ptrt_render_wireframe(ptrt_ctx *c, float thickness, void *out_rgb8, int out_
     K.rgb8 = out_is_device ? (unsigned char *)out_rgb8 : c->wire_rgb8;
     K.rgb8_frame = out_is_device == PTRT_OUT_DEVICE_FRAME ? 1 : 0;
     const int geom = pick_geom(c);
-    const size_t lds = (geom == 0) ? 0 : (size_t)c->stack_entries * 64 * sizeof(uint2);
+    const size_t lds = trace_lds_bytes(c, geom, 0);
     const dim3 grid(K.tiles_x, (c->rows + 7) / 8);
     if (geom == 0)
         hipLaunchKernelGGL(pt::wireframe_kernel<0>, grid, dim3(64), lds, c->stream, K, thickness);

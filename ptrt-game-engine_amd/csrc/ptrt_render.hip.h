@@ -15,31 +15,16 @@ int pick_geom(ptrt_ctx *c) {
     return g;
 }
 
-// PMODE 4 keeps extension and shadow pairs in one list: 64 * meshes entries always fit the extension pairs; the
-// shadow pairs get what is left of a 10-KB LDS budget (16 waves per CU), at least 64 (one mesh per pass), at most
-// another 64 * meshes (everything in one pass)
-int merged_pair_cap(const ptrt_ctx *c) {
-    const size_t rest = (size_t)c->pair_meshes * 32 + 512 + 256 + (size_t)c->stack_entries * 64 * sizeof(uint2) + pt::LEAF_PAIR_BYTES + 24;
-    const int lo = 64 * c->pair_meshes + 64, hi = 128 * c->pair_meshes;
-    int cap = rest < 10240 ? (int)((10240 - rest) / 2) / 64 * 64 : 0;
-    cap = cap < lo ? lo : cap;
-    return cap > hi ? hi : cap;
-}
+// PMODE 4 keeps extension and shadow pairs in one list; the shadow pairs get what is left of a 10-KB LDS budget (16 waves
+// per CU), within the clamps of lds::merged_pair_cap
+constexpr size_t MERGED_LDS_BUDGET = 10240;
+int merged_pair_cap(const ptrt_ctx *c) { return pt::lds::merged_pair_cap(c->pair_meshes, c->stack_entries, MERGED_LDS_BUDGET); }
 
 // in-wave (ray, mesh) pair compaction needs every BLAS to be one leaf and the staged
 // triangle packets to fit a modest LDS budget
 size_t pair_lds_bytes(const ptrt_ctx *c, int pmode) {
-    if (pmode == 4)
-        return (size_t)c->pair_meshes * 32 + 512 + 256 + (size_t)merged_pair_cap(c) * 2 +
-               (size_t)c->stack_entries * 64 * sizeof(uint2) + pt::LEAF_PAIR_BYTES + 24;
-    if (pmode == 3) // no mesh table; pair list for one TLAS leaf per ray; TLAS stack + the rays' leaf starts
-        return ((size_t)c->tlas_max_leaf * 64 + pt::TLAS_FILL_TARGET) * 2 + 512 * pt::TLAS_SLOTS +
-               (size_t)c->stack_entries * 64 * sizeof(uint2) + (size_t)(c->tlas_depth < 1 ? 1 : c->tlas_depth) * 512 +
-               256 * pt::TLAS_SLOTS + pt::LEAF_PAIR_BYTES + 24;
-    // staged heads (PMODE 1: and the mesh table), 16-bit pair entries, the rays' minima (whose second half holds the any-hit flags)
-    const size_t common = (size_t)c->pair_meshes * (pmode == 1 ? 48 : 32) + (pmode == 1 ? pt::pm1_pair_bytes(c->pair_meshes) : (size_t)c->pair_meshes * 128) + 512;
-    return pmode == 1 ? common + (size_t)c->pair_tri_slots * 48 + (size_t)c->pair_meshes * pt::PAIR_PAD * 16 + 16
-                      : common + (size_t)c->stack_entries * 64 * sizeof(uint2) + pt::LEAF_PAIR_BYTES + 24; // (+ the ray totals)
+    return pt::lds::pair_layout(pmode, c->pair_meshes, c->pair_tri_slots, c->stack_entries, c->tlas_max_leaf, c->tlas_depth,
+                                pmode == 4 ? merged_pair_cap(c) : 0).total;
 }
 // 0 lock-step, 1 pairs over single-leaf BLASes, 2 pairs over general BLASes (single-leaf TLAS)
 int pair_mode(const ptrt_ctx *c, int geom, bool merged) {
@@ -54,26 +39,23 @@ int pair_mode(const ptrt_ctx *c, int geom, bool merged) {
         return 1;
     // (PMODE 4's compacted leaf phase is not optional: scenes with leaves beyond its list keep PMODE 2)
     if (geom <= 1 && merged && c->leaf_pairs && c->pair_meshes < 256 && c->pair_tri_slots < (1 << 24) &&
-        (size_t)c->pair_max_leaf * 64 <= (size_t)pt::LEAF_PAIR_BYTES - 512 && pair_lds_bytes(c, 4) <= 40 * 1024)
+        pt::leaf_pairs_fit(c->pair_max_leaf) && pair_lds_bytes(c, 4) <= 40 * 1024)
         return 4;
     if (geom <= 1 && c->pair_meshes < 256 && c->pair_tri_slots < (1 << 24) && pair_lds_bytes(c, 2) <= 40 * 1024)
         return 2;
     return 0;
 }
 
-// Dynamic LDS of a launch in bytes, one formula per loop shape (PMODE 1 lays its workgroup out itself: pm1_layout).
-// A launch_trace workgroup or a ray query: PMODE 0 only has the lanes' stacks, and none where every BLAS is one leaf
+// Dynamic LDS of a launch in bytes: the total of its shape's layout in lds_layout.h (PMODE 1: pm1_layout, below).
+// A launch_trace workgroup or a ray query
 size_t trace_lds_bytes(const ptrt_ctx *c, int geom, int pmode) {
-    return pmode ? pair_lds_bytes(c, pmode) : (geom == 0 ? 0 : (size_t)c->stack_entries * 64 * sizeof(uint2));
+    return pmode ? pair_lds_bytes(c, pmode) : pt::lds::lockstep_layout(geom == 0 ? 0 : c->stack_entries).total;
 }
 // PMODE 2 with option lds_nodes: four tiles per workgroup, one LDS copy of the mesh heads and of the BLAS top levels (north
 // star: "BVH nodes ... staged in LDS")
-size_t lds_nodes_bytes(const ptrt_ctx *c) {
-    return (size_t)c->pair_meshes * (32 + pt::TOP_NODES * 64) +
-           4 * (512 + (size_t)c->pair_meshes * 128 + 256 + (size_t)c->stack_entries * 512 + pt::LEAF_PAIR_BYTES);
-}
-size_t wavefront_lds_bytes(const ptrt_ctx *c) { return (size_t)4 * ((size_t)c->stack_entries * 64 + pt::WF_RING / 2) * sizeof(uint2); }
-size_t async_lds_bytes(const ptrt_ctx *c) { return ((size_t)c->stack_entries * 64 + pt::AS_RING / 2) * sizeof(uint2) + pt::LEAF_PAIR_BYTES; }
+size_t lds_nodes_bytes(const ptrt_ctx *c) { return pt::lds::nodes_layout(c->pair_meshes, c->stack_entries, pt::TOP_NODES).total; }
+size_t wavefront_lds_bytes(const ptrt_ctx *c) { return pt::lds::wavefront_layout(c->stack_entries).total; }
+size_t async_lds_bytes(const ptrt_ctx *c) { return pt::lds::async_layout(c->stack_entries).total; }
 
 // The 3 * EV_RING events of option "time_launches" for auxiliary stream i, all of them or none: a failure part-way destroys
 // what it made and turns the option off for this context, so that no later frame records on a null event.
@@ -254,7 +236,7 @@ int run_wavefront(ptrt_ctx *c, const pt::KParams &K, bool full, size_t lds, int 
 bool async_applicable(const ptrt_ctx *c) {
     if (!c->async_lanes || !c->tlas_single_leaf || c->pair_meshes <= 0 || c->pair_meshes > 64)
         return false;
-    if ((size_t)c->pair_max_leaf * 64 > (size_t)pt::LEAF_PAIR_BYTES - 512) // its leaf phase is always the compacted one
+    if (!pt::leaf_pairs_fit(c->pair_max_leaf)) // its leaf phase is always the compacted one
         return false;
     return async_lds_bytes(c) <= 40 * 1024;
 }
@@ -441,57 +423,26 @@ bool choose_loop_shape(ptrt_ctx *c, int spp, int max_depth, int geom) {
     return tuning;
 }
 
-// PMODE 1: LDS layout of a workgroup (pt::carve_pm1) -> its size in bytes; fills K.lds_* and the tiles per workgroup.
-size_t pm1_layout(ptrt_ctx *c, pt::KParams &K, bool full, int grid, int &pm1_wg) {
-    pm1_wg = 1;
-    // PMODE 1 (pt::carve_pm1): the read-only copies are per workgroup, the lists per wave.  With the simple materials the
-    // kernel exists for one tile per workgroup at five waves per SIMD and for TWO tiles at six (option pm1_wg: 0 = the larger
-    // one if the scene fits its LDS budget, 1 / 2 force); the shading inputs are staged piece by piece while the workgroup
-    // stays within the budget of the occupancy its kernel is built for.
-    const size_t shared0 = (size_t)c->pair_tri_slots * 48 + (size_t)c->pair_meshes * (pt::PAIR_PAD * 16 + 16 + 32);
-    const size_t lights = (size_t)c->n_lights * 64, mats = (size_t)c->pair_meshes * (full ? 96 : 48);
+// PMODE 1: what a workgroup stages and how many tiles it takes (lds::pm1_choose, from the budgets of the occupancy the kernels
+// are built for) -> its size in bytes; fills K.lds_* for pt::carve_pm1.  With the simple materials the kernel exists for one
+// tile per workgroup at five waves per SIMD and for TWO tiles at six (option pm1_wg: 0 = the larger one if the scene fits its
+// LDS budget, 1 / 2 force).
+pt::lds::Pm1Choice pm1_choice(int meshes, int tri_slots, int n_lights, bool full, int stage, int sample_sync, int lds_pad, int pm1_wg) {
     // (the lanes' blue-noise slots, 512 bytes per wave, are only worth their LDS while [A] runs in every iteration: with the
     // samples in step it runs once per sample for the whole wave and reads the table itself -- room for the materials)
-    const bool stage_bn = K.sample_sync == 0;
-    auto layout = [&](int wg, size_t budget, pt::KParams &P, bool may_stage = true) -> size_t { // bytes of the workgroup, 0 if over budget
-        const size_t wave0 = 512 + pt::pm1_pair_bytes(c->pair_meshes) + 16;
-        size_t shared = (shared0 + 15) & ~(size_t)15;
-        int flags = 0;
-        if (shared + wg * wave0 + (size_t)c->lds_pad > budget)
-            return 0;
-        const size_t extra_at = shared;
-        size_t wave = wave0;
-        if (may_stage && c->stage && shared + 128 + wg * (wave0 + (stage_bn ? 512 : 0)) + (size_t)c->lds_pad <= budget) {
-            flags = 4 | (stage_bn ? 8 : 0);
-            shared += 128;
-            wave += stage_bn ? 512 : 0;
-            if ((c->stage & 1) && c->n_lights > 0 && c->n_lights <= pt::LDS_LIGHTS && shared + lights + wg * wave + (size_t)c->lds_pad <= budget) {
-                flags |= 1;
-                shared += lights;
-            }
-            if ((c->stage & 2) && c->pair_meshes <= 42 && shared + mats + wg * wave + (size_t)c->lds_pad <= budget) {
-                flags |= 2;
-                shared += mats;
-            }
-        }
-        P.lds_extra = (int)extra_at;
-        P.lds_flags = flags;
-        P.lds_wave = (int)shared;
-        P.lds_wave_bytes = (int)wave;
-        return shared + wg * wave + (size_t)c->lds_pad;
-    };
-    size_t need = 0;
-    if (!full && c->pm1_wg != 1)
-        need = layout(2, (size_t)pt::lds_per_workgroup(1, false, 2), K);
-    if (need) {
-        pm1_wg = 2;
-    } else {
-        need = layout(1, (size_t)pt::lds_per_wave(1, full), K);
-        if (!need) // (over the budget of the kernel's occupancy: pair_mode admitted the scene, so it runs, with nothing staged)
-            need = layout(1, 64 * 1024, K, false);
-    }
+    const bool stage_bn = sample_sync == 0;
+    return pt::lds::pm1_choose(meshes, tri_slots, n_lights, full, stage, stage_bn, lds_pad, pm1_wg, (size_t)pt::lds_per_workgroup(1, false, 2),
+                               (size_t)pt::lds_per_wave(1, full), 64 * 1024);
+}
+size_t pm1_layout(ptrt_ctx *c, pt::KParams &K, bool full, int grid, int &pm1_wg) {
+    const pt::lds::Pm1Choice P = pm1_choice(c->pair_meshes, c->pair_tri_slots, c->n_lights, full, c->stage, K.sample_sync, c->lds_pad, c->pm1_wg);
+    K.lds_extra = P.s.lds_extra;
+    K.lds_flags = P.s.lds_flags;
+    K.lds_wave = P.s.lds_wave;
+    K.lds_wave_bytes = P.s.lds_wave_bytes;
+    pm1_wg = P.wg;
     K.n_tiles = grid;
-    return need;
+    return P.total;
 }
 
 // What one ptrt_render call has decided about its trace: the loop shape that renders the frame and the facts its launch
