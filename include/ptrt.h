@@ -169,6 +169,15 @@ typedef struct ptrt_probe {
     float reserved[2];      /* 0.0f                                                                                      */
 } ptrt_probe;
 
+/* One lightmap texel's answer from ptrt_query_irradiance: means over the texel's n_dirs rays, 32 bytes. */
+typedef struct ptrt_irradiance {
+    float radiance[3];      /* mean of L_c(t, k); irradiance = pi * this for cosine-distributed directions */
+    float mean_distance;    /* mean of dist = min(depth, max_distance); a miss has depth 1e30f              */
+    float mean_distance_sq; /* mean of dist * dist                                                          */
+    float hit_fraction;     /* mean of (object_id >= 0 ? 1.0f : 0.0f)                                       */
+    float reserved[2];      /* 0.0f                                                                         */
+} ptrt_irradiance;
+
 /* Per-frame counters of the trace stage (Mrays/s numerator). */
 typedef struct ptrt_stats {
     uint64_t extension_rays; /* traceRay calls   (intersection.cuh:526) */
@@ -599,6 +608,55 @@ int ptrt_query_radiance(ptrt_ctx *ctx, const float *origins, const float *direct
 int ptrt_query_probes(ptrt_ctx *ctx, const float *d_positions, int n_probes, const float *d_directions, int n_dirs,
                       uint32_t *d_rng_states, int samples, int max_depth, float max_distance, ptrt_probe *d_out);
 
+/* Lightmap texels on DEVICE memory: the cosine-gather irradiance query (ABI 6, addition only; no counterpart in the
+ * reference).  Texel t has a position positions[t] and a normal N = normals[t] (n_texels*3 floats each; N is used as given and
+ * NOT normalised -- callers pass unit normals) and gathers n_dirs rays.  Ray (t, k), every operation in float32 and separately
+ * rounded:
+ *     samples     u1 = samples2[2k], u2 = samples2[2k+1] (`d_samples2`: ONE set of n_dirs points in [0,1)^2 shared by all texels,
+ *                 used as given); with `d_phases` (n_texels floats, the per-texel rotation; may be NULL) u2 becomes
+ *                 u2 + phases[t], minus 1.0f if that sum is >= 1.0f
+ *     local       r = sqrt(u1), phi = 6.28318530717958647692f * u2, (r*cos(phi), r*sin(phi), sqrt(max(0, 1 - u1))): the path
+ *                 tracer's own cosine-hemisphere sample (sampling.cuh) with u1, u2 in place of generator draws, its sine and
+ *                 cosine the library's deterministic ones
+ *     direction   local.x*T + local.y*B + local.z*N with T, B the reference's createOrthoNormalBasis(N) (hemisphere_to_world),
+ *                 its branch for a degenerate normal included
+ *     origin      positions[t] + offset*N, per component: the product, then the sum
+ *     state       t*n_dirs + k of `d_rng_states` (n_texels*n_dirs*6 uint32, canonical order, advanced IN PLACE as by
+ *                 ptrt_query_radiance)
+ * L(t,k), the first-hit depth and the object id of ray (t, k) are BY DEFINITION what ptrt_query_radiance puts into ptrt_radiance
+ * for that ray and state with the same `samples` and `max_depth` -- the quirk that a caller's ray takes no light sample at its
+ * first hit included.  So the direct term of the analytic lights (ptrt_upload_lights) at the texel itself and at a gather ray's
+ * first hit is absent, as it is in a frame's first vertex; emissive meshes, the sky and the environment map are seen, and the
+ * lights do light every later vertex of a path.  Texel t's record holds MEANS over k:
+ *     radiance[c]       L_c(t, k)                          (pi times it is the irradiance, for cosine-distributed directions)
+ *     mean_distance     dist = min(depth, max_distance)    (a miss has depth 1e30f)
+ *     mean_distance_sq  dist*dist
+ *     hit_fraction      object_id >= 0 ? 1.0f : 0.0f
+ * and reserved is 0.0f.  The sum order of every quantity is part of the contract.  Let w be the smallest power of two >= n_dirs
+ * if n_dirs <= 64, else 64.  A chunk of w consecutive k, padded with +0.0f terms for absent k (selected, not computed), is
+ * summed by folding halves -- v[j] + v[j + w/2], then w/4, .. 1 --, the chunk sums are added in chunk order to a total that
+ * starts at +0.0f (one chunk when n_dirs <= 64), and the total is divided by (float)n_dirs (IEEE division).  For w = 64 this is
+ * ptrt_query_probes's order; tests/irradiance_restatement.py states it in numpy.
+ * ptrt_irradiance_rays writes exactly these origins and directions (n_texels*n_dirs*3 floats each, ray t*n_dirs + k) with one
+ * small kernel on the context's stream: to the bake what ptrt_camera_rays is to a frame -- fed to ptrt_query_radiance with the
+ * same states they give the per-ray records the texel's means are formed from, bit for bit.  It needs no uploaded scene, and
+ * takes at most (2^31 - 1) * 256 rays per call (one thread per ray in blocks of 256; more is PTRT_E_INVALID).
+ * Ordering and side effects are those of ptrt_query_probes: enqueued on the context's stream with no allocation, copy or
+ * synchronisation; neither call touches the context's generator states, frame buffers, ptrt_get_stats counters or timing
+ * histories; ptrt_get_option "query_pmode" reports the query's traversal, option "persist" sizes its grid.  Up to 64 directions
+ * a wave owns 64/w consecutive texels; beyond, one texel, whose chunks of 64 directions it walks in order.  PTRT_E_INVALID
+ * (nothing enqueued; `d_out`, the states and the ray targets untouched) for n_texels < 0, n_dirs < 1, a NULL pointer other than
+ * d_phases, memory that is not the context's device memory or an allocation too small (byte counts are formed in size_t), an
+ * offset that is not finite, and for the query samples / max_depth outside 1..32767 or a max_distance that is not positive
+ * and finite; ptrt_query_irradiance returns PTRT_E_NOT_READY before geometry and materials are uploaded; n_texels == 0 returns
+ * PTRT_OK and launches nothing. */
+int ptrt_irradiance_rays(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n_texels,
+                         const float *d_samples2, int n_dirs, const float *d_phases /* may be NULL */, float offset,
+                         float *d_origins, float *d_directions);
+int ptrt_query_irradiance(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n_texels,
+                          const float *d_samples2, int n_dirs, const float *d_phases /* may be NULL */, float offset,
+                          uint32_t *d_rng_states, int samples, int max_depth, float max_distance, ptrt_irradiance *d_out);
+
 /* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
  * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small
  * kernel on the context's stream into DEVICE memory: rows*W*3 floats each (render_w*render_h*3 at a reduced render size),
@@ -740,7 +798,7 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         2: wherever PMODE 1 runs; 0: never.  ptrt_get_option "refilled" says what the last frame did.
  *                         ticket_tiles 1..16: consecutive tiles per draw from the queue (1; more only pays where the counter
  *                         itself binds -- 1 spp: 0.61 -> 0.49 ms with 4, still behind the one-tile-per-wave kernel's 0.43).
- *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance and ptrt_query_probes: N one-wave workgroups per CU
+ *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance, ptrt_query_probes and ptrt_query_irradiance: N one-wave workgroups per CU
  *                         instead of what the kernel's occupancy holds (tests: a grid smaller than the batch's chunks).
  *   sample_sync -1|0|1    the lanes of a wave start their samples together (1) instead of each as soon as its path has ended (0):
  *                         the wave's lanes then sit at the same bounce, the light-sample phases are skipped by the whole wave at a
@@ -810,7 +868,7 @@ int ptrt_set_option(ptrt_ctx *ctx, const char *name, long long value);
  * timed: render_mode (0 megakernel, 1 wavefront stages, 2 asynchronous lanes), pmode (0 lock-step, 1 pairs over LDS-staged
  * triangles, 2 pair queue, 3 TLAS rounds, 4 merged queue), merged_eff (loop shape of that launch), merged_decided (0 while
  * merged = -1 is still sampling), launches.  ABI 5.  Also read-only (ABI 6): query_pmode, the traversal of the last
- * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes (-1 none yet), and stream, the hipStream_t the context enqueues on. */
+ * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes / ptrt_query_irradiance (-1 none yet), and stream, the hipStream_t the context enqueues on. */
 int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
 
 /* The plan behind option "pm1_lane_groups" for leaves of `leaf_triangles` triangles, as ptrt_upload_geometry builds it; needs

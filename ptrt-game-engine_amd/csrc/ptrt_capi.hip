@@ -20,6 +20,7 @@
 #include "pt_query.hip.h"
 #include "pt_radiance.hip.h"
 #include "pt_probe.hip.h"
+#include "pt_irradiance.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>

@@ -417,6 +417,21 @@ int hs_query_probes(void *s, const void *d_positions, int n_probes, const void *
                                                 static_cast<ptrt_probe *>(d_out)));
     return 0;
 }
+int hs_query_irradiance(void *s, const void *d_positions, const void *d_normals, int n_texels, const void *d_samples2, int n_dirs,
+                        const void *d_phases, float offset, void *d_rng_states, int samples, int max_depth, float max_distance, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryIrradiance(static_cast<const float *>(d_positions), static_cast<const float *>(d_normals), n_texels,
+                                                    static_cast<const float *>(d_samples2), n_dirs, static_cast<const float *>(d_phases),
+                                                    offset, static_cast<uint32_t *>(d_rng_states), samples, max_depth, max_distance,
+                                                    static_cast<ptrt_irradiance *>(d_out)));
+    return 0;
+}
+int hs_irradiance_rays(void *s, const void *d_positions, const void *d_normals, int n_texels, const void *d_samples2, int n_dirs,
+                       const void *d_phases, float offset, void *d_origins, void *d_dirs) {
+    HS_TRY(static_cast<Scene *>(s)->irradianceRays(static_cast<const float *>(d_positions), static_cast<const float *>(d_normals), n_texels,
+                                                   static_cast<const float *>(d_samples2), n_dirs, static_cast<const float *>(d_phases),
+                                                   offset, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
+    return 0;
+}
 int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
     HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;

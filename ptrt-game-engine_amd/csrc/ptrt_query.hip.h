@@ -1,6 +1,7 @@
 // ptrt_query.hip.h -- the device queries of the C ABI: closest hit and occlusion (ptrt_trace_rays, ptrt_query_rays), path-traced
-// radiance (ptrt_query_radiance), light probes (ptrt_query_probes) and the two kernels that let a caller start where a frame
-// starts (ptrt_camera_rays, ptrt_init_rng_states).  What the three traversing queries share is decided once each: the traversal
+// radiance (ptrt_query_radiance), light probes (ptrt_query_probes), lightmap texels (ptrt_query_irradiance, with
+// ptrt_irradiance_rays for the rays alone) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
+// ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
 // (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
 // check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
 // refresh_tlas_heads) and the helpers every entry point shares.
@@ -60,7 +61,7 @@ template <class F> int with_variant(int geom, int pmode, F &&f) {
 }
 
 // A persistent grid of one-wave workgroups: about one per wave slot of the chip, and no more than there are `units` of work for
-// the grid-stride loop (chunks of 64 rays, or probes).  `honour_persist`: option "persist" (persistent waves per CU) overrides
+// the grid-stride loop (chunks of 64 rays, probes, or groups of texels). `honour_persist`: option "persist" (persistent waves per CU) overrides
 // the occupancy the runtime reports -- the shading queries, not the ray queries (include/ptrt.h).
 template <class Kernel, class... Args>
 int launch_persistent(ptrt_ctx *c, Kernel kernel, size_t lds, size_t units, bool honour_persist, const Args &...args) {
@@ -232,6 +233,89 @@ int ptrt_query_probes(ptrt_ctx *c, const float *d_positions, int n_probes, const
         return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
             return launch_persistent(c, pt::probe_query_kernel<G, FULL, PM>, P.lds, probes, true, P.K, d_positions, n_probes, d_directions,
                                      n_dirs, d_rng_states, max_distance, o);
+        });
+    };
+    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+}
+
+int ptrt_irradiance_rays(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
+                         const float *d_phases, float offset, float *d_origins, float *d_directions) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_irradiance_rays: bad context");
+    if (n_texels < 0 || n_dirs < 1 || !d_positions || !d_normals || !d_samples2 || !d_origins || !d_directions)
+        return fail(c, PTRT_E_INVALID, "ptrt_irradiance_rays: bad argument (n_texels %d, n_dirs %d, positions %p, normals %p, samples2 %p, "
+                                       "origins %p, directions %p)", n_texels, n_dirs, (const void *)d_positions, (const void *)d_normals,
+                    (const void *)d_samples2, (const void *)d_origins, (const void *)d_directions);
+    if (!std::isfinite(offset))
+        return fail(c, PTRT_E_INVALID, "ptrt_irradiance_rays: offset=%g (finite)", (double)offset);
+    if (n_texels == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const size_t texels = (size_t)n_texels, ndirs = (size_t)n_dirs, rays = texels * ndirs;
+    if (rays > SIZE_MAX / 24)
+        return fail(c, PTRT_E_INVALID, "ptrt_irradiance_rays: %d texels x %d directions: the rays' byte count overflows", n_texels, n_dirs);
+    // one thread per ray in blocks of 256: the grid's x extent is an int
+    constexpr size_t MAX_RAYS = (size_t)INT_MAX * 256;
+    if (rays > MAX_RAYS)
+        return fail(c, PTRT_E_INVALID, "ptrt_irradiance_rays: %d texels x %d directions: more than %zu rays in one call", n_texels, n_dirs,
+                    MAX_RAYS);
+    const Span sp{"positions", d_positions, texels * 12}, sn{"normals", d_normals, texels * 12}, ss{"samples2", d_samples2, ndirs * 8},
+        sph{"phases", d_phases, texels * sizeof(float)}, so{"origins", d_origins, rays * 12}, sd{"directions", d_directions, rays * 12};
+    if (int rc = d_phases ? check_spans(c, "ptrt_irradiance_rays", {sp, sn, ss, sph, so, sd})
+                          : check_spans(c, "ptrt_irradiance_rays", {sp, sn, ss, so, sd}))
+        return rc;
+    c->touched = true;
+    // irradiance_rays_kernel (pt_irradiance.hip.h): one thread per ray
+    hipLaunchKernelGGL(pt::irradiance_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, c->stream, d_positions, d_normals, rays,
+                       d_samples2, n_dirs, d_phases, offset, d_origins, d_directions);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_query_irradiance(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
+                          const float *d_phases, float offset, uint32_t *d_rng_states, int samples, int max_depth, float max_distance,
+                          ptrt_irradiance *d_out) {
+    static_assert(sizeof(pt::IrradianceOut) == sizeof(ptrt_irradiance) && sizeof(ptrt_irradiance) == 32,
+                  "IrradianceOut must mirror ptrt_irradiance");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_irradiance: bad context");
+    if (n_texels < 0 || n_dirs < 1 || !d_positions || !d_normals || !d_samples2 || !d_rng_states || !d_out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_irradiance: bad argument (n_texels %d, n_dirs %d, positions %p, normals %p, samples2 %p, "
+                                       "rng_states %p, out %p)", n_texels, n_dirs, (const void *)d_positions, (const void *)d_normals,
+                    (const void *)d_samples2, (const void *)d_rng_states, (const void *)d_out);
+    if (!std::isfinite(offset))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_irradiance: offset=%g (finite)", (double)offset);
+    if (int rc = check_shading_query(c, "ptrt_query_irradiance", samples, max_depth, &max_distance))
+        return rc;
+    if (n_texels == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    // byte counts in size_t: n_texels * n_dirs rays is below 2^62 and fits; times 24 bytes of state it need not
+    const size_t texels = (size_t)n_texels, ndirs = (size_t)n_dirs, rays = texels * ndirs;
+    if (rays > SIZE_MAX / 24)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_irradiance: %d texels x %d directions: the states' byte count overflows", n_texels, n_dirs);
+    const Span sp{"positions", d_positions, texels * 12}, sn{"normals", d_normals, texels * 12}, ss{"samples2", d_samples2, ndirs * 8},
+        sph{"phases", d_phases, texels * sizeof(float)}, sst{"rng_states", d_rng_states, rays * 24},
+        sout{"out", d_out, texels * sizeof(ptrt_irradiance)};
+    if (int rc = d_phases ? check_spans(c, "ptrt_query_irradiance", {sp, sn, ss, sph, sst, sout})
+                          : check_spans(c, "ptrt_query_irradiance", {sp, sn, ss, sst, sout}))
+        return rc;
+    QueryPlan P;
+    if (int rc = plan_query(c, true, samples, max_depth, P))
+        return rc;
+    // irradiance_query_kernel (pt_irradiance.hip.h): the grid strides over groups of 64 / w texels, w the smallest power of two
+    // >= n_dirs; beyond 64 directions over texels, one wave per texel
+    int w = 1;
+    while (w < 64 && w < n_dirs)
+        w *= 2;
+    const size_t per_group = (size_t)(64 / w), groups = (texels + per_group - 1) / per_group;
+    pt::IrradianceOut *o = reinterpret_cast<pt::IrradianceOut *>(d_out);
+    auto launch = [&](auto FULL) {
+        return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+            return launch_persistent(c, pt::irradiance_query_kernel<G, FULL, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels,
+                                     d_samples2, n_dirs, d_phases, offset, d_rng_states, max_distance, o);
         });
     };
     return P.full ? launch(std::true_type{}) : launch(std::false_type{});

@@ -1073,6 +1073,27 @@ class Scene {
                                 max_depth > 0 ? max_depth : perfSettings.maxBounceDepth, max_distance, d_out),
               "Probe query failed");
     }
+    // Lightmap texels (ptrt_query_irradiance): texel t gathers n_dirs rays from d_positions[t] + offset * d_normals[t], ray (t, k)
+    // along the cosine-distributed direction the k-th point of d_samples2 (n_dirs * 2 floats in [0,1), ONE set for all texels,
+    // rotated by d_phases[t] if given) maps to about the normal, with generator state t * n_dirs + k (advanced in place); d_out
+    // gets one 32-byte ptrt_irradiance per texel -- mean radiance (pi times it: the irradiance), mean hit distance (clamped to
+    // max_distance), its square and the hit fraction.  Commits what queryRadiance commits.  max_depth <= 0: the frame's depth.
+    void queryIrradiance(const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
+                         const float *d_phases, float offset, uint32_t *d_rng_states, int samples, int max_depth, float max_distance,
+                         ptrt_irradiance *d_out) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_query_irradiance(ctx, d_positions, d_normals, n_texels, d_samples2, n_dirs, d_phases, offset, d_rng_states, samples,
+                                    max_depth > 0 ? max_depth : perfSettings.maxBounceDepth, max_distance, d_out),
+              "Irradiance query failed");
+    }
+    // The rays queryIrradiance traces (ptrt_irradiance_rays): n_texels * n_dirs * 3 floats each, ray t * n_dirs + k.
+    void irradianceRays(const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
+                        const float *d_phases, float offset, float *d_origins, float *d_dirs) {
+        needBackend();
+        check(ptrt_irradiance_rays(ctx, d_positions, d_normals, n_texels, d_samples2, n_dirs, d_phases, offset, d_origins, d_dirs),
+              "Irradiance rays failed");
+    }
     // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
     // tile rows * width * 3 floats each, in the order of the colour buffer.
     void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {

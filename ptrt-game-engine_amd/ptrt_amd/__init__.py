@@ -123,6 +123,12 @@ class Probe(C.Structure):
                 ("hit_fraction", C.c_float), ("reserved", C.c_float * 2)]
 
 
+class Irradiance(C.Structure):
+    """`ptrt_irradiance`: one lightmap texel's answer from ptrt_query_irradiance."""
+    _fields_ = [("radiance", C.c_float * 3), ("mean_distance", C.c_float), ("mean_distance_sq", C.c_float),
+                ("hit_fraction", C.c_float), ("reserved", C.c_float * 2)]
+
+
 class Stats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64),
                 ("shadow_rays_walked", C.c_uint64)]
@@ -137,6 +143,9 @@ assert RADIANCE_DTYPE.itemsize == C.sizeof(Radiance) == 32
 PROBE_DTYPE = np.dtype([("sh", "<f4", (9, 3)), ("mean_distance", "<f4"), ("mean_distance_sq", "<f4"), ("hit_fraction", "<f4"),
                         ("reserved", "<f4", 2)])
 assert PROBE_DTYPE.itemsize == C.sizeof(Probe) == 128
+IRRADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("mean_distance", "<f4"), ("mean_distance_sq", "<f4"), ("hit_fraction", "<f4"),
+                             ("reserved", "<f4", 2)])
+assert IRRADIANCE_DTYPE.itemsize == C.sizeof(Irradiance) == 32
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
@@ -178,6 +187,8 @@ _sig("ptrt_render_wireframe", C.c_int, _vp, C.c_float, _vp, C.c_int)
 _sig("ptrt_query_rays", C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp)
 _sig("ptrt_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("ptrt_query_probes", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp)
+_sig("ptrt_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp)
+_sig("ptrt_query_irradiance", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
@@ -304,6 +315,8 @@ _sig("hs_query_closest", C.c_int, _vp, _vp, _vp, C.c_int, _vp)
 _sig("hs_query_occluded", C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp)
 _sig("hs_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("hs_query_probes", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp)
+_sig("hs_query_irradiance", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_float, _vp)
+_sig("hs_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -409,6 +422,19 @@ def probe_fields(probes):
     for name, (a, b) in PROBE_COLUMNS.items():
         col = probes[:, a:b]
         out[name] = col.reshape(-1, 9, 3) if name == "sh" else col[:, 0] if b - a == 1 else col
+    return out
+
+
+# columns of the (n, 8) float32 rows of Scene.query_irradiance: the fields of ptrt_irradiance / IRRADIANCE_DTYPE
+IRRADIANCE_COLUMNS = dict(radiance=(0, 3), mean_distance=(3, 4), mean_distance_sq=(4, 5), hit_fraction=(5, 6), reserved=(6, 8))
+
+
+def irradiance_fields(records):
+    """Named views of query_irradiance's (n, 8) float32 rows (a tensor or an array): radiance as (n, 3), scalars as (n,)."""
+    out = {}
+    for name, (a, b) in IRRADIANCE_COLUMNS.items():
+        col = records[:, a:b]
+        out[name] = col[:, 0] if b - a == 1 else col
     return out
 
 
@@ -985,6 +1011,71 @@ class Scene:
             0 if max_depth is None else int(max_depth), float(max_distance), _vp(out.data_ptr()))))
         return out
 
+    def _texel_inputs(self, what, positions, normals, samples2, phases):
+        """the shared inputs of query_irradiance / irradiance_rays, checked; returns (n texels, k directions)"""
+        self._device_tensor(f"{what}: positions", positions, 3, "torch.float32")
+        self._device_tensor(f"{what}: normals", normals, 3, "torch.float32")
+        self._device_tensor(f"{what}: samples2", samples2, 2, "torch.float32")
+        n, k = positions.shape[0], samples2.shape[0]
+        if normals.shape[0] != n:
+            raise ValueError(f"{what}: {n} positions, {normals.shape[0]} normals")
+        if k < 1:
+            raise ValueError(f"{what}: no directions")
+        if n >= 2 ** 31 or k >= 2 ** 31:
+            raise ValueError(f"{what}: {n} texels x {k} directions (at most 2^31 - 1 of each per call)")
+        if phases is not None:
+            if not _is_tensor(phases) or phases.dim() != 1:
+                raise ValueError(f"{what}: phases: needs a torch tensor of shape (n,) on the scene's device")
+            self._device_tensor(f"{what}: phases", phases.unsqueeze(1), 1, "torch.float32")
+            if phases.shape[0] != n:
+                raise ValueError(f"{what}: {n} positions, {phases.shape[0]} phases")
+        return n, k
+
+    def query_irradiance(self, positions, normals, samples2, rng_states, samples=1, max_depth=None, max_distance=1e30, offset=1e-4,
+                         phases=None, out=None):
+        """Lightmap texels: texel t gathers one ray per point of `samples2` (k points in [0,1)^2, one set for all texels, used
+        as given) from positions[t] + offset * normals[t], along the cosine-distributed direction that point maps to about
+        normals[t] (unit normals expected; `phases`, (n,) float32, rotates each texel's set about its normal), ray (t, k) with
+        generator state t * k_dirs + k, `samples` paths of `max_depth` bounces each (None: the scene's bounce depth).  torch
+        tensors on this scene's device, contiguous, read in place: positions and normals (n, 3), samples2 (k, 2) float32,
+        rng_states (n * k, 6) int32 (or uint32) ADVANCED IN PLACE.  Returns an (n, 8) float32 tensor, one 32-byte
+        `ptrt_irradiance` per row (`irradiance_fields` names the columns): the means over the directions of the radiance
+        (0:3; pi times it is the irradiance), of the first-hit distance clamped to `max_distance` (3), of its square (4), and
+        the fraction of rays that hit (5); `out` takes such a tensor to write into.  `ptrt_amd.lightmap` has sample sets,
+        phases, quads and the irradiance.  No synchronisation."""
+        n, k = self._texel_inputs("query_irradiance", positions, normals, samples2, phases)
+        self._device_tensor("query_irradiance: rng_states", rng_states, 6, "torch.int32|torch.uint32")
+        if rng_states.shape[0] != n * k:
+            raise ValueError(f"query_irradiance: {n} texels x {k} directions need {n * k} states, got {rng_states.shape[0]}")
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=positions.device)
+        else:
+            self._device_tensor("query_irradiance: out", out, 8, "torch.float32")
+            if out.shape[0] != n:
+                raise ValueError(f"query_irradiance: out has {out.shape[0]} rows for {n} texels")
+        if n == 0:
+            return out
+        self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_irradiance(
+            self._h, _vp(positions.data_ptr()), _vp(normals.data_ptr()), n, _vp(samples2.data_ptr()), k,
+            None if phases is None else _vp(phases.data_ptr()), float(offset), _vp(rng_states.data_ptr()), int(samples),
+            0 if max_depth is None else int(max_depth), float(max_distance), _vp(out.data_ptr()))))
+        return out
+
+    def irradiance_rays(self, positions, normals, samples2, offset=1e-4, phases=None):
+        """(origins, directions): (n * k, 3) float32 tensors holding the rays query_irradiance traces for these texels, ray
+        (t, k) in row t * k_dirs + k (ptrt_irradiance_rays).  Arguments as for query_irradiance.  No synchronisation."""
+        n, k = self._texel_inputs("irradiance_rays", positions, normals, samples2, phases)
+        import torch
+        o = torch.empty((n * k, 3), dtype=torch.float32, device=positions.device)
+        d = torch.empty((n * k, 3), dtype=torch.float32, device=positions.device)
+        if n == 0:
+            return o, d
+        self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_irradiance_rays(
+            self._h, _vp(positions.data_ptr()), _vp(normals.data_ptr()), n, _vp(samples2.data_ptr()), k,
+            None if phases is None else _vp(phases.data_ptr()), float(offset), _vp(o.data_ptr()), _vp(d.data_ptr()))))
+        return o, d
+
     def camera_rays(self, frame, sample=0):
         """(origins, directions): (rows * width, 3) float32 tensors on this scene's device holding the primary rays
         render_to_device gives sample `sample` of frame `frame`, in the order of `read(BUF_ACCUM)` (ptrt_camera_rays; pinhole
@@ -1093,4 +1184,4 @@ class TileFarm:
             pass
 
 
-from . import cameras, probes, scenes  # noqa: E402,F401
+from . import cameras, lightmap, probes, scenes  # noqa: E402,F401
