@@ -698,7 +698,9 @@ int ptrt_get_stats(ptrt_ctx *ctx, ptrt_stats *out);
  * accum/normal width*height*3 floats, depth width*height floats, object_id width*height ints, top-down,
  * i.e. the bands' ptrt_device_buffer contents concatenated in row order.  Camera, previous view-projection
  * and the denoiser/bloom switches are the context's own.  PTRT_E_INVALID for a band context, a reduced
- * render size, or when neither stage is enabled. */
+ * render size, or when neither stage is enabled.  Object ids are any `int32_t` but `INT_MIN`, which the
+ * a-trous staging uses for "outside the image or sky" (`AT_OUTSIDE`): a pixel with that id would be dropped
+ * from every tap of every pass. */
 int ptrt_post_frame(ptrt_ctx *ctx, const float *accum, const float *normal, const float *depth,
                     const int32_t *object_id, void *out_rgb8, int out_is_device);
 

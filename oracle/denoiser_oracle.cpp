@@ -1,6 +1,6 @@
 /*
  * oracle/denoiser_oracle.cpp -- TEST INFRASTRUCTURE (CPU oracle, never linked into the product).
- * PARITY UNPINNED (see ptrt_oracle.cpp): the reference ships no vectors for this stage either.
+ * The reference ships no vectors for this stage; this reading is pinned by the float64 statement of tests/post_truth.py.
  *
  * Restates the post-process that follows the path tracer when the denoiser is enabled
  * (SURVEY 8(f) rank 1):

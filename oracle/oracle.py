@@ -169,6 +169,17 @@ def tonemap(accum, width, rows, threads=1):
     return out
 
 
+lib.oracle_tonemap_float.argtypes = [_fp, C.c_int, _fp]
+
+
+def tonemap_float(image):
+    """tonemap_kernel without its last line: the clamped sRGB value per channel, (n, 3) in the image's own order."""
+    img = np.ascontiguousarray(image, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros_like(img)
+    lib.oracle_tonemap_float(_f(img), img.shape[0], _f(out))
+    return out
+
+
 def trace_rays(scene_desc_ptr, origins, directions):
     o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
     d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)

@@ -1,6 +1,6 @@
 /*
  * oracle/post_oracle.cpp -- TEST INFRASTRUCTURE (CPU oracle, never linked into the product).
- * PARITY UNPINNED (see ptrt_oracle.cpp): the reference ships no vectors for this stage either.
+ * The reference ships no vectors for this stage; this reading is pinned by the float64 statement of tests/post_truth.py.
  *
  * Restates the rest of Scene::render_to_device's post chain, literally,
  * launch by launch, including the reference's mip bookkeeping (mip_w/mip_h are halved on the way

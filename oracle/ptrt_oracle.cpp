@@ -1733,6 +1733,18 @@ void oracle_tonemap(const float *accum, int width, int rows, int total_samples, 
     });
 }
 
+/* tonemap_kernel up to, and without, its last line: the clamped sRGB value of each channel before `* 255.99f` and the cast,
+ * n pixels in the caller's order (tests/post_truth.py judges this number; the bytes hang on a truncation) */
+void oracle_tonemap_float(const float *accum, int n, float *out) {
+    for (int i = 0; i < n; ++i) {
+        V3 color = aces_tonemap(V3(accum[i * 3], accum[i * 3 + 1], accum[i * 3 + 2]) / 1.0f);
+        color = clampv(V3(srgb_oetf(color.x), srgb_oetf(color.y), srgb_oetf(color.z)), 0.f, 1.f);
+        out[i * 3] = color.x;
+        out[i * 3 + 1] = color.y;
+        out[i * 3 + 2] = color.z;
+    }
+}
+
 /* trace_single_ray_kernel (scene_kernels.cuh:38-49), batched */
 void oracle_trace_rays(const ptrt_scene_desc *scene, const float *origins, const float *directions, int n,
                        ptrt_hit *out) {

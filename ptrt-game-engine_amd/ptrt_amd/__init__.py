@@ -134,10 +134,29 @@ class Stats(C.Structure):
                 ("shadow_rays_walked", C.c_uint64)]
 
 
+class DenoiserSettings(C.Structure):
+    """`ptrt_denoiser_settings` (DenoiserSettings of the non-split path, denoiser.cuh:36-73), filled with the reference's defaults
+    by ptrt_denoiser_default_settings; keyword arguments override fields.  Pass to Scene.setDenoiserSettings."""
+    _fields_ = [("tau", C.c_float), ("min_alpha", C.c_float), ("max_history", C.c_float), ("sigma_luminance", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("atrous_iterations", C.c_int32),
+                ("clamp_scale", C.c_float), ("firefly_threshold", C.c_float), ("depth_reject_absolute", C.c_float),
+                ("depth_reject_relative", C.c_float), ("normal_reject_threshold", C.c_float), ("sky_depth_threshold", C.c_float),
+                ("edge_depth_threshold", C.c_float), ("edge_normal_threshold", C.c_float), ("use_object_ids", C.c_int32),
+                ("enable_firefly_suppression", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib.ptrt_denoiser_default_settings(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise AttributeError(f"ptrt_denoiser_settings has no field {k!r}")
+            setattr(self, k, v)
+
+
 HIT_DTYPE = np.dtype([("hit", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3),
                       ("mesh_index", "<i4"), ("front_face", "<i4"), ("u", "<f4"), ("v", "<f4"),
                       ("face_index", "<i4"), ("local_point", "<f4", 3)])
-assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
+assert HIT_DTYPE.itemsize == C.sizeof(Hit) == 64 and C.sizeof(DenoiserSettings) == 68
 RADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("object_id", "<i4")])
 assert RADIANCE_DTYPE.itemsize == C.sizeof(Radiance) == 32
 PROBE_DTYPE = np.dtype([("sh", "<f4", (9, 3)), ("mean_distance", "<f4"), ("mean_distance_sq", "<f4"), ("hit_fraction", "<f4"),
@@ -284,6 +303,7 @@ _sig("ptrt_denoiser_default_settings", None, _vp)
 _sig("ptrt_denoiser_enable", C.c_int, _vp, _vp)
 _sig("ptrt_denoiser_disable", C.c_int, _vp)
 _sig("ptrt_set_prev_view_proj", C.c_int, _vp, _fp)
+_sig("ptrt_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
 _sig("hs_refit_object_changes", C.c_int, _vp)
 _sig("hs_refit_from_device", C.c_int, _vp, C.c_int, _vp)
 _sig("hs_refit_from_host", C.c_int, _vp, C.c_int, _vp)
@@ -599,6 +619,14 @@ class Scene:
     def getSamplesPerPixel(self): return lib.hs_get_samples_per_pixel(self._h)
     def setPerfSamplesPerPixel(self, n): lib.hs_set_perf_samples_per_pixel(self._h, n)
     def setDenoiserEnabled(self, e): self._chk(lib.hs_set_denoiser_enabled(self._h, int(e)))
+    def setDenoiserSettings(self, settings):
+        """`ptrt_denoiser_enable(ctx, &settings)` on the live context: a new Denoiser with these settings (a `DenoiserSettings`)
+        at the current render size; the history starts over.  Whether frames use it stays with setDenoiserEnabled.  Full-frame
+        scenes only; a later setResolutionScale re-creates the denoiser with the defaults, as the reference does."""
+        if not isinstance(settings, DenoiserSettings):
+            raise TypeError("setDenoiserSettings takes a ptrt_amd.DenoiserSettings")
+        self._cchk(lib.ptrt_denoiser_enable(self.ctx, C.byref(settings)))
+
     def setBloomEnabled(self, e): lib.hs_set_bloom_enabled(self._h, int(e))
     def setPerformancePreset(self, name): self._chk(lib.hs_set_performance_preset(self._h, name.encode()))
     def setResolutionScale(self, s): self._chk(lib.hs_set_resolution_scale(self._h, float(s)))

@@ -1,5 +1,6 @@
 """Motion vectors + spatiotemporal denoiser: oracle properties on CPU, GPU parity
-(bit-exact) on the box.  PARITY UNPINNED w.r.t. the CUDA reference (no vectors exist for this stage)."""
+(bit-exact) on the box.  The reference ships no vectors for this stage; what pins the oracle's reading of it is the float64
+statement of tests/post_truth.py (tests/test_post_truth.py, tests/test_post_truth_gpu.py)."""
 import numpy as np
 import pytest
 
