@@ -534,14 +534,17 @@ class Scene {
     // commit.  The host copy of a tree kept on the GPU is brought up to date when something reads it (flatten(), a real
     // TLAS, the next full upload).  So the UNCHANGED call sequence updatePTScene(scene, unified) -> commitObjectChanges()
     // reaches the GPU refit once the application has said  scene.setDynamicGeometryPolicy(...)  after building it.
+    // Every entry point that edits geometry on the device -- this commit, refit* / rebuild* / updateTriangles below -- hands a
+    // description of the edit to ONE route (editOnDevice), and what the device holds of a mesh, with whether the host copy of
+    // its tree is current, is ONE record (Resident); DESIGN.md 3.4 has the table.
     enum class DynamicGeometryPolicy { HostRebuild = 0, GpuRefit = 1, GpuRebuild = 2, GpuRefitAll = 3 };
     void setDynamicGeometryPolicy(DynamicGeometryPolicy p) {
-        // (chosen after the upload: the face lists of the meshes nobody has touched since are what the device holds)
-        if (p != DynamicGeometryPolicy::HostRebuild && gpu_resources_initialized && !geometryDirty && uploadedFaces.size() == meshes.size())
-            for (size_t i = 0; i < meshes.size(); ++i)
-                if (uploadedFaces[i].empty() && !meshes[i]->bvhDirty && !meshes[i]->vertsDirty)
-                    uploadedFaces[i] = meshes[i]->faces;
         dynPolicy = p;
+        // (chosen after the upload: the face lists of the meshes nobody has touched since are what the device holds)
+        if (p != DynamicGeometryPolicy::HostRebuild && gpu_resources_initialized && !geometryDirty && resident.size() == meshes.size())
+            for (size_t i = 0; i < meshes.size(); ++i)
+                if (resident[i].faces.empty() && !meshes[i]->bvhDirty && !meshes[i]->vertsDirty)
+                    recordResident(i);
     }
     DynamicGeometryPolicy getDynamicGeometryPolicy() const { return dynPolicy; }
     // commits that took the GPU path / that re-uploaded the geometry (tests, bench)
@@ -557,20 +560,8 @@ class Scene {
     // on the host copy (so flatten() stays consistent) and on the GPU (ptrt_update_vertices +
     // ptrt_refit, no re-upload of the arena).  Not in the reference.
     void refitObjectChanges() {
-        needBackend();
-        if (!gpu_resources_initialized || geometryDirty)
-            throw std::runtime_error("refitObjectChanges: call uploadToGPU() first (topology must already be on the GPU)");
-        for (size_t i = 0; i < meshes.size(); ++i) {
-            Mesh *m = meshes[i].get();
-            if (!m->vertsDirty)
-                continue;
-            m->refitBVH();
-            m->vertsDirty = false;
-            check(ptrt_update_vertices(ctx, (int)i, &m->vertices[0].x, (int)m->vertices.size(), 0),
-                  "Failed to update vertices");
-        }
-        check(ptrt_refit(ctx), "Failed to refit");
-        syncTLAS();
+        requireUploaded("refitObjectChanges");
+        editOnDevice(takeVertsDirty(), Trees::Refit, HostTrees::FollowNow, Tlas::RebuiltOnHost);
         resetAccumulation();
     }
     // TLAS over the meshes' new boxes: the host copy always; the device copy too when the TLAS has inner nodes
@@ -578,39 +569,22 @@ class Scene {
     // rebuilds it as the reference's commit does)
     void syncTLAS() {
         buildTLAS();
-        hostTlasStale = hostTlasOrderStale = false;
-        flat.tlas_nodes = h_tlasNodes.data();
-        flat.tlas_node_count = (int)h_tlasNodes.size();
-        flat.tlas_mesh_indices = h_tlasMeshIndices.data();
-        flat.tlas_index_count = (int)h_tlasMeshIndices.size();
+        hostTlas = HostTlas::Current;
+        pointFlatAtTLAS();
         if (h_tlasNodes.size() > 1)
-            check(ptrt_update_instances(ctx, flat.meshes, flat.mesh_count, flat.tlas_nodes, flat.tlas_node_count,
-                                        flat.tlas_mesh_indices, flat.tlas_index_count),
-                  "Failed to update the TLAS");
+            sendInstances("Failed to update the TLAS");
     }
     // same, the new positions already being in device memory (no host copy is kept: flatten()
     // then describes the LAST host-side vertices)
     void refitFromDevice(size_t mesh, const float *device_xyz) {
-        needBackend();
-        Mesh *m = getMesh(mesh);
-        if (!m)
-            throw std::runtime_error("refitFromDevice: no such mesh");
-        check(ptrt_update_vertices(ctx, (int)mesh, device_xyz, (int)m->vertices.size(), 1), "Failed to update vertices");
-        check(ptrt_refit(ctx), "Failed to refit");
-        refitDeviceTLAS();
+        editOnDevice({vertexEdit("refitFromDevice", mesh, device_xyz, true)}, Trees::Refit, HostTrees::LeftBehind, Tlas::RefittedOnDevice);
         resetAccumulation();
     }
 
     // same from HOST memory without touching the host copy of the mesh (its vertices are whatever the caller last put
-    // there; the host tree is refitted when something reads it): ptrt_update_vertices(on_device = 0) + ptrt_refit
+    // there, and so is its tree): ptrt_update_vertices(on_device = 0) + ptrt_refit
     void refitFromHost(size_t mesh, const float *host_xyz) {
-        needBackend();
-        Mesh *m = getMesh(mesh);
-        if (!m)
-            throw std::runtime_error("refitFromHost: no such mesh");
-        check(ptrt_update_vertices(ctx, (int)mesh, host_xyz, (int)m->vertices.size(), 0), "Failed to update vertices");
-        check(ptrt_refit(ctx), "Failed to refit");
-        refitDeviceTLAS();
+        editOnDevice({vertexEdit("refitFromHost", mesh, host_xyz, false)}, Trees::Refit, HostTrees::LeftBehind, Tlas::RefittedOnDevice);
         resetAccumulation();
     }
 
@@ -618,64 +592,26 @@ class Scene {
     // (ptrt_build_bvh: Morton-order median split over the uploaded tree shape + refit) instead of
     // Mesh::buildBVH on the CPU + re-upload (scene.cuh:656-733).  The host copy of each rebuilt tree
     // follows (prim order read back, boxes refitted) so flatten() describes what the GPU traverses.
+    // Without `syncHostCopy`, behind a TLAS with inner nodes the host copy follows lazily, as under the GpuRebuild policy: left
+    // dirty, the mesh would be rebuilt on the host and everything uploaded again by the next frame, a second topology.
     void rebuildObjectChanges(bool syncHostCopy = true) {
-        needBackend();
-        if (!gpu_resources_initialized || geometryDirty)
-            throw std::runtime_error("rebuildObjectChanges: call uploadToGPU() first");
-        for (size_t i = 0; i < meshes.size(); ++i) {
-            Mesh *m = meshes[i].get();
-            if (!m->vertsDirty)
-                continue;
-            m->vertsDirty = false;
-            check(ptrt_update_vertices(ctx, (int)i, &m->vertices[0].x, (int)m->vertices.size(), 0),
-                  "Failed to update vertices");
-            check(ptrt_build_bvh(ctx, (int)i), "Failed to build BVH");
-            if (syncHostCopy)
-                syncPrimOrder(i);
-            else if (h_tlasNodes.size() > 1 && i < hostTreeStale.size()) {
-                // behind a TLAS with inner nodes the host copy follows lazily, as under the GpuRebuild policy: left dirty, the
-                // mesh would be rebuilt on the host and everything uploaded again by the next frame, a second topology
-                hostTreeStale[i] = 2;
-                m->bvhDirty = false;
-            }
-        }
-        if (syncHostCopy)
-            syncTLAS();
-        else
-            refitDeviceTLAS();
+        requireUploaded("rebuildObjectChanges");
+        editOnDevice(takeVertsDirty(), Trees::Rebuild, syncHostCopy ? HostTrees::FollowNow : HostTrees::MarkedBehindInnerNodes,
+                     syncHostCopy ? Tlas::RebuiltOnHost : Tlas::RefittedOnDevice);
         resetAccumulation();
     }
     // same, new positions already in device memory (host copy not updated)
     void rebuildFromDevice(size_t mesh, const float *device_xyz) {
-        needBackend();
-        Mesh *m = getMesh(mesh);
-        if (!m)
-            throw std::runtime_error("rebuildFromDevice: no such mesh");
-        check(ptrt_update_vertices(ctx, (int)mesh, device_xyz, (int)m->vertices.size(), 1), "Failed to update vertices");
-        check(ptrt_build_bvh(ctx, (int)mesh), "Failed to build BVH");
-        refitDeviceTLAS();
+        editOnDevice({vertexEdit("rebuildFromDevice", mesh, device_xyz, true)}, Trees::Rebuild, HostTrees::LeftBehind, Tlas::RefittedOnDevice);
         resetAccumulation();
     }
     // updatePTScene's `Triangles` path (PTRTtransfer.cuh:2204-2385) for a soup mesh made by
     // addTriangles with room for its original triangle count: `tri_count` new triangles (9 floats
     // each) from host or device memory, BVH rebuilt on the GPU.  The host copy of the mesh gets the
-    // same padded vertices when the data is on the host.
+    // same padded vertices when the data is on the host; from device memory neither it nor any TLAS follows.
     void updateTriangles(size_t mesh, const float *verts9, int tri_count, bool on_device = false) {
-        needBackend();
-        Mesh *m = getMesh(mesh);
-        if (!m)
-            throw std::runtime_error("updateTriangles: no such mesh");
-        check(ptrt_update_triangles(ctx, (int)mesh, verts9, tri_count, on_device ? 1 : 0), "Failed to update triangles");
-        check(ptrt_build_bvh(ctx, (int)mesh), "Failed to build BVH");
-        if (!on_device) {
-            const size_t real = (size_t)tri_count * 3;
-            for (size_t v = 0; v < m->vertices.size(); ++v) {
-                const size_t s = v < real ? v : (real ? real - 1 : 0);
-                m->vertices[v] = real ? vec3(verts9[s * 3], verts9[s * 3 + 1], verts9[s * 3 + 2]) : vec3(0.0f);
-            }
-            syncPrimOrder(mesh);
-            syncTLAS();
-        }
+        editOnDevice({vertexEdit("updateTriangles", mesh, verts9, on_device, tri_count)}, Trees::Rebuild,
+                     on_device ? HostTrees::LeftBehind : HostTrees::FollowNow, on_device ? Tlas::Untouched : Tlas::RebuiltOnHost);
         resetAccumulation();
     }
     // Instances moved, nothing else changed, and the TLAS keeps the topology it was uploaded with (not in the reference, whose
@@ -684,9 +620,7 @@ class Scene {
     // of consecutive meshes -- and ptrt_refit_tlas refits the TLAS there; nothing waits for the stream.  The host TLAS is
     // refitted over the same topology (refitTLAS), so flatten() describes what the GPU traverses.
     void refitInstanceChanges() {
-        needBackend();
-        if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
-            throw std::runtime_error("refitInstanceChanges: call uploadToGPU() first (the TLAS topology must already be on the GPU)");
+        requireUploaded("refitInstanceChanges");
         refitMovedInstances();
         resetAccumulation();
     }
@@ -695,94 +629,49 @@ class Scene {
     // synchronisation.  The host TLAS follows through the same arithmetic (reorderTLASOnHost's), so flatten() describes what
     // the GPU traverses; where host root boxes lag the device's it follows by read-back when something reads it.
     void reorderTLAS() {
-        needBackend();
-        if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
-            throw std::runtime_error("reorderTLAS: call uploadToGPU() first (the TLAS topology must already be on the GPU)");
+        requireUploaded("reorderTLAS");
         refitMovedInstances(true);
         resetAccumulation();
     }
     // (the work of refitInstanceChanges and reorderTLAS; a commit under GpuRefitAll comes here as well)
     void refitMovedInstances(bool reorder = false) {
-        std::vector<ptrt_instance_xform> run;
-        int first = 0;
-        auto flush = [&] {
-            if (!run.empty())
-                check(ptrt_set_instance_transforms(ctx, first, (int)run.size(), run.data()), "Failed to set instance transforms");
-            run.clear();
-        };
-        for (size_t i = 0; i < meshes.size(); ++i) {
-            if (!takeInstanceMove(i)) {
-                flush();
-                continue;
+        std::vector<ptrt_instance_xform> run; // (consecutive moved meshes [i - run.size(), i) awaiting one call)
+        for (size_t i = 0; i <= meshes.size(); ++i) {
+            if (i < meshes.size() && takeInstanceMove(i)) {
+                run.emplace_back();
+                writeInstance(run.back(), meshes[i]->transform);
+            } else if (!run.empty()) {
+                check(ptrt_set_instance_transforms(ctx, (int)(i - run.size()), (int)run.size(), run.data()), "Failed to set instance transforms");
+                run.clear();
             }
-            if (run.empty())
-                first = (int)i;
-            const ptrt_mesh_desc &d = flatMeshes[i];
-            ptrt_instance_xform x;
-            std::memcpy(x.world, d.world, sizeof x.world);
-            std::memcpy(x.inverse, d.inverse, sizeof x.inverse);
-            std::memcpy(x.normal, d.normal, sizeof x.normal);
-            x.has_transform = d.has_transform;
-            run.push_back(x);
         }
-        flush();
         if (reorder)
             check(ptrt_reorder_tlas(ctx), "Failed to re-order the TLAS");
         else
             check(ptrt_refit_tlas(ctx), "Failed to refit the TLAS");
-        bool roots_lag = hostTlasStale; // (host root boxes that lag the device's: the host TLAS follows by read-back, lazily)
-        for (unsigned char st : hostTreeStale)
-            roots_lag = roots_lag || st != 0;
-        if (roots_lag) {
-            hostTlasStale = true;
-            hostTlasOrderStale = hostTlasOrderStale || (reorder && h_tlasNodes.size() > 1);
-        } else {
-            const std::vector<AABB> world = meshWorldBoxes();
-            if (reorder)
-                mortonOrderTLAS(world);
-            refitTLASNode(0, world, 0);
-        }
+        bool roots_lag = hostTlas != HostTlas::Current; // (host root boxes that lag the device's: the host TLAS follows by read-back, lazily)
+        for (const Resident &r : resident)
+            roots_lag = roots_lag || r.hostTree != HostTree::Current;
+        if (roots_lag)
+            markHostTlas(reorder && h_tlasNodes.size() > 1 ? HostTlas::OrderStale : HostTlas::BoxesStale);
+        else
+            refitHostTLAS(reorder);
     }
     // the host half alone, for a Scene without a back end (tests, tools that only flatten())
-    void refitInstanceChangesOnHost() {
-        if (geometryDirty && ctx)
-            throw std::runtime_error("refitInstanceChangesOnHost: geometry is dirty");
-        if (flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
-            prepareHostStructures();
-        for (size_t i = 0; i < meshes.size(); ++i)
-            takeInstanceMove(i);
-        refitTLAS();
-        resetAccumulation();
-    }
+    void refitInstanceChangesOnHost() { moveInstancesOnHost("refitInstanceChangesOnHost", false); }
     // Host twin of ptrt_reorder_tlas, for a Scene without a back end as well: h_tlasMeshIndices in Morton order of the meshes'
     // world-box centres (mortonOrderTLAS), then refitTLAS() over the kept topology.
-    void reorderTLASOnHost() {
-        if (geometryDirty && ctx)
-            throw std::runtime_error("reorderTLASOnHost: geometry is dirty");
-        if (flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
-            prepareHostStructures();
-        for (size_t i = 0; i < meshes.size(); ++i)
-            takeInstanceMove(i);
-        const std::vector<AABB> world = meshWorldBoxes();
-        mortonOrderTLAS(world);
-        refitTLASNode(0, world, 0);
-        resetAccumulation();
-    }
+    void reorderTLASOnHost() { moveInstancesOnHost("reorderTLASOnHost", true); }
     // Host twin of ptrt_refit_tlas: the boxes of h_tlasNodes over the topology they have -- every mesh's world box from its
     // root box through Transform3D::transformAABB (as buildTLAS takes it), every leaf the union of its members, every inner
     // node the union of its children.  min / max are exact: the device's refit gives the same bits.
-    void refitTLAS() { refitTLASNode(0, meshWorldBoxes(), 0); }
+    void refitTLAS() { refitHostTLAS(false); }
     std::vector<AABB> meshWorldBoxes() const {
         if (h_tlasNodes.empty())
             throw std::runtime_error("refitTLAS: no TLAS built yet");
         std::vector<AABB> world(meshes.size());
-        for (size_t i = 0; i < meshes.size(); ++i) {
-            const Mesh *m = meshes[i].get();
-            if (m->bvhNodes.empty())
-                throw std::runtime_error("Mesh BVH not built before TLAS");
-            const DeviceBVHNode &root = m->bvhNodes[0];
-            world[i] = m->transform.transformAABB(AABB{vec3(root.bmin.x, root.bmin.y, root.bmin.z), vec3(root.bmax.x, root.bmax.y, root.bmax.z)});
-        }
+        for (size_t i = 0; i < meshes.size(); ++i)
+            world[i] = meshWorldBox(i);
         return world;
     }
     // pt::reorder_tlas_kernel on the host (morton30 / spread10 of csrc/pt_build.hip.h restated: change both or neither), operation by operation (-ffp-contract=off on both sides): mesh i's key is the
@@ -837,32 +726,23 @@ class Scene {
     // current boxes and handed to the device with the matrices (ptrt_update_instances; synchronises) -- for a caller that wants a
     // fresh topology, say once the refitted one has cost a few per cent of frame time.
     void reseatTLAS() {
-        needBackend();
-        if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size())
-            throw std::runtime_error("reseatTLAS: call uploadToGPU() first");
-        hostTlasStale = hostTlasOrderStale = false; // (rebuilt below; only the meshes' own trees have to follow the device first)
+        requireUploaded("reseatTLAS");
+        hostTlas = HostTlas::Current; // (rebuilt below; only the meshes' own trees have to follow the device first)
         syncHostTrees();
         for (size_t i = 0; i < meshes.size(); ++i)
             takeInstanceMove(i);
         buildTLAS();
-        flat.tlas_nodes = h_tlasNodes.data();
-        flat.tlas_node_count = (int)h_tlasNodes.size();
-        flat.tlas_mesh_indices = h_tlasMeshIndices.data();
-        flat.tlas_index_count = (int)h_tlasMeshIndices.size();
-        check(ptrt_update_instances(ctx, flat.meshes, flat.mesh_count, flat.tlas_nodes, flat.tlas_node_count, flat.tlas_mesh_indices,
-                                    flat.tlas_index_count),
-              "Failed to update the TLAS");
+        pointFlatAtTLAS();
+        sendInstances("Failed to update the TLAS");
         instancesDirty = false;
         resetAccumulation();
     }
     // host copy of mesh `i`'s tree := what the GPU now traverses
     void syncPrimOrder(size_t i) {
-        Mesh *m = getMesh(i);
-        if (!m)
+        if (!getMesh(i))
             throw std::runtime_error("syncPrimOrder: no such mesh");
-        check(ptrt_read_prim_order(ctx, (int)i, m->bvhPrimIndices.data(), (int)m->bvhPrimIndices.size()),
-              "Failed to read the prim order");
-        m->refitBVH();
+        readPrimOrder(i);
+        meshes[i]->refitBVH();
     }
 
     bool hasObjectChanges() const {
@@ -1214,15 +1094,32 @@ class Scene {
             clearcoatRoughness, subsurfaceRadius, anisotropy, sheen, iridescence, iridescenceThickness;
     } soa;
     ptrt_scene_desc flat{};
-    // dynamic-geometry policy: the face lists and vertex counts of the last upload, and which host trees lag the device's
+    // What the device holds of one mesh since the last ptrt_upload_geometry, and whether the host copy of its tree still equals
+    // the device's: BoxesStale -- the device refitted it (Mesh::refitBVH brings the host copy up); OrderStale -- the device
+    // rebuilt it (the prim order is read back first).  A mark only grows until syncHostTrees() consumes it: an order read-back
+    // stays pending across later refits.
+    enum class HostTree : unsigned char { Current, BoxesStale, OrderStale };
+    struct Resident {
+        size_t verts = 0, faceCount = 0;
+        std::vector<Tri> faces; // kept under a non-default policy only (HostRebuild pays nothing for the copy)
+        bool soup = false;      // `faces` is the unshared-vertex pattern {3k, 3k+1, 3k+2} (sameFaces)
+        HostTree hostTree = HostTree::Current;
+        void mark(HostTree t) { hostTree = t > hostTree ? t : hostTree; }
+    };
+    std::vector<Resident> resident;
+    // the same for the TLAS: the device refitted it (ptrt_refit_tlas) over root boxes the host has not followed yet, or
+    // re-ordered it as well (ptrt_reorder_tlas: the index array is read back with the boxes)
+    enum class HostTlas : unsigned char { Current, BoxesStale, OrderStale };
+    HostTlas hostTlas = HostTlas::Current;
+    void markHostTlas(HostTlas t) { hostTlas = t > hostTlas ? t : hostTlas; }
     DynamicGeometryPolicy dynPolicy = DynamicGeometryPolicy::HostRebuild;
-    std::vector<std::vector<Tri>> uploadedFaces;
-    std::vector<size_t> uploadedVerts;
-    std::vector<unsigned char> hostTreeStale, uploadedSoup;
-    bool hostTlasStale = false; // the device refitted its TLAS (ptrt_refit_tlas) over root boxes the host has not followed yet
-    bool hostTlasOrderStale = false; // ... and re-ordered it (ptrt_reorder_tlas): the index array is read back with the boxes
     size_t gpuDynamicCommits = 0, geometryUploads = 0;
     double commitMicros = 0.0, compareMicros = 0.0;
+    struct Timer { // adds its lifetime, in microseconds, to `acc`
+        double &acc;
+        std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+        ~Timer() { acc += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+    };
 
     void needBackend() const {
         if (!ctx)
@@ -1245,24 +1142,77 @@ class Scene {
         resetAccumulation();
     }
 
-    // mesh i's instance transform changed since its descriptor was written: matrices, descriptor and lastWorld brought up to
-    // date as prepareHostStructures does for a moved instance; false if nothing changed
-    bool takeInstanceMove(size_t i) {
-        Mesh *m = meshes[i].get();
-        if (m->transform.dirty)
-            m->transform.updateMatrices();
-        else if (std::memcmp(&lastWorld[i], &m->transform.worldMatrix, sizeof(mat4)) == 0)
-            return false;
-        lastWorld[i] = m->transform.worldMatrix;
-        ptrt_mesh_desc &d = flatMeshes[i];
-        std::memcpy(d.world, m->transform.worldMatrix.m, sizeof d.world);
-        std::memcpy(d.inverse, m->transform.inverseMatrix.m, sizeof d.inverse);
-        std::memcpy(d.normal, m->transform.normalMatrix.m, sizeof d.normal);
-        d.has_transform = (m->transform.position.length() > 0.001f || m->transform.rotation.length() > 0.001f ||
-                           fabsf(m->transform.scale.x - 1.0f) > 0.001f)
+    // ---- small pieces every route below shares ----
+    // (one form for every caller: after an upload without geometryDirty the descriptors are sized and the TLAS exists, so the two
+    // extra conditions refitInstanceChanges / reorderTLAS used to name alone refuse nothing the others accepted)
+    void requireUploaded(const char *who) const {
+        needBackend();
+        if (!gpu_resources_initialized || geometryDirty || flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
+            throw std::runtime_error(std::string(who) + ": call uploadToGPU() first (the geometry and the TLAS topology must already be on the GPU)");
+    }
+    // the matrices and the has_transform rule of a descriptor (ptrt_mesh_desc) or of an instance record (ptrt_instance_xform)
+    template <class Desc> static void writeInstance(Desc &d, const Transform3D &t) {
+        std::memcpy(d.world, t.worldMatrix.m, sizeof d.world);
+        std::memcpy(d.inverse, t.inverseMatrix.m, sizeof d.inverse);
+        std::memcpy(d.normal, t.normalMatrix.m, sizeof d.normal);
+        d.has_transform = (t.position.length() > 0.001f || t.rotation.length() > 0.001f || fabsf(t.scale.x - 1.0f) > 0.001f)
                               ? 1
-                              : 0; // scene.cuh:718-721
+                              : 0; // scene.cuh:718-721 (only scale.x is inspected)
+    }
+    // mesh i's instance transform is not the one its descriptor was last written from
+    bool instanceMoved(size_t i) const {
+        const Transform3D &t = meshes[i]->transform;
+        return t.dirty || std::memcmp(&lastWorld[i], &t.worldMatrix, sizeof(mat4)) != 0;
+    }
+    // ... then matrices, descriptor and lastWorld are brought up to date, as prepareHostStructures does; false if nothing changed
+    bool takeInstanceMove(size_t i) {
+        if (!instanceMoved(i))
+            return false;
+        Transform3D &t = meshes[i]->transform;
+        t.updateMatrices();
+        lastWorld[i] = t.worldMatrix;
+        writeInstance(flatMeshes[i], t);
         return true;
+    }
+    // mesh i's world box as every TLAS takes it: its root node's box through Transform3D::transformAABB
+    AABB meshWorldBox(size_t i) const {
+        const Mesh *m = meshes[i].get();
+        if (m->bvhNodes.empty())
+            throw std::runtime_error("Mesh BVH not built before TLAS");
+        const DeviceBVHNode &root = m->bvhNodes[0];
+        return m->transform.transformAABB(AABB{vec3(root.bmin.x, root.bmin.y, root.bmin.z), vec3(root.bmax.x, root.bmax.y, root.bmax.z)});
+    }
+    void pointFlatAtTLAS() {
+        flat.tlas_nodes = h_tlasNodes.data();
+        flat.tlas_node_count = (int)h_tlasNodes.size();
+        flat.tlas_mesh_indices = h_tlasMeshIndices.data();
+        flat.tlas_index_count = (int)h_tlasMeshIndices.size();
+    }
+    void sendInstances(const char *what) { // every descriptor's matrices and the host's TLAS (synchronises)
+        check(ptrt_update_instances(ctx, flat.meshes, flat.mesh_count, flat.tlas_nodes, flat.tlas_node_count, flat.tlas_mesh_indices,
+                                    flat.tlas_index_count),
+              what);
+    }
+    void readPrimOrder(size_t i) { // (synchronises)
+        Mesh *m = meshes[i].get();
+        check(ptrt_read_prim_order(ctx, (int)i, m->bvhPrimIndices.data(), (int)m->bvhPrimIndices.size()), "Failed to read the prim order");
+    }
+    // the host TLAS over the topology it has, optionally re-ordered first as ptrt_reorder_tlas re-orders the device's
+    void refitHostTLAS(bool reorder) {
+        const std::vector<AABB> world = meshWorldBoxes();
+        if (reorder)
+            mortonOrderTLAS(world);
+        refitTLASNode(0, world, 0);
+    }
+    void moveInstancesOnHost(const char *who, bool reorder) {
+        if (geometryDirty && ctx)
+            throw std::runtime_error(std::string(who) + ": geometry is dirty");
+        if (flatMeshes.size() != meshes.size() || h_tlasNodes.empty())
+            prepareHostStructures();
+        for (size_t i = 0; i < meshes.size(); ++i)
+            takeInstanceMove(i);
+        refitHostTLAS(reorder);
+        resetAccumulation();
     }
     AABB refitTLASNode(int n, const std::vector<AABB> &world, int depth) {
         if (n < 0 || n >= (int)h_tlasNodes.size() || depth > 64)
@@ -1282,28 +1232,13 @@ class Scene {
         N.bmax = {b.bmax.x, b.bmax.y, b.bmax.z};
         return b;
     }
-    // behind a TLAS with inner nodes the root boxes a GPU refit / rebuild moved reach the TLAS by a refit on the device; the
-    // host copy follows when something reads it (syncHostTrees).  A single-leaf TLAS got its box from ptrt_refit itself.
-    void refitDeviceTLAS() {
-        if (h_tlasNodes.size() <= 1)
-            return;
-        check(ptrt_refit_tlas(ctx), "Failed to refit the TLAS");
-        hostTlasStale = true;
-    }
-
     // TLAS over the meshes' world AABBs, same builder and leaf limit as the BLAS
     // (scene.cuh:458-594)
     void buildTLAS() {
         std::vector<ptrt_detail::BuildRef> refs(meshes.size());
         for (size_t i = 0; i < meshes.size(); ++i) {
-            Mesh *m = meshes[i].get();
-            if (m->transform.dirty)
-                m->transform.updateMatrices();
-            if (m->bvhNodes.empty())
-                throw std::runtime_error("Mesh BVH not built before TLAS");
-            const DeviceBVHNode &root = m->bvhNodes[0];
-            AABB local{vec3(root.bmin.x, root.bmin.y, root.bmin.z), vec3(root.bmax.x, root.bmax.y, root.bmax.z)};
-            AABB world = m->transform.transformAABB(local);
+            meshes[i]->transform.updateMatrices();
+            const AABB world = meshWorldBox(i);
             refs[i].id = (int)i;
             refs[i].b = world;
             refs[i].c = world.center();
@@ -1325,11 +1260,10 @@ class Scene {
         if (meshes.empty())
             return;
         // (a TLAS the DEVICE refitted needs no host trees until something reads or moves them)
-        bool need_trees = forRead || geometryDirty || flatMeshes.size() != meshes.size() || (h_tlasNodes.size() != 1 && !hostTlasStale);
+        bool need_trees = forRead || geometryDirty || flatMeshes.size() != meshes.size() || (h_tlasNodes.size() != 1 && hostTlas == HostTlas::Current);
         for (size_t i = 0; i < meshes.size() && !need_trees; ++i) {
             const Mesh *m = meshes[i].get();
-            need_trees = m->vertsDirty || m->bvhDirty || m->bvhNodes.empty() || m->transform.dirty ||
-                         std::memcmp(&lastWorld[i], &m->transform.worldMatrix, sizeof(mat4)) != 0;
+            need_trees = m->vertsDirty || m->bvhDirty || m->bvhNodes.empty() || instanceMoved(i);
         }
         const bool synced = need_trees && syncHostTrees(); // (trees the GPU refitted / rebuilt since the host last looked)
         // (refitted trees move the box of a single-leaf TLAS; one with inner nodes was refitted on the device and read back)
@@ -1352,15 +1286,11 @@ class Scene {
                 tlas_dirty = true;
                 geometryDirty = true;
             }
-            bool moved = m->transform.dirty;
-            if (moved)
-                m->transform.updateMatrices();
-            else
-                moved = std::memcmp(&lastWorld[i], &m->transform.worldMatrix, sizeof(mat4)) != 0;
-            if (moved) { // an instance moved: new matrices + TLAS, the triangles stay (ptrt_update_instances)
+            if (instanceMoved(i)) { // an instance moved: new matrices + TLAS, the triangles stay (ptrt_update_instances)
                 tlas_dirty = true;
                 instancesDirty = true;
             }
+            m->transform.updateMatrices();
             lastWorld[i] = m->transform.worldMatrix;
             ptrt_mesh_desc &d = flatMeshes[i];
             d.verts = reinterpret_cast<const ptrt_vec3 *>(m->vertices.data());
@@ -1371,13 +1301,7 @@ class Scene {
             d.node_count = (int)m->bvhNodes.size();
             d.prim_indices = m->bvhPrimIndices.data();
             d.prim_count = (int)m->bvhPrimIndices.size();
-            std::memcpy(d.world, m->transform.worldMatrix.m, sizeof d.world);
-            std::memcpy(d.inverse, m->transform.inverseMatrix.m, sizeof d.inverse);
-            std::memcpy(d.normal, m->transform.normalMatrix.m, sizeof d.normal);
-            d.has_transform = (m->transform.position.length() > 0.001f || m->transform.rotation.length() > 0.001f ||
-                               fabsf(m->transform.scale.x - 1.0f) > 0.001f)
-                                  ? 1
-                                  : 0; // scene.cuh:718-721 (only scale.x is inspected)
+            writeInstance(d, m->transform);
         }
         if (tlas_dirty)
             buildTLAS();
@@ -1408,10 +1332,7 @@ class Scene {
         }
         flat.meshes = flatMeshes.data();
         flat.mesh_count = (int)flatMeshes.size();
-        flat.tlas_nodes = h_tlasNodes.data();
-        flat.tlas_node_count = (int)h_tlasNodes.size();
-        flat.tlas_mesh_indices = h_tlasMeshIndices.data();
-        flat.tlas_index_count = (int)h_tlasMeshIndices.size();
+        pointFlatAtTLAS();
         flat.materials = ptrt_materials{soa.albedo.data(), soa.specular.data(), soa.metallic.data(),
                                         soa.roughness.data(), soa.emission.data(), soa.ior.data(),
                                         soa.transmission.data(), soa.transmissionRoughness.data(),
@@ -1430,66 +1351,128 @@ class Scene {
         flat.env_height = env_height;
     }
 
+    // ---- the one route of a device-side geometry edit ----
+    // An edit: new positions for mesh `mesh` from host or device memory -- all `count` vertices (ptrt_update_vertices), or
+    // `count` triangles of a soup with room for more (ptrt_update_triangles).
+    struct VertexEdit {
+        size_t mesh;
+        const float *data;
+        int count;
+        bool onDevice, triangles;
+    };
+    enum class Trees { Refit, Rebuild }; // one ptrt_refit over every mesh, or ptrt_build_bvh per edited mesh
+    // The host copy of an edited tree: brought up at once (a rebuild's prim order read back, boxes refitted); marked in its
+    // Resident record for syncHostTrees() and the mesh's dirty flags taken -- always, or only behind a TLAS with inner nodes
+    // (else the mesh stays dirty for the next commit's host rebuild); or left behind: the caller keeps no host copy.
+    enum class HostTrees { FollowNow, Marked, MarkedBehindInnerNodes, LeftBehind };
+    // The TLAS over the moved root boxes: rebuilt on the host over its CURRENT trees and sent if it has inner nodes (syncTLAS;
+    // a single leaf got its box from ptrt_refit / ptrt_build_bvh); only if it has inner nodes, the marked trees synced first,
+    // a single leaf's host copy following lazily; refitted on the device if it has inner nodes, the host's marked stale; moved
+    // instances' matrices sent and refitted there; or left alone.
+    enum class Tlas { RebuiltOnHost, RebuiltBehindInnerNodes, RefittedOnDevice, RefittedOnDeviceWithMoves, Untouched };
+
+    VertexEdit hostVertices(size_t i) const { return {i, &meshes[i]->vertices[0].x, (int)meshes[i]->vertices.size(), false, false}; }
+    VertexEdit vertexEdit(const char *who, size_t mesh, const float *data, bool onDevice, int triangles = -1) const {
+        needBackend();
+        if (!getMesh(mesh))
+            throw std::runtime_error(std::string(who) + ": no such mesh");
+        return {mesh, data, triangles < 0 ? (int)meshes[mesh]->vertices.size() : triangles, onDevice, triangles >= 0};
+    }
+    // every mesh whose vertices the caller rewrote in place, as an edit from its host copy; the flag is taken
+    std::vector<VertexEdit> takeVertsDirty() {
+        std::vector<VertexEdit> edits;
+        for (size_t i = 0; i < meshes.size(); ++i)
+            if (meshes[i]->vertsDirty) {
+                meshes[i]->vertsDirty = false;
+                edits.push_back(hostVertices(i));
+            }
+        return edits;
+    }
+    void editOnDevice(const std::vector<VertexEdit> &edits, Trees trees, HostTrees host, Tlas tlas) {
+        for (const VertexEdit &e : edits) {
+            if (e.triangles)
+                check(ptrt_update_triangles(ctx, (int)e.mesh, e.data, e.count, e.onDevice ? 1 : 0), "Failed to update triangles");
+            else
+                check(ptrt_update_vertices(ctx, (int)e.mesh, e.data, e.count, e.onDevice ? 1 : 0), "Failed to update vertices");
+            if (trees == Trees::Rebuild)
+                check(ptrt_build_bvh(ctx, (int)e.mesh), "Failed to build BVH");
+            hostTreeFollows(e, trees, host);
+        }
+        if (trees == Trees::Refit)
+            check(ptrt_refit(ctx), "Failed to refit");
+        tlasFollows(tlas);
+    }
+    void hostTreeFollows(const VertexEdit &e, Trees trees, HostTrees how) {
+        Mesh *m = meshes[e.mesh].get();
+        if (how == HostTrees::FollowNow) {
+            for (size_t v = 0, real = (size_t)e.count * 3; e.triangles && v < m->vertices.size(); ++v) {
+                const size_t s = v < real ? v : (real ? real - 1 : 0); // (the padded vertices the device now holds)
+                m->vertices[v] = real ? vec3(e.data[s * 3], e.data[s * 3 + 1], e.data[s * 3 + 2]) : vec3(0.0f);
+            }
+            if (trees == Trees::Rebuild)
+                readPrimOrder(e.mesh);
+            m->refitBVH();
+        } else if (how == HostTrees::Marked || (how == HostTrees::MarkedBehindInnerNodes && h_tlasNodes.size() > 1)) {
+            resident[e.mesh].mark(trees == Trees::Rebuild ? HostTree::OrderStale : HostTree::BoxesStale);
+            m->bvhDirty = m->vertsDirty = false;
+            flatMeshes[e.mesh].verts = reinterpret_cast<const ptrt_vec3 *>(m->vertices.data()); // (the caller may have re-allocated them)
+            flatMeshes[e.mesh].faces = m->faces.data();
+        }
+    }
+    void tlasFollows(Tlas how) {
+        const bool inner = h_tlasNodes.size() > 1; // (the one place the TLAS's shape decides; hostTreeFollows has the trees')
+        if (how == Tlas::RebuiltBehindInnerNodes && inner)
+            syncHostTrees();
+        if (how == Tlas::RebuiltOnHost || (how == Tlas::RebuiltBehindInnerNodes && inner)) {
+            syncTLAS();
+        } else if (how == Tlas::RefittedOnDeviceWithMoves) {
+            refitMovedInstances();
+        } else if (how == Tlas::RefittedOnDevice && inner) {
+            check(ptrt_refit_tlas(ctx), "Failed to refit the TLAS");
+            markHostTlas(HostTlas::BoxesStale);
+        }
+    }
+
     // The dynamic-geometry policy (setDynamicGeometryPolicy): meshes whose vertices changed while their topology is what
     // the device holds keep their uploaded tree.  Returns false when the commit has to take the reference's route.
     bool commitOnGpu() {
         if (dynPolicy == DynamicGeometryPolicy::HostRebuild || !gpu_resources_initialized || geometryDirty ||
-            uploadedFaces.size() != meshes.size() || flatMeshes.size() != meshes.size())
+            resident.size() != meshes.size() || flatMeshes.size() != meshes.size())
             return false;
-        std::vector<size_t> moved;
+        std::vector<VertexEdit> edits;
         for (size_t i = 0; i < meshes.size(); ++i) {
             const Mesh *m = meshes[i].get();
             if (!m->bvhDirty && !m->vertsDirty)
                 continue;
-            const std::vector<Tri> &uf = uploadedFaces[i];
-            if (m->bvhNodes.empty() || m->vertices.size() != uploadedVerts[i] || m->faces.size() != uf.size())
+            if (m->bvhNodes.empty() || m->vertices.size() != resident[i].verts || m->faces.size() != resident[i].faces.size())
                 return false;
-            const auto c0 = std::chrono::steady_clock::now();
-            const bool same = sameFaces(*m, i);
-            compareMicros += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - c0).count();
-            if (!same)
+            if (!sameFaces(*m, resident[i]))
                 return false;
-            moved.push_back(i);
+            edits.push_back(hostVertices(i));
         }
         const bool all = dynPolicy == DynamicGeometryPolicy::GpuRefitAll;
         bool instances = false;
         for (size_t i = 0; all && i < meshes.size() && !instances; ++i)
-            instances = meshes[i]->transform.dirty || std::memcmp(&lastWorld[i], &meshes[i]->transform.worldMatrix, sizeof(mat4)) != 0;
-        if (moved.empty() && !instances)
+            instances = instanceMoved(i);
+        if (edits.empty() && !instances)
             return false;
-        const bool rebuild = dynPolicy == DynamicGeometryPolicy::GpuRebuild;
-        for (size_t i : moved) {
-            Mesh *m = meshes[i].get();
-            check(ptrt_update_vertices(ctx, (int)i, &m->vertices[0].x, (int)m->vertices.size(), 0), "Failed to update vertices");
-            if (rebuild)
-                check(ptrt_build_bvh(ctx, (int)i), "Failed to build BVH");
-            m->bvhDirty = m->vertsDirty = false;
-            // 1: boxes to refit on the host; 2: the prim order must be read back first (it stays pending across later refits)
-            hostTreeStale[i] = rebuild ? 2 : (hostTreeStale[i] == 2 ? 2 : 1);
-            flatMeshes[i].verts = reinterpret_cast<const ptrt_vec3 *>(m->vertices.data()); // (the caller may have re-allocated them)
-            flatMeshes[i].faces = m->faces.data();
-        }
-        if (!rebuild && !moved.empty())
-            check(ptrt_refit(ctx), "Failed to refit");
-        if (all) { // the TLAS is refitted on the device and rebuilt nowhere
-            if (instances)
-                refitMovedInstances();
-            else
-                refitDeviceTLAS();
-        } else if (h_tlasNodes.size() > 1) { // a real TLAS is rebuilt on the host over the new boxes, as the reference's commit does
-            syncHostTrees();
-            syncTLAS();
-        }
+        // under GpuRefitAll the TLAS is refitted on the device and rebuilt nowhere; else a real TLAS is rebuilt on the host over
+        // the new boxes, as the reference's commit does, and a single leaf needs nothing
+        const Tlas tlas = !all ? Tlas::RebuiltBehindInnerNodes : instances ? Tlas::RefittedOnDeviceWithMoves : Tlas::RefittedOnDevice;
+        if (edits.empty())
+            tlasFollows(tlas); // (instances alone moved: no vertices, no refit)
+        else
+            editOnDevice(edits, dynPolicy == DynamicGeometryPolicy::GpuRebuild ? Trees::Rebuild : Trees::Refit, HostTrees::Marked, tlas);
         ++gpuDynamicCommits;
         return true;
     }
-    // Is the face list of mesh i what the device holds?  A `Triangles` mesh as updatePTScene rewrites it (PTRTtransfer.cuh:2249-2270)
+    // Is the face list of mesh m what the device holds?  A `Triangles` mesh as updatePTScene rewrites it (PTRTtransfer.cuh:2249-2270)
     // is an unshared-vertex soup: face k = {3k, 3k+1, 3k+2}.  If the uploaded list was that soup (noted at upload), the new
     // list is checked against the PATTERN -- one pass over 12 bytes per face, no second array to stream -- else word by word
     // against the copy kept from the upload.
-    bool sameFaces(const Mesh &m, size_t i) const {
-        const std::vector<Tri> &uf = uploadedFaces[i];
-        if (i < uploadedSoup.size() && uploadedSoup[i]) {
+    bool sameFaces(const Mesh &m, const Resident &r) {
+        Timer timer{compareMicros};
+        if (r.soup) {
             const Tri *f = m.faces.data();
             const int n = (int)m.faces.size();
             int bad = 0;
@@ -1497,29 +1480,52 @@ class Scene {
                 bad |= (f[k].v0 ^ (3 * k)) | (f[k].v1 ^ (3 * k + 1)) | (f[k].v2 ^ (3 * k + 2));
             return bad == 0;
         }
-        return std::memcmp(m.faces.data(), uf.data(), uf.size() * sizeof(Tri)) == 0;
+        return std::memcmp(m.faces.data(), r.faces.data(), r.faces.size() * sizeof(Tri)) == 0;
     }
-    // host copies of the trees the GPU refitted (boxes) or rebuilt (prim order, then boxes); true if any changed
+    // what the device holds of mesh i := the host arrays as they stand -- after an upload, or for a mesh nobody has touched
+    // since when a policy is chosen later; the host-tree mark is not this function's
+    void recordResident(size_t i) {
+        const Mesh &m = *meshes[i];
+        Resident &r = resident[i];
+        r.verts = m.vertices.size();
+        r.faceCount = m.faces.size();
+        r.faces.clear();
+        r.soup = false;
+        if (dynPolicy == DynamicGeometryPolicy::HostRebuild)
+            return;
+        r.faces = m.faces;
+        r.soup = r.faces.size() * 3 == r.verts;
+        for (size_t k = 0; r.soup && k < r.faces.size(); ++k)
+            r.soup = r.faces[k].v0 == (int)(3 * k) && r.faces[k].v1 == (int)(3 * k + 1) && r.faces[k].v2 == (int)(3 * k + 2);
+    }
+    // host copies of the trees the GPU refitted (boxes) or rebuilt (prim order, then boxes); true if any changed.  A marked mesh
+    // whose arrays are no longer the size the device holds was resized by the caller since: its tree cannot describe them (a
+    // refit would index past their ends), so the mark is dropped and the mesh left dirty for the host rebuild of this commit.
     bool syncHostTrees() {
         bool any = false;
-        for (size_t i = 0; i < hostTreeStale.size() && i < meshes.size(); ++i) {
-            if (!hostTreeStale[i])
+        for (size_t i = 0; i < resident.size() && i < meshes.size(); ++i) {
+            Resident &r = resident[i];
+            const HostTree was = r.hostTree;
+            if (was == HostTree::Current)
                 continue;
+            r.hostTree = HostTree::Current;
             Mesh *m = meshes[i].get();
-            if (hostTreeStale[i] == 2 && ctx)
-                check(ptrt_read_prim_order(ctx, (int)i, m->bvhPrimIndices.data(), (int)m->bvhPrimIndices.size()),
-                      "Failed to read the prim order");
+            if (m->vertices.size() != r.verts || m->faces.size() != r.faceCount) {
+                m->bvhDirty = true;
+                continue;
+            }
+            if (was == HostTree::OrderStale && ctx)
+                readPrimOrder(i);
             const bool bd = m->bvhDirty; // (a caller's later edit stays pending)
             m->refitBVH();
             m->bvhDirty = bd;
-            hostTreeStale[i] = 0;
             any = true;
         }
-        if (hostTlasStale && ctx && !h_tlasNodes.empty()) { // the TLAS as the device refitted it (ptrt_read_tlas synchronises)
-            if (hostTlasOrderStale)
+        if (hostTlas != HostTlas::Current && ctx && !h_tlasNodes.empty()) { // the TLAS as the device refitted it (ptrt_read_tlas synchronises)
+            if (hostTlas == HostTlas::OrderStale)
                 check(ptrt_read_tlas_order(ctx, h_tlasMeshIndices.data(), (int)h_tlasMeshIndices.size()), "Failed to read the TLAS order");
             check(ptrt_read_tlas(ctx, h_tlasNodes.data(), (int)h_tlasNodes.size()), "Failed to read the TLAS");
-            hostTlasStale = hostTlasOrderStale = false;
+            hostTlas = HostTlas::Current;
         }
         return any;
     }
@@ -1527,11 +1533,7 @@ class Scene {
     void updateAccelerationStructures() {
         if (meshes.empty())
             return;
-        struct Timer {
-            double &acc;
-            std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-            ~Timer() { acc += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
-        } timer{commitMicros};
+        Timer timer{commitMicros};
         if (!ctx) { // host-only scene: the host half of a commit (trees, TLAS, material arrays); there is nothing to upload to
             prepareHostStructures();
             return;
@@ -1543,32 +1545,15 @@ class Scene {
                                        flat.tlas_mesh_indices, flat.tlas_index_count),
                   "Failed to upload geometry");
             geometryDirty = instancesDirty = false;
-            hostTlasStale = hostTlasOrderStale = false;
+            hostTlas = HostTlas::Current;
             ++geometryUploads;
-            // what the device now holds, for the dynamic-geometry policy
-            uploadedFaces.resize(meshes.size());
-            uploadedVerts.resize(meshes.size());
-            uploadedSoup.assign(meshes.size(), 0);
-            hostTreeStale.assign(meshes.size(), 0);
-            for (size_t i = 0; i < meshes.size(); ++i) {
-                uploadedVerts[i] = meshes[i]->vertices.size();
-                if (dynPolicy != DynamicGeometryPolicy::HostRebuild) {
-                    uploadedFaces[i] = meshes[i]->faces;
-                    const std::vector<Tri> &f = uploadedFaces[i];
-                    bool soup = f.size() * 3 == meshes[i]->vertices.size();
-                    for (size_t k = 0; soup && k < f.size(); ++k)
-                        soup = f[k].v0 == (int)(3 * k) && f[k].v1 == (int)(3 * k + 1) && f[k].v2 == (int)(3 * k + 2);
-                    uploadedSoup[i] = soup ? 1 : 0;
-                } else {
-                    uploadedFaces[i].clear(); // (the default policy pays nothing for the copies)
-                }
-            }
+            resident.assign(meshes.size(), Resident{}); // what the device now holds
+            for (size_t i = 0; i < meshes.size(); ++i)
+                recordResident(i);
         } else if (instancesDirty) {
-            check(ptrt_update_instances(ctx, flat.meshes, flat.mesh_count, flat.tlas_nodes, flat.tlas_node_count,
-                                        flat.tlas_mesh_indices, flat.tlas_index_count),
-                  "Failed to update instances");
+            sendInstances("Failed to update instances");
             instancesDirty = false;
-            hostTlasStale = hostTlasOrderStale = false;
+            hostTlas = HostTlas::Current;
         }
         if (materialsDirty) {
             check(ptrt_upload_materials(ctx, &flat.materials), "Failed to upload materials");

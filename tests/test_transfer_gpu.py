@@ -77,6 +77,48 @@ def test_update_pt_scene_then_commit_reaches_the_gpu_path(P, O, blue_noise, tmp_
     s.close()
 
 
+@pytest.mark.parametrize("cube_moves", [True, False])
+@pytest.mark.parametrize("policy", ["GpuRefit", "GpuRebuild"])
+def test_fewer_triangles_right_after_a_gpu_commit(P, O, blue_noise, policy, cube_moves):
+    """A commit on the GPU path, then at once -- no flatten(), read or frame in between -- a commit that rewrites the same
+    mesh with fewer triangles: the host tree the first commit left stale cannot describe the new arrays, so it is neither read
+    back nor refitted but rebuilt and uploaded, and the frame equals the oracle's.  `cube_moves`: the first step is
+    transfer_step, whose moved instance makes that commit sync the host trees itself; without it the mark is still pending
+    when the smaller mesh arrives (tests/test_host_commit_traces.py has the call sequence)."""
+    w, h = 96, 64
+    s = P.Scene(w, h, device=0)
+    water, cube = P.scenes.transfer_demo(s)
+    s.setDynamicGeometryPolicy(policy)
+    s.setPerfSamplesPerPixel(1)
+    s.setMaxBounceDepth(3)
+    s.setDenoiserEnabled(False)
+    s.setBloomEnabled(False)
+    s.initBlueNoise()
+    s.uploadToGPU()
+    rng = O.xorwow_init(P.DEFAULT_SEED, 0, w * h)
+
+    def frame():
+        fc = s.getFrameCount()
+        rgb = s.render_to_host()
+        c = O.render(s.flatten(), w, h, 1, 3, fc, blue_noise, rng, threads=4)
+        assert np.array_equal(bits(s.read(P.BUF_ACCUM)), bits(c["accum"]))
+        assert np.array_equal(O.tonemap(c["accum"], w, h).reshape(-1), rgb.reshape(-1))
+
+    frame()
+    if cube_moves:
+        P.scenes.transfer_step(s, water, cube, 1)
+    else:
+        s.setTriangleSoup(water, P.scenes.transfer_sheet(1))
+        s.commitObjectChanges()
+    assert s.commitCounts() == (1, 1)
+    s.setTriangleSoup(water, P.scenes.transfer_sheet(2)[:200])
+    s.commitObjectChanges()
+    assert s.commitCounts() == (1, 2)
+    frame()
+    assert s.commitCounts() == (1, 2)
+    s.close()
+
+
 def test_policy_falls_back_when_the_topology_changes(P, O, blue_noise):
     """A commit whose mesh has a different face count (or a new mesh) takes the reference's route whatever the policy, and the
     policy resumes on the next commit with the new topology."""
