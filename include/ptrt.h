@@ -178,6 +178,15 @@ typedef struct ptrt_irradiance {
     float reserved[2];      /* 0.0f                                                                         */
 } ptrt_irradiance;
 
+/* One lightmap texel's answer from ptrt_query_direct: the analytic lights' direct term over Q = light_count * n_shadow shadow
+ * samples, 32 bytes. */
+typedef struct ptrt_direct {
+    float irradiance[3];      /* sum over q of the unblocked samples' weights, divided by (float)n_shadow */
+    float lit_fraction;       /* samples walked and not blocked, divided by (float)Q                      */
+    float shadowed_fraction;  /* samples blocked, divided by (float)Q                                     */
+    float reserved[3];        /* 0.0f                                                                     */
+} ptrt_direct;
+
 /* Per-frame counters of the trace stage (Mrays/s numerator). */
 typedef struct ptrt_stats {
     uint64_t extension_rays; /* traceRay calls   (intersection.cuh:526) */
@@ -626,7 +635,7 @@ int ptrt_query_probes(ptrt_ctx *ctx, const float *d_positions, int n_probes, con
  * L(t,k), the first-hit depth and the object id of ray (t, k) are BY DEFINITION what ptrt_query_radiance puts into ptrt_radiance
  * for that ray and state with the same `samples` and `max_depth` -- the quirk that a caller's ray takes no light sample at its
  * first hit included.  So the direct term of the analytic lights (ptrt_upload_lights) at the texel itself and at a gather ray's
- * first hit is absent, as it is in a frame's first vertex; emissive meshes, the sky and the environment map are seen, and the
+ * first hit is absent, as it is in a frame's first vertex (ptrt_query_direct, below, bakes the term at the texel); emissive meshes, the sky and the environment map are seen, and the
  * lights do light every later vertex of a path.  Texel t's record holds MEANS over k:
  *     radiance[c]       L_c(t, k)                          (pi times it is the irradiance, for cosine-distributed directions)
  *     mean_distance     dist = min(depth, max_distance)    (a miss has depth 1e30f)
@@ -656,6 +665,64 @@ int ptrt_irradiance_rays(ptrt_ctx *ctx, const float *d_positions, const float *d
 int ptrt_query_irradiance(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n_texels,
                           const float *d_samples2, int n_dirs, const float *d_phases /* may be NULL */, float offset,
                           uint32_t *d_rng_states, int samples, int max_depth, float max_distance, ptrt_irradiance *d_out);
+
+/* Lightmap texels on DEVICE memory: the direct term of the analytic lights (ptrt_upload_lights) at the texel itself -- what the
+ * cosine gather above cannot see (ABI 6, addition only; no counterpart in the reference).  Texel t has P = positions[t] and
+ * N = normals[t] (n_texels*3 floats each; N is used as given and NOT normalised).  The lights are light_first ..
+ * light_first + light_count - 1 of the uploaded set (a caller bakes per-light layers with ranges), Q = light_count * n_shadow,
+ * and term q = j*n_shadow + s is shadow sample s of light light_first + j.  Every operation in float32 and separately rounded,
+ * in this order:
+ *     u1, u2      samples2[2s], samples2[2s+1] (`d_samples2`: ONE set of n_shadow points in [0,1)^2 for all texels and lights,
+ *                 used as given); with `d_phases` (n_texels floats; may be NULL) u2 becomes u2 + phases[t], minus 1.0f if that
+ *                 sum is >= 1.0f.  Only a local light with radius > 0 reads them.
+ *     L, pdf, radiance, att, light_dist
+ *                 the path tracer's own light sample (sample_direct_lighting_with_mat, path_logic.cuh:311-381) with
+ *                 hit.point = P, hit.normal = N, ONE light in the pick (pdf_pick = 1.0f: a sphere light's density is
+ *                 1 / solid_angle above the reference's 1e-6f threshold and 1.0f below it) and u1, u2 in place of the two
+ *                 draws of sample_cone_direction; attenuation, spot factor, the radius*radius / dist^2 clamp and
+ *                 light_dist = 1e30f for a directional light are the reference's
+ *     cos         dot(N, L)
+ *     weight[c]   ((radiance[c] * att) * cos) / pdf  if cos > 0.0f && pdf > 0.0f, else +0.0f.  No soft clamp: the reference's
+ *                 clamp of 500 belongs to the BSDF product, which has no part here
+ *     walked      weight.x > 0 || weight.y > 0 || weight.z > 0 (a NaN weight is not walked: the reference's idiom for a
+ *                 sample that adds nothing either way)
+ *     origin      P + offset*N, per component: the product, then the sum (offset = 1e-4f: the bits of the path tracer's own
+ *                 shadow origin)
+ *     tmax        light_dist - 1e-3f
+ *     blocked     walked && bvh_any_hit_tlas(origin, L, tmax): BY DEFINITION what ptrt_query_rays(PTRT_QUERY_OCCLUDED) answers
+ *                 for that ray; meshes with transmission > 0.5 do not block
+ *     term[c]     weight[c] if walked && !blocked, else +0.0f
+ * Texel t's record holds
+ *     irradiance[c]      sum over q of term[c], divided by (float)n_shadow: the sum over the lights of each light's mean
+ *     lit_fraction       sum over q of (walked && !blocked ? 1.0f : 0.0f), divided by (float)Q
+ *     shadowed_fraction  sum over q of (blocked ? 1.0f : 0.0f), divided by (float)Q
+ * and reserved is 0.0f.  Both fractions above zero: a penumbra, or a texel some lights reach; both zero: every sample faces
+ * away, lies outside a cone or has zero weight.  A light with a radius contributes radiance * solid angle (its density is
+ * 1 / solid_angle): the reference's model, not renormalised.  The sum order is ptrt_query_irradiance's with Q in place of
+ * n_dirs: w is the smallest power of two >= Q if Q <= 64, else 64; a chunk of w consecutive q, padded with +0.0f (selected,
+ * not computed), is folded by halves -- v[j] + v[j + w/2], then w/4, .. 1 --, chunk sums are added in chunk order to a total
+ * that starts at +0.0f, and one IEEE division ends each quantity.  tests/direct_restatement.py states it in numpy.
+ * light_count == 0 gives rows of all-zero bytes and PTRT_OK.
+ * ptrt_direct_rays writes, for ray t*Q + q, origin and L (3 floats each), tmax (1 float) and weight (3 floats) as above --
+ * for rays that are not walked too, as computed, NaN included -- with one small kernel on the context's stream (one thread
+ * per ray in blocks of 256, at most (2^31 - 1) * 256 rays per call).  It needs uploaded lights but no geometry.
+ * Ordering and side effects are those of ptrt_query_rays: enqueued on the context's stream with no allocation, copy or
+ * synchronisation, behind earlier frames, uploads (light uploads included), refits and instance updates; later frames are
+ * ordered behind it; neither call touches the context's generator states, frame buffers, ptrt_get_stats counters or timing
+ * histories; ptrt_get_option "query_pmode" reports the query's traversal, option "persist" sizes its grid as for the shading
+ * queries; band and interleaved contexts answer for the whole scene.  PTRT_E_INVALID (nothing enqueued, every output
+ * untouched) for n_texels < 0, n_shadow < 1, light_first < 0, light_count < 0, light_first + light_count beyond the uploaded
+ * lights, a NULL pointer other than d_phases, memory that is not the context's device memory or an allocation too small (byte
+ * counts are formed in size_t), a Q beyond 2^31 - 1 or a ray count beyond the limits above, or an offset that is not finite;
+ * ptrt_query_direct returns PTRT_E_NOT_READY before geometry is uploaded; n_texels == 0 returns PTRT_OK and launches
+ * nothing. */
+int ptrt_direct_rays(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n_texels,
+                     const float *d_samples2, int n_shadow, const float *d_phases /* may be NULL */, float offset,
+                     int light_first, int light_count,
+                     float *d_origins, float *d_directions, float *d_tmax, float *d_weights);
+int ptrt_query_direct(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n_texels,
+                      const float *d_samples2, int n_shadow, const float *d_phases /* may be NULL */, float offset,
+                      int light_first, int light_count, ptrt_direct *d_out);
 
 /* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
  * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small
@@ -800,7 +867,7 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         2: wherever PMODE 1 runs; 0: never.  ptrt_get_option "refilled" says what the last frame did.
  *                         ticket_tiles 1..16: consecutive tiles per draw from the queue (1; more only pays where the counter
  *                         itself binds -- 1 spp: 0.61 -> 0.49 ms with 4, still behind the one-tile-per-wave kernel's 0.43).
- *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance, ptrt_query_probes and ptrt_query_irradiance: N one-wave workgroups per CU
+ *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance, ptrt_query_probes, ptrt_query_irradiance and ptrt_query_direct: N one-wave workgroups per CU
  *                         instead of what the kernel's occupancy holds (tests: a grid smaller than the batch's chunks).
  *   sample_sync -1|0|1    the lanes of a wave start their samples together (1) instead of each as soon as its path has ended (0):
  *                         the wave's lanes then sit at the same bounce, the light-sample phases are skipped by the whole wave at a
@@ -870,7 +937,7 @@ int ptrt_set_option(ptrt_ctx *ctx, const char *name, long long value);
  * timed: render_mode (0 megakernel, 1 wavefront stages, 2 asynchronous lanes), pmode (0 lock-step, 1 pairs over LDS-staged
  * triangles, 2 pair queue, 3 TLAS rounds, 4 merged queue), merged_eff (loop shape of that launch), merged_decided (0 while
  * merged = -1 is still sampling), launches.  ABI 5.  Also read-only (ABI 6): query_pmode, the traversal of the last
- * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes / ptrt_query_irradiance (-1 none yet), and stream, the hipStream_t the context enqueues on. */
+ * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes / ptrt_query_irradiance / ptrt_query_direct (-1 none yet), and stream, the hipStream_t the context enqueues on. */
 int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
 
 /* The plan behind option "pm1_lane_groups" for leaves of `leaf_triangles` triangles, as ptrt_upload_geometry builds it; needs

@@ -397,6 +397,16 @@ PT_DEV uint32_t rng_next(Rng &s) {
 }
 // curand_uniform: (0,1]
 PT_DEV float rng_uniform(Rng &s) { return (float)rng_next(s) * 2.3283064e-10f + (2.3283064e-10f / 2.0f); }
+// Two given numbers in place of a generator's next two draws: the draw source of a sampler templated on one
+// (sample_cone_direction, sample_light) where the caller supplies the sample -- direct_sample, pt_direct.hip.h.
+struct GivenDraws {
+    float next, then;
+};
+PT_DEV float rng_uniform(GivenDraws &g) {
+    const float u = g.next;
+    g.next = g.then;
+    return u;
+}
 
 // ---------------------------------------------------------------- materials
 // One record = 6 float4 (see ptrt_capi.hip: pack_material)
@@ -573,7 +583,7 @@ PT_DEV f3 to_world(f3 sample, f3 N) {
     orthoBasis(N, T, B);
     return sample.x * T + sample.y * B + sample.z * N;
 }
-PT_DEV f3 sample_cone_direction(Rng &rng, f3 cone_dir, float cos_theta_max) {
+template <class Draws> PT_DEV f3 sample_cone_direction(Draws &rng, f3 cone_dir, float cos_theta_max) {
     const float u1 = rng_uniform(rng);
     const float u2 = rng_uniform(rng);
     const float cos_theta = 1.0f - u1 * (1.0f - cos_theta_max);

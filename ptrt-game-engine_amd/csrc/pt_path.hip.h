@@ -59,8 +59,10 @@ PT_DEV int pick_light(Rng &rng, const int n_lights) {
 
 // The sample of the picked light seen from `hit` (path_logic.cuh:313-356, 840): direction L, its density, the light's radiance
 // and the attenuation -- kept apart so that the caller's product is formed in the reference's order -- and the shadow ray's
-// origin and length.  A light with a radius draws its cone sample here.
-PT_DEV void sample_light(const LightRec &light, const int n_lights, const Surface &hit, Rng &rng, f3 &L, float &pdf_sample,
+// origin and length.  A light with a radius draws its cone sample here, from `rng`: the generator, or the two numbers a caller
+// gives (GivenDraws: direct_sample, pt_direct.hip.h).
+template <class Draws>
+PT_DEV void sample_light(const LightRec &light, const int n_lights, const Surface &hit, Draws &rng, f3 &L, float &pdf_sample,
                          f3 &light_scale, float &light_att, f3 &shadow_o, float &shadow_tmax) {
     const float pdf_pick = 1.0f / (float)n_lights;
     float attenuation = 1.0f;

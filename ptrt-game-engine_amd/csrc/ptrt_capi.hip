@@ -21,6 +21,7 @@
 #include "pt_radiance.hip.h"
 #include "pt_probe.hip.h"
 #include "pt_irradiance.hip.h"
+#include "pt_direct.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>

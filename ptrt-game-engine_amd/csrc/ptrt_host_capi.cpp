@@ -432,6 +432,23 @@ int hs_irradiance_rays(void *s, const void *d_positions, const void *d_normals, 
                                                    offset, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;
 }
+int hs_light_count(void *s) { return (int)static_cast<Scene *>(s)->getLightCount(); }
+int hs_query_direct(void *s,const void *d_positions, const void *d_normals, int n_texels, const void *d_samples2, int n_shadow,
+                    const void *d_phases, float offset, int light_first, int light_count, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryDirect(static_cast<const float *>(d_positions), static_cast<const float *>(d_normals), n_texels,
+                                                static_cast<const float *>(d_samples2), n_shadow, static_cast<const float *>(d_phases),
+                                                offset, light_first, light_count, static_cast<ptrt_direct *>(d_out)));
+    return 0;
+}
+int hs_direct_rays(void *s, const void *d_positions, const void *d_normals, int n_texels, const void *d_samples2, int n_shadow,
+                   const void *d_phases, float offset, int light_first, int light_count, void *d_origins, void *d_dirs, void *d_tmax,
+                   void *d_weights) {
+    HS_TRY(static_cast<Scene *>(s)->directRays(static_cast<const float *>(d_positions), static_cast<const float *>(d_normals), n_texels,
+                                               static_cast<const float *>(d_samples2), n_shadow, static_cast<const float *>(d_phases),
+                                               offset, light_first, light_count, static_cast<float *>(d_origins),
+                                               static_cast<float *>(d_dirs), static_cast<float *>(d_tmax), static_cast<float *>(d_weights)));
+    return 0;
+}
 int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
     HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;

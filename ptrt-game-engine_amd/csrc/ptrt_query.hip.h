@@ -1,6 +1,6 @@
 // ptrt_query.hip.h -- the device queries of the C ABI: closest hit and occlusion (ptrt_trace_rays, ptrt_query_rays), path-traced
 // radiance (ptrt_query_radiance), light probes (ptrt_query_probes), lightmap texels (ptrt_query_irradiance, with
-// ptrt_irradiance_rays for the rays alone) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
+// ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
 // ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
 // (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
 // check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
@@ -319,6 +319,115 @@ int ptrt_query_irradiance(ptrt_ctx *c, const float *d_positions, const float *d_
         });
     };
     return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+}
+
+} // extern "C"
+
+namespace {
+
+// What ptrt_direct_rays and ptrt_query_direct refuse alike, and the counts they share: Q terms per texel, n_texels * Q rays.
+struct DirectShape {
+    size_t texels = 0, terms = 0, rays = 0;
+};
+int check_direct(ptrt_ctx *c, const char *fn, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2,
+                 int n_shadow, float offset, int light_first, int light_count, DirectShape &S) {
+    if (n_texels < 0 || n_shadow < 1 || !d_positions || !d_normals || !d_samples2)
+        return fail(c, PTRT_E_INVALID, "%s: bad argument (n_texels %d, n_shadow %d, positions %p, normals %p, samples2 %p)", fn, n_texels,
+                    n_shadow, (const void *)d_positions, (const void *)d_normals, (const void *)d_samples2);
+    if (light_first < 0 || light_count < 0 || (long long)light_first + light_count > (long long)c->n_lights)
+        return fail(c, PTRT_E_INVALID, "%s: lights %d .. %d + %d of %d uploaded", fn, light_first, light_first, light_count, c->n_lights);
+    if (!std::isfinite(offset))
+        return fail(c, PTRT_E_INVALID, "%s: offset=%g (finite)", fn, (double)offset);
+    // counts in size_t: Q is below 2^62 and has to fit an int; n_texels * Q rays, times 12 bytes, has to fit size_t
+    S.texels = (size_t)n_texels;
+    S.terms = (size_t)light_count * (size_t)n_shadow;
+    if (S.terms > (size_t)INT_MAX)
+        return fail(c, PTRT_E_INVALID, "%s: %d lights x %d shadow samples: more than %d terms per texel", fn, light_count, n_shadow, INT_MAX);
+    S.rays = S.texels * S.terms;
+    if (S.rays > SIZE_MAX / 12)
+        return fail(c, PTRT_E_INVALID, "%s: %d texels x %zu terms: the rays' byte count overflows", fn, n_texels, S.terms);
+    return PTRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ptrt_direct_rays(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_shadow,
+                     const float *d_phases, float offset, int light_first, int light_count, float *d_origins, float *d_directions,
+                     float *d_tmax, float *d_weights) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_direct_rays: bad context");
+    if (!d_origins || !d_directions || !d_tmax || !d_weights)
+        return fail(c, PTRT_E_INVALID, "ptrt_direct_rays: bad argument (origins %p, directions %p, tmax %p, weights %p)",
+                    (const void *)d_origins, (const void *)d_directions, (const void *)d_tmax, (const void *)d_weights);
+    DirectShape S;
+    if (int rc = check_direct(c, "ptrt_direct_rays", d_positions, d_normals, n_texels, d_samples2, n_shadow, offset, light_first, light_count, S))
+        return rc;
+    // one thread per ray in blocks of 256: the grid's x extent is an int
+    constexpr size_t MAX_RAYS = (size_t)INT_MAX * 256;
+    if (S.rays > MAX_RAYS)
+        return fail(c, PTRT_E_INVALID, "ptrt_direct_rays: %d texels x %zu terms: more than %zu rays in one call", n_texels, S.terms, MAX_RAYS);
+    if (S.rays == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const Span sp{"positions", d_positions, S.texels * 12}, sn{"normals", d_normals, S.texels * 12},
+        ss{"samples2", d_samples2, (size_t)n_shadow * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
+        so{"origins", d_origins, S.rays * 12}, sd{"directions", d_directions, S.rays * 12}, st{"tmax", d_tmax, S.rays * sizeof(float)},
+        sw{"weights", d_weights, S.rays * 12};
+    if (int rc = d_phases ? check_spans(c, "ptrt_direct_rays", {sp, sn, ss, sph, so, sd, st, sw})
+                          : check_spans(c, "ptrt_direct_rays", {sp, sn, ss, so, sd, st, sw}))
+        return rc;
+    c->touched = true;
+    // direct_rays_kernel (pt_direct.hip.h): one thread per ray
+    hipLaunchKernelGGL(pt::direct_rays_kernel, dim3((unsigned)((S.rays + 255) / 256)), dim3(256), 0, c->stream, c->d_lights, d_positions,
+                       d_normals, S.rays, d_samples2, n_shadow, d_phases, offset, light_first, (int)S.terms, d_origins, d_directions,
+                       d_tmax, d_weights);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_query_direct(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_shadow,
+                      const float *d_phases, float offset, int light_first, int light_count, ptrt_direct *d_out) {
+    static_assert(sizeof(pt::DirectOut) == sizeof(ptrt_direct) && sizeof(ptrt_direct) == 32, "DirectOut must mirror ptrt_direct");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_direct: bad context");
+    if (!d_out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_direct: bad argument (out %p)", (const void *)d_out);
+    DirectShape S;
+    if (int rc = check_direct(c, "ptrt_query_direct", d_positions, d_normals, n_texels, d_samples2, n_shadow, offset, light_first, light_count, S))
+        return rc;
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_direct: geometry not uploaded");
+    if (n_texels == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const Span sp{"positions", d_positions, S.texels * 12}, sn{"normals", d_normals, S.texels * 12},
+        ss{"samples2", d_samples2, (size_t)n_shadow * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
+        sout{"out", d_out, S.texels * sizeof(ptrt_direct)};
+    if (int rc = d_phases ? check_spans(c, "ptrt_query_direct", {sp, sn, ss, sph, sout}) : check_spans(c, "ptrt_query_direct", {sp, sn, ss, sout}))
+        return rc;
+    if (S.terms == 0) { // no lights asked for: rows of zero bytes, in stream order
+        c->touched = true;
+        HIP_TRY(c, hipMemsetAsync(d_out, 0, S.texels * sizeof(ptrt_direct), c->stream));
+        return PTRT_OK;
+    }
+    QueryPlan P;
+    if (int rc = plan_query(c, false, 0, 0, P))
+        return rc;
+    // direct_query_kernel (pt_direct.hip.h): the grid strides over groups of 64 / w texels, w the smallest power of two >= Q;
+    // beyond 64 terms over texels, one wave per texel
+    size_t w = 1;
+    while (w < 64 && w < S.terms)
+        w *= 2;
+    const size_t per_group = 64 / w, groups = (S.texels + per_group - 1) / per_group;
+    pt::DirectOut *o = reinterpret_cast<pt::DirectOut *>(d_out);
+    return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+        return launch_persistent(c, pt::direct_query_kernel<G, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels, d_samples2,
+                                 n_shadow, d_phases, offset, light_first, (int)S.terms, o);
+    });
 }
 
 int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins, float *d_directions) {

@@ -974,6 +974,30 @@ class Scene {
         check(ptrt_irradiance_rays(ctx, d_positions, d_normals, n_texels, d_samples2, n_dirs, d_phases, offset, d_origins, d_dirs),
               "Irradiance rays failed");
     }
+    // The analytic lights' direct term at lightmap texels (ptrt_query_direct): texel t takes n_shadow light samples of each of
+    // the lights light_first .. light_first + light_count - 1 (light_count < 0: all from light_first on) at d_positions[t] with
+    // normal d_normals[t] -- the path tracer's own sample, its cone numbers the points of d_samples2 (n_shadow * 2 floats, rotated
+    // by d_phases[t] if given) --, walks their shadow rays from d_positions[t] + offset * d_normals[t], and d_out gets one 32-byte
+    // ptrt_direct per texel: the irradiance and the fractions of samples lit and shadowed.  Commits what queryRadiance commits.
+    void queryDirect(const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_shadow,
+                     const float *d_phases, float offset, int light_first, int light_count, ptrt_direct *d_out) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_query_direct(ctx, d_positions, d_normals, n_texels, d_samples2, n_shadow, d_phases, offset, light_first,
+                                light_count < 0 ? (int)lights.size() - light_first : light_count, d_out),
+              "Direct query failed");
+    }
+    // The shadow rays queryDirect walks and their weights (ptrt_direct_rays): per ray t * Q + q, Q = light_count * n_shadow, an
+    // origin and a direction (3 floats each), a length and a weight (3 floats), for rays the query would not walk too.
+    void directRays(const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_shadow,
+                    const float *d_phases, float offset, int light_first, int light_count, float *d_origins, float *d_dirs,
+                    float *d_tmax, float *d_weights) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_direct_rays(ctx, d_positions, d_normals, n_texels, d_samples2, n_shadow, d_phases, offset, light_first,
+                               light_count < 0 ? (int)lights.size() - light_first : light_count, d_origins, d_dirs, d_tmax, d_weights),
+              "Direct rays failed");
+    }
     // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
     // tile rows * width * 3 floats each, in the order of the colour buffer.
     void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {

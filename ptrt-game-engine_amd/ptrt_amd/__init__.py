@@ -129,6 +129,12 @@ class Irradiance(C.Structure):
                 ("hit_fraction", C.c_float), ("reserved", C.c_float * 2)]
 
 
+class Direct(C.Structure):
+    """`ptrt_direct`: one lightmap texel's answer from ptrt_query_direct."""
+    _fields_ = [("irradiance", C.c_float * 3), ("lit_fraction", C.c_float), ("shadowed_fraction", C.c_float),
+                ("reserved", C.c_float * 3)]
+
+
 class Stats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64),
                 ("shadow_rays_walked", C.c_uint64)]
@@ -165,6 +171,8 @@ assert PROBE_DTYPE.itemsize == C.sizeof(Probe) == 128
 IRRADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("mean_distance", "<f4"), ("mean_distance_sq", "<f4"), ("hit_fraction", "<f4"),
                              ("reserved", "<f4", 2)])
 assert IRRADIANCE_DTYPE.itemsize == C.sizeof(Irradiance) == 32
+DIRECT_DTYPE = np.dtype([("irradiance", "<f4", 3), ("lit_fraction", "<f4"), ("shadowed_fraction", "<f4"), ("reserved", "<f4", 3)])
+assert DIRECT_DTYPE.itemsize == C.sizeof(Direct) == 32
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
@@ -208,6 +216,8 @@ _sig("ptrt_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_i
 _sig("ptrt_query_probes", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("ptrt_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp)
 _sig("ptrt_query_irradiance", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_float, _vp)
+_sig("ptrt_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
+_sig("ptrt_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp)
 _sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
@@ -337,6 +347,9 @@ _sig("hs_query_radiance", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int
 _sig("hs_query_probes", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("hs_query_irradiance", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("hs_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp)
+_sig("hs_light_count", C.c_int, _vp)
+_sig("hs_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp)
+_sig("hs_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -453,6 +466,19 @@ def irradiance_fields(records):
     """Named views of query_irradiance's (n, 8) float32 rows (a tensor or an array): radiance as (n, 3), scalars as (n,)."""
     out = {}
     for name, (a, b) in IRRADIANCE_COLUMNS.items():
+        col = records[:, a:b]
+        out[name] = col[:, 0] if b - a == 1 else col
+    return out
+
+
+# columns of the (n, 8) float32 rows of Scene.query_direct: the fields of ptrt_direct / DIRECT_DTYPE
+DIRECT_COLUMNS = dict(irradiance=(0, 3), lit_fraction=(3, 4), shadowed_fraction=(4, 5), reserved=(5, 8))
+
+
+def direct_fields(records):
+    """Named views of query_direct's (n, 8) float32 rows (a tensor or an array): irradiance as (n, 3), scalars as (n,)."""
+    out = {}
+    for name, (a, b) in DIRECT_COLUMNS.items():
         col = records[:, a:b]
         out[name] = col[:, 0] if b - a == 1 else col
     return out
@@ -1103,6 +1129,74 @@ class Scene:
             self._h, _vp(positions.data_ptr()), _vp(normals.data_ptr()), n, _vp(samples2.data_ptr()), k,
             None if phases is None else _vp(phases.data_ptr()), float(offset), _vp(o.data_ptr()), _vp(d.data_ptr()))))
         return o, d
+
+    def lightCount(self):
+        return lib.hs_light_count(self._h)
+
+    def _direct_inputs(self, what, positions, normals, samples2, phases, lights):
+        """the shared inputs of query_direct / direct_rays, checked; returns (n texels, samples2, shadow samples, first light,
+        light count)"""
+        have = self.lightCount()
+        try:
+            first, count = (0, have) if lights is None else (int(lights[0]), int(lights[1]))
+        except (TypeError, IndexError):
+            raise ValueError(f"{what}: lights={lights!r}, expected None or (first, count)") from None
+        if first < 0 or count < 0 or first + count > have:
+            raise ValueError(f"{what}: lights ({first}, {count}) of the scene's {have}")
+        self._device_tensor(f"{what}: positions", positions, 3, "torch.float32")
+        if samples2 is None:
+            import torch
+            samples2 = torch.from_numpy(lightmap.hammersley2(1)).to(positions.device)
+        n, k = self._texel_inputs(what, positions, normals, samples2, phases)
+        if count * k >= 2 ** 31:
+            raise ValueError(f"{what}: {count} lights x {k} shadow samples (at most 2^31 - 1 terms per texel)")
+        return n, samples2, k, first, count
+
+    def query_direct(self, positions, normals, samples2=None, phases=None, offset=1e-4, lights=None, out=None):
+        """The analytic lights' direct term at lightmap texels: texel t takes one light sample per point of `samples2` (k points
+        in [0,1)^2, one set for all texels and lights, the two numbers of a sphere light's cone sample; None: the one point of
+        `lightmap.hammersley2(1)`) of each light of `lights` ((first, count) of the scene's lights; None: all) at positions[t]
+        with normal normals[t] (used as given), and walks the shadow rays of the samples that can add something from
+        positions[t] + offset * normals[t] (`phases`, (n,) float32, rotates each texel's set).  torch tensors on this scene's
+        device, contiguous, read in place: positions and normals (n, 3), samples2 (k, 2) float32.  Returns an (n, 8) float32
+        tensor, one 32-byte `ptrt_direct` per row (`direct_fields` names the columns): the irradiance (0:3) -- the sum over the
+        lights of each light's mean over its samples; a light with a radius contributes radiance * solid angle --, the fraction
+        of samples that reached the texel (3) and that were blocked (4); `out` takes such a tensor to write into.
+        `ptrt_amd.lightmap` adds it to a gather's rows.  No synchronisation."""
+        n, samples2, k, first, count = self._direct_inputs("query_direct", positions, normals, samples2, phases, lights)
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=positions.device)
+        else:
+            self._device_tensor("query_direct: out", out, 8, "torch.float32")
+            if out.shape[0] != n:
+                raise ValueError(f"query_direct: out has {out.shape[0]} rows for {n} texels")
+        if n == 0:
+            return out
+        self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_direct(
+            self._h, _vp(positions.data_ptr()), _vp(normals.data_ptr()), n, _vp(samples2.data_ptr()), k,
+            None if phases is None else _vp(phases.data_ptr()), float(offset), first, count, _vp(out.data_ptr()))))
+        return out
+
+    def direct_rays(self, positions, normals, samples2=None, phases=None, offset=1e-4, lights=None):
+        """(origins, directions, tmax, weights): (n * Q, 3), (n * Q, 3), (n * Q,) and (n * Q, 3) float32 tensors holding the shadow
+        rays of query_direct for these texels and what each adds when it is not blocked, term (t, q) in row t * Q + q with
+        Q = light count * k and q = light * k + sample (ptrt_direct_rays) -- for the samples query_direct does not walk too
+        (weight not positive, NaN included).  Arguments as for query_direct.  No synchronisation."""
+        n, samples2, k, first, count = self._direct_inputs("direct_rays", positions, normals, samples2, phases, lights)
+        import torch
+        rays = n * count * k
+        o = torch.empty((rays, 3), dtype=torch.float32, device=positions.device)
+        d = torch.empty((rays, 3), dtype=torch.float32, device=positions.device)
+        t = torch.empty((rays,), dtype=torch.float32, device=positions.device)
+        w = torch.empty((rays, 3), dtype=torch.float32, device=positions.device)
+        if rays == 0:
+            return o, d, t, w
+        self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_direct_rays(
+            self._h, _vp(positions.data_ptr()), _vp(normals.data_ptr()), n, _vp(samples2.data_ptr()), k,
+            None if phases is None else _vp(phases.data_ptr()), float(offset), first, count, _vp(o.data_ptr()), _vp(d.data_ptr()),
+            _vp(t.data_ptr()), _vp(w.data_ptr()))))
+        return o, d, t, w
 
     def camera_rays(self, frame, sample=0):
         """(origins, directions): (rows * width, 3) float32 tensors on this scene's device holding the primary rays

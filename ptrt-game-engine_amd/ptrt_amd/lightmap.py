@@ -3,7 +3,10 @@ with the (n, 8) rows.  Plain numpy, no device code -- the arrays go to the devic
 come back with .cpu().numpy() (torch tensors on the host are accepted where rows are).
 
 A texel's rays are cosine-distributed about its normal, so the mean of their radiance times pi is the irradiance; a texel whose
-rays mostly end close by -- inside a wall, under a carpet -- is one a baker fills from its neighbours (`invalid_texels`)."""
+rays mostly end close by -- inside a wall, under a carpet -- is one a baker fills from its neighbours (`invalid_texels`).
+
+Scene.query_direct adds what the gather cannot see, the analytic lights at the texel itself: `direct_irradiance`,
+`penumbra_texels` and `total_irradiance` read its rows."""
 import math
 
 import numpy as np
@@ -79,3 +82,31 @@ def invalid_texels(records, threshold):
     mean_distance < threshold: the texel lies inside or right under geometry, and a baker dilates its neighbours over it."""
     r = _rows(records)
     return (r[:, 5] >= np.float32(1.0)) & (r[:, 3] < np.float32(threshold))
+
+
+def direct_irradiance(rows):
+    """(n, 3) float32: the irradiance columns of query_direct's (n, 8) rows -- already an irradiance (the lights' radiance times
+    attenuation times the cosine, over the sample's density), no factor of pi"""
+    return np.ascontiguousarray(_rows(rows)[:, 0:3].astype(np.float32))
+
+
+def penumbra_texels(rows):
+    """(n,) bool: texels of query_direct's rows that some shadow samples reached and some did not -- lit_fraction > 0 and
+    shadowed_fraction > 0: a sphere light's penumbra, or a texel lit by some lights of the range and shadowed from others.
+    These are the texels that gain from more shadow samples."""
+    r = _rows(rows)
+    return (r[:, 3] > np.float32(0.0)) & (r[:, 4] > np.float32(0.0))
+
+
+def total_irradiance(direct_rows, gather_rows):
+    """(n, 3) float32: direct_irradiance(direct_rows) + irradiance(gather_rows), the direct term of the analytic lights at the
+    texel plus pi times the gather's mean radiance (one float32 product and one sum per value).
+
+    What this sum still LACKS: a gather ray takes no light sample at its first hit (the quirk of a caller's ray, include/ptrt.h),
+    so the analytic lights' one-bounce term -- light that reaches the texel after exactly one diffuse reflection off the surface
+    a gather ray hits first -- is absent; emissive meshes, the sky and every later bounce are in the gather.  A lit first vertex
+    for the gather is not built."""
+    d, g = direct_irradiance(direct_rows), irradiance(gather_rows)
+    if d.shape != g.shape:
+        raise ValueError(f"total_irradiance: {d.shape[0]} direct rows, {g.shape[0]} gather rows")
+    return d + g
