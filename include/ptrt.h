@@ -909,6 +909,16 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         query did (0 as well under another traversal mode, PMODE 4 among them).  The value travels with a
  *                         launch's arguments: a frame recorded into a caller's hipGraph keeps the value from when it was captured,
  *                         as it keeps pair_split and the transform flag -- record again after any of the calls above.
+ *   tri_frames -1|0|1     PMODE 1's megakernel: the tangent frame (T, B) that turns a BSDF sample into world space is read from a
+ *                         per-triangle table instead of being computed at every vertex.  On a mesh without a transform the shading
+ *                         normal is the packet's geometric normal or its negation, so ptrt_upload_geometry stores, with the
+ *                         normals, what orthoBasis returns for both (64 bytes per triangle); a lane loads the record of its
+ *                         triangle and side.  Same bits: the record holds the function's own result.  -1 (default) and 1: on
+ *                         while the upload's normals stand and no mesh of the scene has a transform (1 never forces it); 0:
+ *                         never.  The calls that turn plain_leaf off turn this off too until the next ptrt_upload_geometry -- a
+ *                         refit writes new normals and no frames, so a scene that refits every frame keeps computing them.
+ *                         ptrt_get_option "tri_frames_eff" says what the last frame did.  Travels with a launch's arguments as
+ *                         plain_leaf does.
  *   tile_run 0..64        the one-tile-per-workgroup kernels' workgroup -> tile map.  Consecutive workgroups go to the eight XCDs in
  *                         turn; with n > 0, of every 8 n consecutive tiles XCD x renders tiles [x n, (x + 1) n) -- neighbours,
  *                         whose rays walk the same part of the trees, share an L2 -- instead of every eighth tile.  8 (default):

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                             const LightRec light = load_light(K.lights, pick_light(rng, K.n_lights));
                             // this lane's next ray is its shadow ray (origin and length straight into ro, tm); [E] follows
                             // when that is finished
-                            sample_light(light, K.n_lights, hit, rng, L, pdf_sample, light_scale, light_att, ro, tm);
+                            sample_light(light, K.inv_n_lights, hit, rng, L, pdf_sample, light_scale, light_att, ro, tm);
                             ++n_shadow;
                             anyq = true;
                             newray = true;

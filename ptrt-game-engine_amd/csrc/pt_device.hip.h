@@ -79,6 +79,18 @@ PT_DEV float rcp_ieee_above(float y) {
         r = below ? r : 1.0f / y;
     return r;
 }
+// -1.0f / y, through the same core: rounding to nearest is symmetric, so -(RN(1 / y)) == RN(-1 / y) for every y the core
+// covers.  Everything outside mid_exponent -- NaN and the infinities included -- takes the ORIGINAL expression under the same
+// wave-wide ballot, so that a NaN's sign bit is what the compiler's sequence gives.  tests/test_neg_rcp_gpu.py: all 2^32 inputs.
+PT_DEV float neg_rcp_ieee(float y) {
+    const float r0 = __builtin_amdgcn_rcpf(y);
+    const float e = fma_(-y, r0, 1.0f);
+    float r = -fma_(e, r0, r0);
+    const bool mid = mid_exponent(y);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!mid) != 0ull, 0))
+        r = mid ? r : -1.0f / y;
+    return r;
+}
 // v / t for a vector: the reference divides component by component (vec3.cuh:54-56), so three IEEE divisions share their
 // divisor -- and hipcc's expansion of each (above) shares nothing, because v_div_scale looks at both operands.  With the
 // correctly rounded reciprocal r = RN(1/t) of rcp_ieee's Newton core, ONE residual step per component is enough
@@ -571,9 +583,10 @@ PT_DEV void orthoBasis(f3 N, f3 &T, f3 &B) {
         B = mk3(0.0f, 1.0f, 0.0f);
         return;
     }
-    const f3 Nn = N * (1.0f / sqrt_ieee(len2));
+    // (both reciprocals through the Newton core, equal in bits to `1.0f / y` and `-1.0f / y` for every input: rcp_ieee, neg_rcp_ieee)
+    const f3 Nn = N * rcp_ieee(sqrt_ieee(len2));
     const float s = __builtin_copysignf(1.0f, Nn.z);
-    const float a = -1.0f / (s + Nn.z);
+    const float a = neg_rcp_ieee(s + Nn.z);
     const float b = Nn.x * Nn.y * a;
     T = mk3(1.0f + s * Nn.x * Nn.x * a, s * b, -s * Nn.x);
     B = cross(Nn, T);
@@ -581,6 +594,24 @@ PT_DEV void orthoBasis(f3 N, f3 &T, f3 &B) {
 PT_DEV f3 to_world(f3 sample, f3 N) {
     f3 T, B;
     orthoBasis(N, T, B);
+    return sample.x * T + sample.y * B + sample.z * N;
+}
+// N's frame where a caller may already hold it: T and B as orthoBasis(N) returns them, read from the per-triangle table
+// (tri_normals_kernel, KParams::tri_frames) -- `have` false: nobody has, and to_world makes them.  The default is a constant,
+// so a loop that passes no frame compiles to the text above.
+struct TangentFrame {
+    f3 T, B;
+    bool have;
+};
+PT_DEV TangentFrame no_frame() { return TangentFrame{f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}, false}; }
+PT_DEV f3 to_world(f3 sample, f3 N, const TangentFrame &F) {
+    f3 T, B;
+    if (F.have) {
+        T = F.T;
+        B = F.B;
+    } else {
+        orthoBasis(N, T, B);
+    }
     return sample.x * T + sample.y * B + sample.z * N;
 }
 template <class Draws> PT_DEV f3 sample_cone_direction(Draws &rng, f3 cone_dir, float cos_theta_max) {
@@ -602,7 +633,7 @@ PT_DEV f3 sample_cosine_hemisphere(Rng &rng) {
     det_sincos(phi, sp, cp);
     return mk3(r * cp, r * sp, sqrt_ieee(max_(0.0f, 1.0f - u1)));
 }
-PT_DEV f3 importance_sample_ggx(Rng &rng, f3 N, float roughness) {
+PT_DEV f3 importance_sample_ggx(Rng &rng, f3 N, float roughness, const TangentFrame &F = no_frame()) {
     const float a = roughness * roughness;
     const float a2 = a * a;
     const float u1 = rng_uniform(rng);
@@ -613,7 +644,7 @@ PT_DEV f3 importance_sample_ggx(Rng &rng, f3 N, float roughness) {
     const float sinTheta = sqrt_ieee(max_(0.0f, 1.0f - cosTheta * cosTheta));
     float sp, cp;
     det_sincos(phi, sp, cp);
-    return to_world(mk3(sinTheta * cp, sinTheta * sp, cosTheta), N);
+    return to_world(mk3(sinTheta * cp, sinTheta * sp, cosTheta), N, F);
 }
 
 // --------------------------------------------------------------- BSDF eval
@@ -773,8 +804,9 @@ template <bool FULL> PT_DEV float material_pdf(const Surface &hit, const Materia
 template <bool FULL>
 // `draws_only`: the vertex is the path's last (the depth limit follows): nothing of the scattered ray will be looked at, only
 // the generator has to move on exactly as it would -- the same uniforms drawn, the same answer, none of the arithmetic.
+// `F`: the tangent frame of hit.normal, where the caller has it (TangentFrame).
 PT_DEV bool material_scatter(const Surface &hit, const Material &mat, f3 ray_dir, Rng &rng, f3 &scattered_dir,
-                             f3 &attenuation, bool &is_specular_bounce, bool draws_only = false) {
+                             f3 &attenuation, bool &is_specular_bounce, bool draws_only = false, const TangentFrame &F = no_frame()) {
     const f3 V = -ray_dir;
     const f3 N = hit.normal;
     const float NdotV = max_(dot(N, V), 0.0f);
@@ -820,7 +852,7 @@ PT_DEV bool material_scatter(const Surface &hit, const Material &mat, f3 ray_dir
             const bool pick_refl = !pick_coat && (u < P_coat + P_trans_reflect);
             const bool is_refraction = !pick_coat && !pick_refl;
             const float sample_roughness = pick_coat ? clearcoatRough : (pick_refl ? rough : transRough);
-            f3 H = importance_sample_ggx(rng, N, sample_roughness);
+            f3 H = importance_sample_ggx(rng, N, sample_roughness, F);
             is_specular_bounce = (sample_roughness < 0.1f);
             if (!is_refraction) {
                 scattered_dir = reflectVec(-V, H);
@@ -944,7 +976,7 @@ PT_DEV bool material_scatter(const Surface &hit, const Material &mat, f3 ray_dir
         const float s1 = sqrt_ieee(ggx ? (1.0f - u2) / (1.0f + (a2 - 1.0f) * u2) : u1);
         const float s2 = sqrt_ieee(max_(0.0f, 1.0f - (ggx ? s1 * s1 : u1)));
         const float rad = ggx ? s2 : s1, up = ggx ? s1 : s2;
-        const f3 w = to_world(mk3(rad * cp, rad * sp, up), N);
+        const f3 w = to_world(mk3(rad * cp, rad * sp, up), N, F);
         const f3 refl = reflectVec(-V, w);
         scattered_dir.x = ggx ? refl.x : w.x;
         scattered_dir.y = ggx ? refl.y : w.y;

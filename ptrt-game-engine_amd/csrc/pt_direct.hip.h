@@ -56,7 +56,7 @@ PT_DEV DirectSample direct_sample(const float4 *__restrict__ lights, const float
     DirectSample r;
     f3 radiance, path_o;
     float pdf, att;
-    sample_light(light, 1, hit, u, r.L, pdf, radiance, att, path_o, r.tmax);
+    sample_light(light, 1.0f, hit, u, r.L, pdf, radiance, att, path_o, r.tmax);
     const float c = dot(hit.normal, r.L);
     r.weight = mk3(0.0f);
     if (c > 0.0f && pdf > 0.0f)

@@ -134,6 +134,13 @@ struct KParams {
     // leaves out the root test, the PMODE 1 pair batches the instance arithmetic.  PMODE 4 (trace_merged,
     // build_pairs_merged) does not read it.  Last, so that no other argument moved.
     int plain_leaf;
+    // 1.0f / (float)n_lights, divided once on the host: the IEEE quotient the light sampling used to form per vertex (the
+    // same bits; pt_path.hip.h sample_light, path_trace_kernel [C]).  0 when there are no lights: nobody reads it then.
+    float inv_n_lights;
+    // PMODE 1 [E]: the tangent frames of every triangle's two shading normals (tri_normals_kernel), or nullptr -- then, as in
+    // every other loop, to_world makes its frame with orthoBasis.  Non-null only while the normals in the packets are the
+    // upload's and no mesh has a transform (option "tri_frames", plan_frame).  After everything that was here before.
+    const float4 *tri_frames;
 };
 constexpr int COUNTER_WORDS = 4;
 
@@ -643,7 +650,13 @@ template <int GEOM> PT_DEV bool any_hit(const KParams &K, bool alive, f3 o, f3 d
 // computed once per (re)packing by the one function below and kept in the packets' three spare w words, instead of a cross
 // product, a square root and three divisions (~100 VALU) in every shading iteration.
 PT_DEV f3 packet_normal(float4 p1, float4 p2) { return normalize(cross(mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z))); }
-__global__ void tri_normals_kernel(float4 *__restrict__ tris, int n_slots) {
+// The tangent frame of to_world (orthoBasis) is a function of the shading normal, and on a mesh without a transform that
+// normal is exactly gn or -gn (make_surface_of): two frames per triangle, made here with the normals.  tri_frames holds
+// TRI_FRAME_F4 float4 per leaf slot: {T, -}, {B, -} of orthoBasis(gn), then the same of orthoBasis(-gn) -- each what the
+// function itself returns for that argument (the back frame's B differs from the front one's in the signs of its zeros), so a
+// lane that reads its record has the bits it would have computed.  A slot whose normal is not finite cannot be hit.
+constexpr int TRI_FRAME_F4 = 4;
+__global__ void tri_normals_kernel(float4 *__restrict__ tris, float4 *__restrict__ tri_frames, int n_slots) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_slots)
         return;
@@ -651,6 +664,13 @@ __global__ void tri_normals_kernel(float4 *__restrict__ tris, int n_slots) {
     tris[s * 3 + 0].w = gn.x;
     tris[s * 3 + 1].w = gn.y;
     tris[s * 3 + 2].w = gn.z;
+    f3 T, B;
+    orthoBasis(gn, T, B);
+    tri_frames[s * TRI_FRAME_F4 + 0] = make_float4(T.x, T.y, T.z, 0.0f);
+    tri_frames[s * TRI_FRAME_F4 + 1] = make_float4(B.x, B.y, B.z, 0.0f);
+    orthoBasis(-gn, T, B);
+    tri_frames[s * TRI_FRAME_F4 + 2] = make_float4(T.x, T.y, T.z, 0.0f);
+    tri_frames[s * TRI_FRAME_F4 + 3] = make_float4(B.x, B.y, B.z, 0.0f);
 }
 
 // Two-level node records: record i = {node i, node of its left child, node of its right child} (an absent or leaf child's
@@ -934,6 +954,103 @@ __global__ void div3_check_kernel(uint32_t first, uint32_t count, int mode, unsi
             ++bad;
         }
     }
+}
+
+// exhaustive check of neg_rcp_ieee: every fp32 bit pattern against the compiler's `-1.0f / y`, BITWISE (a NaN's sign and payload
+// included: outside its range neg_rcp_ieee is that expression).  out as in rcp_check_kernel.
+__global__ void neg_rcp_check_kernel(unsigned int *out) {
+    const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long b = tid; b < (1ull << 32); b += stride) {
+        const float y = __uint_as_float((uint32_t)b);
+        const float want = -1.0f / y;
+        const float got = neg_rcp_ieee(y);
+        if (__float_as_uint(want) != __float_as_uint(got)) {
+            const unsigned int k = atomicAdd(&out[0], 1u);
+            if (k < 8)
+                out[1 + k] = (uint32_t)b;
+        }
+    }
+}
+
+// orthoBasis as it was written before its two reciprocals went through the Newton core: the compiler's divisions.  The
+// statement orthoBasis_check_kernel compares pt::orthoBasis with.
+PT_DEV void orthoBasis_divided(f3 N, f3 &T, f3 &B) {
+    const float len2 = dot(N, N);
+    if (len2 < 1e-20f) {
+        T = mk3(1.0f, 0.0f, 0.0f);
+        B = mk3(0.0f, 1.0f, 0.0f);
+        return;
+    }
+    const f3 Nn = N * (1.0f / sqrt_ieee(len2));
+    const float s = __builtin_copysignf(1.0f, Nn.z);
+    const float a = -1.0f / (s + Nn.z);
+    const float b = Nn.x * Nn.y * a;
+    T = mk3(1.0f + s * Nn.x * Nn.x * a, s * b, -s * Nn.x);
+    B = cross(Nn, T);
+}
+PT_DEV uint32_t check_hash(uint32_t x) { // (lowbias32)
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+// The k-th normal of the check, by its class k & 7: 0..3 a random unit vector (as normalize() leaves it); 4 axis-aligned and
+// diagonal directions with zeros of BOTH signs; 5 a random direction scaled so that len2 lies in [0.25e-20, 2.25e-20], either
+// side of orthoBasis's threshold; 6 a unit vector with one component NaN or infinite; 7 three arbitrary bit patterns.
+PT_DEV f3 orthoBasis_check_normal(uint32_t seed, uint32_t k) {
+    const uint32_t h0 = check_hash(seed ^ (k * 3u + 0u)), h1 = check_hash(seed ^ (k * 3u + 1u)) + h0, h2 = check_hash(h1 ^ (k * 3u + 2u));
+    const f3 r = mk3((float)(int32_t)h0 * 0x1p-31f, (float)(int32_t)h1 * 0x1p-31f, (float)(int32_t)h2 * 0x1p-31f);
+    f3 u = normalize(r);
+    const uint32_t cls = k & 7u, j = k >> 3;
+    if (cls == 4) {
+        const auto v = [](uint32_t i) { return __uint_as_float(((i & 2u) ? 0x3f800000u : 0u) | ((i & 1u) << 31)); }; // 0, -0, 1, -1
+        u = mk3(v(j), v(j >> 2), v(j >> 4));
+        if (j & 64u)
+            u = normalize(u); // (the diagonals; the all-zero vector becomes NaN, which is an input like any other)
+    } else if (cls == 5) {
+        u = u * (1e-10f * (0.5f + (float)(h2 >> 8) * 0x1p-24f));
+    } else if (cls == 6) {
+        const float bad = __uint_as_float((j & 4u) ? (0x7f800000u | ((j & 8u) << 28)) : (0x7fc00000u | ((j & 8u) << 28) | (h2 & 0x3fffffu)));
+        if ((j & 3u) == 0)
+            u.x = bad;
+        else if ((j & 3u) == 1)
+            u.y = bad;
+        else
+            u.z = bad;
+    } else if (cls == 7) {
+        u = mk3(__uint_as_float(h0), __uint_as_float(h1), __uint_as_float(h2));
+    }
+    return u;
+}
+// pt::orthoBasis against orthoBasis_divided over `count` normals from `seed`: T and B compared BITWISE.  out[0] = mismatching
+// normals, out[1..6] = the first two offending normals' bit patterns, out[7] = normals that took the len2 < 1e-20 arm,
+// out[8] = normals whose T or B holds a NaN (so that a test can tell that every class was met).
+__global__ void orthoBasis_check_kernel(uint32_t seed, uint32_t count, unsigned int *out) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count)
+        return;
+    const f3 N = orthoBasis_check_normal(seed, k);
+    f3 T, B, T0, B0;
+    orthoBasis(N, T, B);
+    orthoBasis_divided(N, T0, B0);
+    const bool ne = __float_as_uint(T.x) != __float_as_uint(T0.x) || __float_as_uint(T.y) != __float_as_uint(T0.y) ||
+                    __float_as_uint(T.z) != __float_as_uint(T0.z) || __float_as_uint(B.x) != __float_as_uint(B0.x) ||
+                    __float_as_uint(B.y) != __float_as_uint(B0.y) || __float_as_uint(B.z) != __float_as_uint(B0.z);
+    if (ne) {
+        const unsigned int m = atomicAdd(&out[0], 1u);
+        if (m < 2) {
+            out[1 + 3 * m] = __float_as_uint(N.x);
+            out[2 + 3 * m] = __float_as_uint(N.y);
+            out[3 + 3 * m] = __float_as_uint(N.z);
+        }
+    }
+    if (dot(N, N) < 1e-20f)
+        atomicAdd(&out[7], 1u);
+    if (T0.x != T0.x || T0.y != T0.y || T0.z != T0.z || B0.x != B0.x || B0.y != B0.y || B0.z != B0.z)
+        atomicAdd(&out[8], 1u);
 }
 
 // deterministic-math probe for tests: op 0 sin, 1 cos, 2 exp, 3 log, 4 pow

@@ -62,9 +62,9 @@ PT_DEV int pick_light(Rng &rng, const int n_lights) {
 // origin and length.  A light with a radius draws its cone sample here, from `rng`: the generator, or the two numbers a caller
 // gives (GivenDraws: direct_sample, pt_direct.hip.h).
 template <class Draws>
-PT_DEV void sample_light(const LightRec &light, const int n_lights, const Surface &hit, Draws &rng, f3 &L, float &pdf_sample,
+PT_DEV void sample_light(const LightRec &light, const float inv_n_lights, const Surface &hit, Draws &rng, f3 &L, float &pdf_sample,
                          f3 &light_scale, float &light_att, f3 &shadow_o, float &shadow_tmax) {
-    const float pdf_pick = 1.0f / (float)n_lights;
+    const float pdf_pick = inv_n_lights; // 1.0f / (float)n_lights: KParams::inv_n_lights, the host's IEEE quotient
     float attenuation = 1.0f;
     float light_dist = 1e30f;
     const f3 light_radiance = light.color * light.intensity;
@@ -128,12 +128,15 @@ PT_DEV bool light_sample_value(const Surface &hit, const Material &mat, const f3
 // The BSDF sample and what follows it (path_logic.cuh:843-896): scatter, Russian roulette from the third vertex, the
 // throughput's clamp, the next ray from the offset origin, the depth limit.  True: the path goes on with (ro, rd) -- it ends
 // where the material absorbs, the roulette kills, or `bounce` reaches max_depth (ray and throughput are then the last vertex's).
+// `F`: hit.normal's tangent frame from the per-triangle table (KParams::tri_frames), for a loop that reads it; none of the
+// loops this file serves does by default -- path_trace_kernel's PMODE 1 is the one measured to gain.
 template <bool FULL>
 PT_DEV bool scatter_and_continue(const Surface &hit, const Material &mat, Rng &rng, const int max_depth, f3 &ro, f3 &rd,
-                                 f3 &throughput, int &bounce, bool &ray_spec, bool &prev_was_specular) {
+                                 f3 &throughput, int &bounce, bool &ray_spec, bool &prev_was_specular,
+                                 const TangentFrame &F = no_frame()) {
     f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
     bool is_specular = false;
-    if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular))
+    if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular, false, F))
         return false;
     prev_was_specular = is_specular;
     if (bounce >= 2) { // Russian roulette (path_logic.cuh:871-880)

@@ -91,7 +91,7 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
                     // light sample of next-event estimation (path_logic.cuh:305-382, 840)
                     if (!ray_spec && KC.n_lights > 0) {
                         const LightRec light = load_light(KC.lights, pick_light(rng, KC.n_lights));
-                        sample_light(light, KC.n_lights, hit, rng, L, pdf_sample, light_scale, light_att, shadow_o, shadow_tmax);
+                        sample_light(light, KC.inv_n_lights, hit, rng, L, pdf_sample, light_scale, light_att, shadow_o, shadow_tmax);
                         want_shadow = true;
                     }
                 }

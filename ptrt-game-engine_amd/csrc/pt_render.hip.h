@@ -2296,7 +2296,9 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         const KParams &KB = kparams(kp0);
         // ---- [B] closest hit, all live lanes together (PMODE 4: and the parked shadow rays in the same traversal)
         Hit h;
-        int h_order = 0; // PMODE 1: the hit mesh's place in the leaf (what the staged tables are indexed by)
+        int h_order = 0; // PMODE 1: the hit mesh's place in the leaf (what the staged tables are indexed by); from the end of [C]
+                         // with the hit's record in tri_frames above H_ORDER_BITS
+        constexpr int H_ORDER_BITS = 10, H_ORDER_MASK = (1 << H_ORDER_BITS) - 1;
         if (MERGED) {
             bool blocked = false;
             const unsigned long long t_tr = TS_NOW();
@@ -2397,13 +2399,18 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
                     if (sb < 0x10000 || prev_was_specular)
                         acc = acc + throughput * mk3(m2.x, m2.y, m2.z);
                 }
+                // PMODE 1: where [E] finds the tangent frame of this triangle and side (KParams::tri_frames), carried in h_order
+                // above the mesh's place (< 1024 meshes, pair_mode): kept as h.slot, it was one more register across the
+                // shadow phase and the lane-refill kernel put four in scratch
+                if (PMODE == 1)
+                    h_order |= (h.slot * TRI_FRAME_F4 + (hit.front_face ? 0 : 2)) << H_ORDER_BITS;
                 // light sample of next-event estimation (path_logic.cuh:305-382, 840)
                 if (!ray_spec && KC.n_lights > 0) {
                     float r = rng_uniform(rng);
                     r = min_(r, 0.99999994f);
                     const int light_index = (int)(r * (float)KC.n_lights);
                     const LightRec light = lights_lds ? load_light<true>(PL.lights, light_index) : load_light(KC.lights, light_index);
-                    const float pdf_pick = 1.0f / (float)KC.n_lights;
+                    const float pdf_pick = KC.inv_n_lights; // 1.0f / (float)n_lights, the host's quotient (KParams)
                     float attenuation = 1.0f;
                     float light_dist = 1e30f;
                     const f3 light_radiance = light.color * light.intensity;
@@ -2474,7 +2481,7 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         bool lit = false;
         f3 lit_now = mk3(0.0f);
         if (want_shadow) {
-            int mi = mats_lds ? h_order : h.mesh;
+            int mi = mats_lds ? (h_order & H_ORDER_MASK) : h.mesh;
             asm volatile("" : "+v"(mi)); // (its own fetch of the material: not 22 registers live across the shadow phase)
             const Material mat = mats_lds ? load_material<true, MAT_F4>(PL.mats, mi) : load_material(KC2.materials, mi);
             const f3 V = -rd;
@@ -2539,14 +2546,28 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         const unsigned long long t_pe = TS_NOW();
         // ---- [E] second half of the shading
         if (shaded) {
-            const Material mat = mats_lds ? load_material<true, MAT_F4>(PL.mats, h_order) : load_material(KE.materials, h.mesh);
-            f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
-            bool is_specular = false;
             // (the path's last vertex -- the depth limit follows: the scattered ray is never traced and the throughput never read
             // again, so only the generator moves on, by the uniforms the reference draws here: lobe, direction, roulette.  With
             // the samples in step this is the whole wave in one iteration of max_depth.)
             const bool last = (sb >> 16) + 1 >= KE.max_depth;
-            if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular, last)) {
+            // PMODE 1: the frame of to_world from the triangle's record (KParams::tri_frames) -- hit.normal is gn or -gn there,
+            // so T and B are what orthoBasis(hit.normal) returns.  The two loads go out first and are waited for at to_world,
+            // behind the material, the generator's draws and det_sincos.  Wave-uniform: the pointer is a launch constant.
+            TangentFrame F = no_frame();
+            if (PMODE == 1 && KE.tri_frames != nullptr) {
+                F.have = true;
+                if (!last) {
+                    // (three dwords of each float4: the w words hold nothing)
+                    const float3 *rec = (const float3 *)(KE.tri_frames + (h_order >> H_ORDER_BITS)); // ([C])
+                    const float3 fT = rec[0], fB = *(const float3 *)((const float4 *)rec + 1);
+                    F.T = mk3(fT.x, fT.y, fT.z);
+                    F.B = mk3(fB.x, fB.y, fB.z);
+                }
+            }
+            const Material mat = mats_lds ? load_material<true, MAT_F4>(PL.mats, h_order & H_ORDER_MASK) : load_material(KE.materials, h.mesh);
+            f3 scatter_dir = mk3(0.0f), att = mk3(0.0f);
+            bool is_specular = false;
+            if (!material_scatter<FULL>(hit, mat, rd, rng, scatter_dir, att, is_specular, last, F)) {
                 end_path = true;
             } else {
                 prev_was_specular = is_specular;

@@ -346,7 +346,7 @@ template <bool FULL> PT_DEV void wf_shade_path(const KParams &K, const WfParams 
                             const LightRec light = load_light(K.lights, pick_light(rng, K.n_lights));
                             f3 L, light_scale, shadow_o, c;
                             float pdf_sample, light_att, shadow_tmax;
-                            sample_light(light, K.n_lights, hit, rng, L, pdf_sample, light_scale, light_att, shadow_o, shadow_tmax);
+                            sample_light(light, K.inv_n_lights, hit, rng, L, pdf_sample, light_scale, light_att, shadow_o, shadow_tmax);
                             want_shadow = true;
                             ++n_shadow;
                             // what an unoccluded light sample adds; kept until the shadow ray has been traced

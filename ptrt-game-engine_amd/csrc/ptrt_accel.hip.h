@@ -388,6 +388,8 @@ void free_scene(ptrt_ctx *c) {
     dfree(c->d_nodes);
     dfree(c->d_nodes2);
     dfree(c->d_tris);
+    dfree(c->d_tri_frames);
+    c->tri_frames_ok = false;
     dfree(c->d_tlas_nodes);
     dfree(c->d_leaves);
     dfree(c->d_tlas_leaves);
@@ -630,7 +632,7 @@ int refit_tlas_entry(ptrt_ctx *c, const char *who, bool reorder) {
         return rc;
     if (!c->inst_c2_all)
         set_inst_c2(c, host_inst_c2(c));
-    c->plain_leaf_ok = false; // (the device rewrites the TLAS root box)
+    c->plain_leaf_ok = c->tri_frames_ok = false; // (the device rewrites the TLAS root box)
     if (int rc = deal ? run_graphed(c, GK_REORDER_TLAS, [c](hipStream_t st) { return enqueue_reorder_tlas(c, st); })
                       : run_graphed(c, GK_REFIT_TLAS, [c](hipStream_t st) { return enqueue_refit_tlas(c, st); }))
         return rc;
@@ -843,9 +845,11 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
     put(c->d_tris, R.tris);
     if (failed)
         return failed;
-    if (!R.tris.empty()) { // the packets' geometric normals, by the same device code a repack uses (pt::packet_normal)
+    if (!R.tris.empty()) { // the packets' geometric normals, by the same device code a repack uses (pt::packet_normal), and with
+                           // them the tangent frames of both shading normals of every triangle (option "tri_frames")
         const int n = (int)(R.tris.size() / 3);
-        hipLaunchKernelGGL(pt::tri_normals_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_tris, n);
+        HIP_TRY(c, hipMalloc((void **)&c->d_tri_frames, (size_t)n * pt::TRI_FRAME_F4 * sizeof(float4)));
+        hipLaunchKernelGGL(pt::tri_normals_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_tris, c->d_tri_frames, n);
         HIP_TRY(c, hipGetLastError());
     }
     if (int rc = upload_tlas(c, mesh_count, tlas_nodes, tlas_node_count, tlas_mesh_indices, tlas_index_count, false))
@@ -870,6 +874,10 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
     c->pm1_plan_ok = c->pair_leaf_uniform && pt::pm1_build_plan(c->pair_max_leaf, &c->pm1_plan);
     // (from the descriptors' fp32 values, which are the ones that went up: rec[0..1] of a mesh, node 0 of the TLAS)
     c->plain_leaf_ok = pt::plain_leaf_scene(meshes, mesh_count, tlas_nodes, tlas_node_count, tlas_mesh_indices, tlas_index_count);
+    // the frames stand while the packets' normals do and a shading normal is one of them: no mesh with a transform.  A refit or
+    // rebuild writes new normals and no frames (a scene that refits every frame would pay for a table it reads once); whatever
+    // clears plain_leaf_ok clears this too, until the next full upload.
+    c->tri_frames_ok = c->d_tri_frames != nullptr && !c->any_transform;
     if (int rc = upload_instance_pretests(c, meshes, mesh_count))
         return rc;
     c->have_geometry = true;
@@ -892,7 +900,7 @@ int ptrt_update_instances(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_co
     if (int rc = upload_tlas(c, mesh_count, tlas_nodes, tlas_node_count, tlas_mesh_indices, tlas_index_count, true))
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // frames in flight still read the old records
-    c->plain_leaf_ok = false; // (a new root box over mesh boxes only the device may know: derived again by the next full upload)
+    c->plain_leaf_ok = c->tri_frames_ok = false; // (a new root box over mesh boxes only the device may know: derived again by the next full upload)
     c->any_transform = false;
     c->xf_host_stale = false; // (every mesh's flag bit and matrices are rewritten below, on both sides)
     for (int m = 0; m < mesh_count; ++m) {
@@ -1011,7 +1019,7 @@ int ptrt_set_instance_transforms_device(ptrt_ctx *c, int first_mesh, int count, 
         return rc;
     c->xf_host_stale = true;
     c->any_transform = true;
-    c->plain_leaf_ok = false;
+    c->plain_leaf_ok = c->tri_frames_ok = false;
     c->inst_pre_ok = false; // the first-pass boxes follow with the next ptrt_refit_tlas / ptrt_reorder_tlas
     hipLaunchKernelGGL(pt::scatter_xforms_kernel, dim3((count * 37 + 255) / 256), dim3(256), 0, c->stream,
                        reinterpret_cast<const float *>(d_xf), abi, c->d_mesh_recs, first_mesh, count);
@@ -1041,7 +1049,7 @@ int ptrt_set_instance_poses_device(ptrt_ctx *c, int first_mesh, int count, const
                     c->device);
     c->xf_host_stale = true;
     c->any_transform = true;
-    c->plain_leaf_ok = false;
+    c->plain_leaf_ok = c->tri_frames_ok = false;
     c->inst_pre_ok = false; // the first-pass boxes follow with the next ptrt_refit_tlas / ptrt_reorder_tlas
     hipLaunchKernelGGL(pt::compose_poses_kernel, dim3((count + pt::POSE_BLOCK - 1) / pt::POSE_BLOCK), dim3(pt::POSE_BLOCK), 0, c->stream,
                        reinterpret_cast<const float *>(d_pose), c->d_mesh_recs, first_mesh, count);
@@ -1215,7 +1223,7 @@ int ptrt_refit(ptrt_ctx *c) {
     if (int rc = set_device(c))
         return rc;
     c->inst_pre_ok = false; // root boxes move on the device: the instances' first-pass boxes are stale until the next upload
-    c->plain_leaf_ok = false; // ... and nobody has compared them with the root box (plain_leaf.h)
+    c->plain_leaf_ok = c->tri_frames_ok = false; // ... and nobody has compared them with the root box (plain_leaf.h)
     return run_graphed(c, GK_REFIT, [c](hipStream_t st) { return enqueue_refit(c, st); });
 }
 
@@ -1224,7 +1232,7 @@ int ptrt_build_bvh(ptrt_ctx *c, int mesh) {
         return rc;
     // (as in ptrt_refit -- but ahead of the mesh check: a call refused for its mesh index still marks the boxes stale)
     c->inst_pre_ok = false;
-    c->plain_leaf_ok = false;
+    c->plain_leaf_ok = c->tri_frames_ok = false;
     if (mesh < 0 || mesh >= c->n_meshes)
         return fail(c, PTRT_E_INVALID, "ptrt_build_bvh: no mesh %d", mesh);
     if (!c->mesh_rebuildable[mesh])

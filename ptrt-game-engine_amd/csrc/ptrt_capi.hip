@@ -143,6 +143,10 @@ struct ptrt_ctx {
     // single-leaf TLAS, no instanced mesh, every mesh box inside the root box (plain_leaf.h): derived by a full upload, cleared by
     // whatever moves a box or sets a transform without the host seeing the result
     bool plain_leaf_ok = false;
+    // per leaf slot the tangent frames of orthoBasis(gn) and orthoBasis(-gn) (pt::tri_normals_kernel), written by a full upload;
+    // tri_frames_ok: they match the packets' normals and no mesh has a transform -- set there, cleared with plain_leaf_ok
+    float4 *d_tri_frames = nullptr;
+    bool tri_frames_ok = false;
     int tlas_max_leaf = 0, tlas_depth = 0;
     bool have_geometry = false, have_materials = false;
 
@@ -209,6 +213,8 @@ struct ptrt_ctx {
     int pm1_lane_groups_eff = 0;     // ... the last frame or ray query (0 as well when another traversal mode ran it)
     int plain_leaf = -1;             // option "plain_leaf": -1 (default) and 1: on where the upload derived it (plain_leaf_ok), 0 never (make_params)
     int plain_leaf_eff = 0;          // ... the last frame or query (0 as well when a traversal mode without the pair builder ran it)
+    int tri_frames = -1;             // option "tri_frames": -1 (default) and 1: PMODE 1 reads to_world's frame from d_tri_frames where tri_frames_ok, 0 never (plan_frame)
+    int tri_frames_eff = 0;          // ... the last frame
     int tile_run = 8;                // option "tile_run": of every 8 * run consecutive tiles XCD x renders a run of neighbours (path_trace_kernel); 0: tile k on workgroup k
     int ticket_tiles = 1;            // option "ticket_tiles": consecutive tiles per ticket of the queue
     int persist = 0, n_cus = 0;      // option "persist": persistent waves per CU (0 = the variant's occupancy): lane refill and the radiance query
@@ -436,6 +442,7 @@ pt::KParams make_params(ptrt_ctx *c) {
     K.tlas_root_ref = c->tlas_root_ref;
     K.n_meshes = c->n_meshes;
     K.n_lights = c->n_lights;
+    K.inv_n_lights = c->n_lights > 0 ? 1.0f / (float)c->n_lights : 0.0f;
     K.stack_entries = c->stack_entries;
     K.pair_meshes = c->pair_meshes;
     K.pair_tri_slots = c->pair_tri_slots;

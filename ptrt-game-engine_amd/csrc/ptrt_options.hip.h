@@ -66,6 +66,7 @@ const Option OPTIONS[] = {
     {"pm1_full_leaf", &ptrt_ctx::pm1_full_leaf, OPT_TRISTATE}, // PMODE 1: triangle loops without partial-leaf handling when every leaf is full (0: never)
     {"pm1_lane_groups", &ptrt_ctx::pm1_lane_groups, OPT_TRISTATE}, // PMODE 1: a pair-list tail's lanes per pair from the leaf's divisors, by the upload's plan (0: the 2^sh rule)
     {"plain_leaf", &ptrt_ctx::plain_leaf, OPT_TRISTATE}, // PMODE 1, 2: no TLAS root test, no instance arithmetic per pair batch, where the upload found the leaf plain (0: never; 1 does not force it)
+    {"tri_frames", &ptrt_ctx::tri_frames, OPT_TRISTATE}, // PMODE 1 megakernel: to_world's tangent frame from the per-triangle table where the upload's normals stand and no mesh has a transform (0: never; 1 does not force it)
     {"tile_run", &ptrt_ctx::tile_run, OPT_REJECT, 0, 64}, // 0 (tile k on workgroup k) or the tiles per XCD and run, 1..64
     {"ticket_tiles", &ptrt_ctx::ticket_tiles, OPT_CLAMP, 1, 16},
     {"refill", &ptrt_ctx::refill, OPT_CLAMP, 0, 2},
@@ -90,6 +91,7 @@ const Option OPTIONS[] = {
     {"pm1_full_leaf_eff", &ptrt_ctx::pm1_full_leaf_eff, OPT_READ_ONLY},
     {"pm1_lane_groups_eff", &ptrt_ctx::pm1_lane_groups_eff, OPT_READ_ONLY}, // ... of the last frame or ray query, whichever came last
     {"plain_leaf_eff", &ptrt_ctx::plain_leaf_eff, OPT_READ_ONLY}, // ... of the last frame or query, whichever came last
+    {"tri_frames_eff", &ptrt_ctx::tri_frames_eff, OPT_READ_ONLY}, // ... of the last frame
     {"refilled", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->refill_eff ? 1 : 0; }},
     {"split_eff", &ptrt_ctx::split_eff, OPT_READ_ONLY},
     {"pipelined", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->pipelined_last ? 1 : 0; }},
@@ -244,10 +246,19 @@ int ptrt_debug_sqrt_check(ptrt_ctx *c, unsigned int *out9) {
 }
 
 // test hook: div3's core for the divisors 1.m, m in [first, first + count), against every numerator significand (mode 0), or
-// div3 with out-of-range exponents (modes 1, 2); out9[0] = mismatches, out9[1..8] = first offending {a, t} bit patterns
+// div3 with out-of-range exponents (modes 1, 2); out9[0] = mismatches, out9[1..8] = first offending {a, t} bit patterns.
+// Two more checks of reciprocals ride on this entry point (the exported names are pinned): mode 4, neg_rcp_ieee against
+// `-1.0f / y` for all 2^32 inputs (first, count unused; out9 as ptrt_debug_rcp_check); mode 5, orthoBasis against its text
+// with the compiler's divisions over `count` normals from the seed `first` (out9: pt::orthoBasis_check_kernel)
 int ptrt_debug_div3_check(ptrt_ctx *c, unsigned int first, unsigned int count, int mode, unsigned int *out9) {
-    if (!ctx_live(c) || !out9 || count == 0 || count > (1u << 23) || mode < 0 || mode > 3)
+    if (!ctx_live(c) || !out9 || count == 0 || count > (1u << 23) || mode < 0 || mode > 5)
         return fail(c, PTRT_E_INVALID, "ptrt_debug_div3_check: bad argument");
+    if (mode == 4)
+        return run_check(c, out9, [c](unsigned int *d) { hipLaunchKernelGGL(pt::neg_rcp_check_kernel, dim3(4096), dim3(256), 0, c->stream, d); });
+    if (mode == 5)
+        return run_check(c, out9, [=](unsigned int *d) {
+            hipLaunchKernelGGL(pt::orthoBasis_check_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, first, count, d);
+        });
     return run_check(c, out9, [=](unsigned int *d) {
         hipLaunchKernelGGL(pt::div3_check_kernel, dim3((count + 63) / 64), dim3(64), 0, c->stream, first, count, mode, d);
     });

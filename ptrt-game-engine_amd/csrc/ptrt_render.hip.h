@@ -509,6 +509,10 @@ int plan_frame(ptrt_ctx *c, pt::KParams &K, int spp, int max_depth, FramePlan &P
               : pmode == 1 && P.pm1_wg == 2                       ? FramePlan::PM1_WG2
               : pmode == 2 && c->lds_nodes && c->stack_entries > 0 ? FramePlan::LDS_NODES
                                                                   : FramePlan::TILES;
+    // to_world's frame from the per-triangle table: PMODE 1's megakernel alone (K.tri_frames is null out of make_params)
+    if (pmode == 1 && (P.shape == FramePlan::TILES || P.shape == FramePlan::PM1_WG2) && c->tri_frames != 0 && c->tri_frames_ok && !c->any_transform)
+        K.tri_frames = c->d_tri_frames;
+    c->tri_frames_eff = K.tri_frames ? 1 : 0;
     switch (P.shape) {
     case FramePlan::ASYNC: P.lds = async_lds_bytes(c); break;
     case FramePlan::WAVEFRONT: P.lds = wavefront_lds_bytes(c); break;
