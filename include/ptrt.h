@@ -187,6 +187,14 @@ typedef struct ptrt_direct {
     float reserved[3];        /* 0.0f                                                                     */
 } ptrt_direct;
 
+/* One texel of a lightmap atlas from ptrt_atlas_texels, 32 bytes. */
+typedef struct ptrt_atlas_texel {
+    float position[3];  /* world                                                                        */
+    int32_t face;       /* mesh-local face index; unspecified where mesh < 0                             */
+    float normal[3];    /* world, unit, the FRONT side: the side cross(e1, e2) points to                 */
+    int32_t mesh;       /* uploaded mesh index, -1 = no triangle covers this texel's centre              */
+} ptrt_atlas_texel;
+
 /* Per-frame counters of the trace stage (Mrays/s numerator). */
 typedef struct ptrt_stats {
     uint64_t extension_rays; /* traceRay calls   (intersection.cuh:526) */
@@ -724,6 +732,50 @@ int ptrt_query_direct(ptrt_ctx *ctx, const float *d_positions, const float *d_no
                       const float *d_samples2, int n_shadow, const float *d_phases /* may be NULL */, float offset,
                       int light_first, int light_count, ptrt_direct *d_out);
 
+/* The front of a lightmap bake: the UV charts of uploaded mesh `mesh_index` rasterised into an atlas of atlas_w x atlas_h
+ * records in DEVICE memory -- the texels whose positions and normals ptrt_query_irradiance and ptrt_query_direct take.  d_uv
+ * holds face_count * 6 floats on the device: the (x, y) of corners v0, v1, v2 of face f, in the face's own corner order, in
+ * TEXEL units.  Texel (i, j) is record j * atlas_w + i and its centre is ((float)i + 0.5f, (float)j + 0.5f).
+ * Coverage and barycentrics are one definition in fp32, every operation rounded on its own, `/` the IEEE quotient:
+ *     d1 = (x1-x0, y1-y0)   d2 = (x2-x0, y2-y0)   q = (px-x0, py-y0)        A = d1x*d2y - d1y*d2x
+ *     b1 = (qx*d2y - qy*d2x) / A      b2 = (d1x*qy - d1y*qx) / A      b0 = (1 - b1) - b2
+ *     covered  <=>  b0 >= 0 && b1 >= 0 && b2 >= 0
+ * so both windings work (the quotients carry A's sign), edges are inclusive and a NaN fails.  A face with a non-finite corner,
+ * A == 0 or A NaN covers nothing; corners far outside the atlas (+-1e30) are legal.  The centres tested for a face are those of
+ * columns max(floor(min x) - 1, 0) .. min(ceil(max x), atlas_w - 1) and the rows alike -- every centre inside the triangle's
+ * bounds, with a texel to spare.  A covered texel's record: position = the local point (v0 + b1*e1) + b2*e2 per component from
+ * the face's uploaded triangle (e1 = v1 - v0, e2 = v2 - v0 as the upload subtracted them, or as the last refit / rebuild
+ * repacked them), through the mesh's world matrix if it has a transform; normal = the triangle's stored geometric normal,
+ * normalize(cross(e1, e2)), with a transform normalize(normal matrix * it) -- what a front-face hit of ptrt_query_rays reports;
+ * face = f; mesh = mesh_index.  tests/atlas_restatement.py states all of it in numpy.
+ * Ownership is a contract: within one call the LOWEST face index covering a centre owns the texel, whatever the leaf order
+ * (ptrt_build_bvh), the grid (option "persist") or the lanes per triangle (option "atlas_lanes").  clear != 0: every record
+ * starts empty (mesh -1, position and normal 0).  clear == 0: d_texels holds records of earlier calls; a texel with
+ * mesh >= 0 is kept whole -- earlier calls win, which is how several meshes share an atlas -- and the others are filled as
+ * above.  A face that is in no leaf slot of its BVH is not rasterised (no ray can hit it either); a face in several slots
+ * gives the same record.
+ * Three launches on the context's stream -- prime the records, an atomic minimum of the face index per covered texel, the
+ * winners' records behind the kernel boundary -- on a persistent grid over the mesh's leaf slots (option "persist" sizes it),
+ * `atlas_lanes` lanes to a triangle's texel range; no allocation, copy or synchronisation; ordered like ptrt_query_rays,
+ * behind uploads, refits, rebuilds and instance updates, and it leaves generator states, frame buffers, counters and timing
+ * histories alone.  PTRT_E_INVALID (nothing enqueued, d_texels untouched) for a mesh_index outside the uploaded meshes,
+ * atlas_w or atlas_h < 1 or a product above 2^28, a NULL pointer, d_texels not 16-byte or d_uv not 4-byte aligned, memory that
+ * is not the context's device memory or an allocation too small; PTRT_E_NOT_READY before geometry is uploaded.
+ * (ABI 6, addition only.) */
+int ptrt_atlas_texels(ptrt_ctx *ctx, int mesh_index, const float *d_uv, int atlas_w, int atlas_h, int clear,
+                      ptrt_atlas_texel *d_texels);
+
+/* The tail of a bake: `passes` dilation passes over an atlas of float4 {r, g, b, valid} texels in DEVICE memory, d_a -> d_b ->
+ * d_a ..; the result is in d_b for an odd `passes`, in d_a for an even one (the other buffer holds the pass before).  A texel
+ * is valid when valid != 0.  One pass: a valid texel is copied; an invalid texel with n > 0 valid 8-neighbours inside the
+ * atlas becomes the sum of their rgb -- from 0.0f, in the order (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1), fp32,
+ * each sum rounded -- divided by (float)n, with valid = 1.0f; an invalid texel with no valid neighbour is copied as it is.  A
+ * pass reads only its source, so a texel filled in pass k counts as valid from pass k + 1 on.  One launch per pass on the
+ * context's stream, 16-byte loads and stores, no allocation, copy or synchronisation; side effects as ptrt_atlas_texels.
+ * PTRT_E_INVALID (nothing enqueued) for passes outside 1 .. 64, atlas sizes as above, a NULL or not 16-byte aligned pointer,
+ * buffers that overlap, memory that is not the context's device memory or too small.  Needs no scene.  (ABI 6, addition only.) */
+int ptrt_atlas_dilate(ptrt_ctx *ctx, float *d_a, float *d_b, int atlas_w, int atlas_h, int passes);
+
 /* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
  * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small
  * kernel on the context's stream into DEVICE memory: rows*W*3 floats each (render_w*render_h*3 at a reduced render size),
@@ -919,6 +971,10 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         refit writes new normals and no frames, so a scene that refits every frame keeps computing them.
  *                         ptrt_get_option "tri_frames_eff" says what the last frame did.  Travels with a launch's arguments as
  *                         plain_leaf does.
+ *   atlas_lanes -1|1|4|16|64   ptrt_atlas_texels: the lanes that share one triangle's texel range (a wave takes 64 / lanes leaf
+ *                         slots at a time).  -1 (default): chosen on the host from atlas texels / faces of the mesh (DESIGN.md
+ *                         3.28); anything else is PTRT_E_INVALID.  Same bytes under every value.  ptrt_get_option
+ *                         "atlas_lanes_eff" says what the last ptrt_atlas_texels ran (0: none yet).
  *   tile_run 0..64        the one-tile-per-workgroup kernels' workgroup -> tile map.  Consecutive workgroups go to the eight XCDs in
  *                         turn; with n > 0, of every 8 n consecutive tiles XCD x renders tiles [x n, (x + 1) n) -- neighbours,
  *                         whose rays walk the same part of the trees, share an L2 -- instead of every eighth tile.  8 (default):

@@ -22,6 +22,7 @@
 #include "pt_probe.hip.h"
 #include "pt_irradiance.hip.h"
 #include "pt_direct.hip.h"
+#include "pt_atlas.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -260,6 +261,8 @@ struct ptrt_ctx {
     unsigned long long tune_key = ~0ull, tune_launch[2 * TUNE_SAMPLES] = {};
     int last_pmode = 0;                  // PMODE of the last megakernel launch (ptrt_get_option "pmode")
     int query_pmode = -1;                // traversal of the last ray query (ptrt_get_option "query_pmode"; -1 none yet)
+    int atlas_lanes = -1;                // option "atlas_lanes": lanes per triangle of ptrt_atlas_texels, 1 / 4 / 16 / 64, or -1: by the texels per face
+    int atlas_lanes_eff = 0;             // ... of the last ptrt_atlas_texels (0 none yet)
     bool last_merged_possible = false;   // ... and whether that scene has the two loop shapes to choose from
     bool timed = false;
     bool prev_post = false;              // the previous frame had a denoiser / bloom chain behind its trace (ptrt_render "pipeline")

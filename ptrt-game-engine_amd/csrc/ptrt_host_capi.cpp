@@ -449,6 +449,16 @@ int hs_direct_rays(void *s, const void *d_positions, const void *d_normals, int 
                                                static_cast<float *>(d_dirs), static_cast<float *>(d_tmax), static_cast<float *>(d_weights)));
     return 0;
 }
+int hs_atlas_texels(void *s, int mesh, const void *d_uv, int atlas_w, int atlas_h, int clear, void *d_texels) {
+    HS_TRY(static_cast<Scene *>(s)->atlasTexels((size_t)mesh, static_cast<const float *>(d_uv), atlas_w, atlas_h, clear != 0,
+                                                static_cast<ptrt_atlas_texel *>(d_texels)));
+    return 0;
+}
+// 0: the result is in d_a; 1: in d_b
+int hs_atlas_dilate(void *s, void *d_a, void *d_b, int atlas_w, int atlas_h, int passes) {
+    HS_TRY(return static_cast<Scene *>(s)->atlasDilate(static_cast<float *>(d_a), static_cast<float *>(d_b), atlas_w, atlas_h, passes) == d_b
+                      ? 1 : 0);
+}
 int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
     HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;

@@ -27,6 +27,7 @@ enum OptPolicy {
     OPT_MASK,      // value & hi
     OPT_TRISTATE,  // negative -> -1 (choose), else 0 / 1
     OPT_SNAP_124,  // <= 0 -> 0, else the largest of 1, 2, 4 not above it
+    OPT_LANES,     // -1 (choose) or a power of four up to 64 -- 1, 4, 16, 64; PTRT_E_INVALID otherwise
 };
 
 // One row per name: both entry points walk this table.  `field` is where the value lives; the few entries that are computed
@@ -85,6 +86,7 @@ const Option OPTIONS[] = {
     {"denoiser_active", &ptrt_ctx::dn_active, OPT_BOOL}, // perfSettings.enableDenoiser: use the (already allocated) denoiser or not
     {"motion_vectors", &ptrt_ctx::mv_active, OPT_BOOL}, // perfSettings.enableMotionVectors
     {"use_graphs", &ptrt_ctx::use_graphs, OPT_BOOL}, // 0: issue the refit / rebuild launches one by one instead of replaying a hipGraph
+    {"atlas_lanes", &ptrt_ctx::atlas_lanes, OPT_LANES}, // ptrt_atlas_texels: lanes that share one triangle's texel range (-1: from atlas texels per face)
     // read-only facts about the last ptrt_render (so that a measurement can say what ran)
     {"sample_sync_eff", &ptrt_ctx::sample_sync_eff, OPT_READ_ONLY},
     {"pm1_dense_roots_eff", &ptrt_ctx::pm1_dense_roots_eff, OPT_READ_ONLY},
@@ -92,6 +94,7 @@ const Option OPTIONS[] = {
     {"pm1_lane_groups_eff", &ptrt_ctx::pm1_lane_groups_eff, OPT_READ_ONLY}, // ... of the last frame or ray query, whichever came last
     {"plain_leaf_eff", &ptrt_ctx::plain_leaf_eff, OPT_READ_ONLY}, // ... of the last frame or query, whichever came last
     {"tri_frames_eff", &ptrt_ctx::tri_frames_eff, OPT_READ_ONLY}, // ... of the last frame
+    {"atlas_lanes_eff", &ptrt_ctx::atlas_lanes_eff, OPT_READ_ONLY}, // ... of the last ptrt_atlas_texels: 1, 4, 16 or 64 (0: none yet)
     {"refilled", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->refill_eff ? 1 : 0; }},
     {"split_eff", &ptrt_ctx::split_eff, OPT_READ_ONLY},
     {"pipelined", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->pipelined_last ? 1 : 0; }},
@@ -139,6 +142,10 @@ int ptrt_set_option(ptrt_ctx *c, const char *name, long long value) {
     case OPT_MASK: v = value & o->hi; break;
     case OPT_TRISTATE: v = value < 0 ? -1 : (value ? 1 : 0); break;
     case OPT_SNAP_124: v = value <= 0 ? 0 : (value >= 4 ? 4 : (value >= 2 ? 2 : 1)); break;
+    case OPT_LANES:
+        if (value != -1 && value != 1 && value != 4 && value != 16 && value != 64)
+            return fail(c, PTRT_E_INVALID, "%s must be -1, 1, 4, 16 or 64", name);
+        break;
     case OPT_READ_ONLY: break;
     }
     if (o->set)

@@ -1,6 +1,7 @@
 // ptrt_query.hip.h -- the device queries of the C ABI: closest hit and occlusion (ptrt_trace_rays, ptrt_query_rays), path-traced
 // radiance (ptrt_query_radiance), light probes (ptrt_query_probes), lightmap texels (ptrt_query_irradiance, with
-// ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
+// ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights), the lightmap
+// atlas around them (ptrt_atlas_texels, ptrt_atlas_dilate: no traversal) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
 // ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
 // (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
 // check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
@@ -428,6 +429,97 @@ int ptrt_query_direct(ptrt_ctx *c, const float *d_positions, const float *d_norm
         return launch_persistent(c, pt::direct_query_kernel<G, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels, d_samples2,
                                  n_shadow, d_phases, offset, light_first, (int)S.terms, o);
     });
+}
+
+} // extern "C"
+
+namespace {
+
+// What ptrt_atlas_texels and ptrt_atlas_dilate ask of an atlas: at least one texel each way, at most 2^28 in all (a texel
+// number fits an int with room for the kernels' index arithmetic).
+constexpr long long ATLAS_MAX_TEXELS = 1ll << 28;
+bool atlas_size_ok(int atlas_w, int atlas_h) { return atlas_w >= 1 && atlas_h >= 1 && (long long)atlas_w * atlas_h <= ATLAS_MAX_TEXELS; }
+bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// Lanes per triangle when option "atlas_lanes" is -1, from the only estimate of a face's texels the host has (the atlas's
+// texels over the mesh's faces).  Measured on an MI355X (profiles/atlas_time.json): 64 lanes were the fastest
+// or tied in every bucket from 14 to 1.4 M texels per face; at 14 the call is three launch latencies under 16 and 64 alike,
+// and below that a scan range has fewer texels than a wave has lanes.
+int atlas_auto_lanes(long long texels, int faces) {
+    const long long per_face = texels / (faces > 0 ? faces : 1);
+    return per_face < 16 ? 16 : 64;
+}
+
+} // namespace
+
+extern "C" {
+
+int ptrt_atlas_texels(ptrt_ctx *c, int mesh_index, const float *d_uv, int atlas_w, int atlas_h, int clear, ptrt_atlas_texel *d_texels) {
+    static_assert(sizeof(pt::AtlasTexel) == sizeof(ptrt_atlas_texel) && sizeof(ptrt_atlas_texel) == 32, "AtlasTexel must mirror ptrt_atlas_texel");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_texels: bad context");
+    if (!d_uv || !d_texels || !atlas_size_ok(atlas_w, atlas_h))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_texels: bad argument (uv %p, texels %p, atlas %d x %d: 1 x 1 .. 2^28 texels)",
+                    (const void *)d_uv, (const void *)d_texels, atlas_w, atlas_h);
+    if (!aligned16(d_texels) || ((uintptr_t)d_uv & 3u))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_texels: texels %p must be 16-byte aligned, uv %p 4-byte", (const void *)d_texels,
+                    (const void *)d_uv);
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_atlas_texels: geometry not uploaded");
+    if (mesh_index < 0 || mesh_index >= c->n_meshes)
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_texels: mesh %d of %d uploaded", mesh_index, c->n_meshes);
+    if (int rc = set_device(c))
+        return rc;
+    const size_t texels = (size_t)atlas_w * (size_t)atlas_h;
+    const int faces = c->mesh_face_count[(size_t)mesh_index], slots = c->mesh_slot_count[(size_t)mesh_index];
+    if (int rc = check_spans(c, "ptrt_atlas_texels", {{"uv", d_uv, (size_t)faces * 24}, {"texels", d_texels, texels * sizeof(ptrt_atlas_texel)}}))
+        return rc;
+    c->touched = true;
+    const int g = c->atlas_lanes > 0 ? c->atlas_lanes : atlas_auto_lanes((long long)texels, faces);
+    const int log2g = g == 64 ? 6 : g == 16 ? 4 : g == 4 ? 2 : 0;
+    c->atlas_lanes_eff = 1 << log2g;
+    pt::AtlasTexel *t = reinterpret_cast<pt::AtlasTexel *>(d_texels);
+    hipLaunchKernelGGL(pt::atlas_prime_kernel, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, c->stream, t, (uint32_t)texels,
+                       clear ? 1 : 0);
+    HIP_TRY(c, hipGetLastError());
+    if (slots <= 0)
+        return PTRT_OK;
+    // atlas_raster_kernel (pt_atlas.hip.h) twice over units of 64 / g leaf slots: the minimum face per texel, then -- behind
+    // the kernel boundary -- the winners' records
+    const size_t per = (size_t)(64 >> log2g), units = ((size_t)slots + per - 1) / per;
+    const float4 *rec = c->d_mesh_recs + (size_t)mesh_index * pt::MESH_REC_F4;
+    const int base = c->mesh_slot_base[(size_t)mesh_index];
+    if (int rc = launch_persistent(c, pt::atlas_raster_kernel<1>, 0, units, true, (const float4 *)c->d_tris, (const int4 *)c->d_slot_face, rec,
+                                   base, slots, mesh_index, d_uv, atlas_w, atlas_h, log2g, t))
+        return rc;
+    return launch_persistent(c, pt::atlas_raster_kernel<2>, 0, units, true, (const float4 *)c->d_tris, (const int4 *)c->d_slot_face, rec, base,
+                             slots, mesh_index, d_uv, atlas_w, atlas_h, log2g, t);
+}
+
+int ptrt_atlas_dilate(ptrt_ctx *c, float *d_a, float *d_b, int atlas_w, int atlas_h, int passes) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_dilate: bad context");
+    if (!d_a || !d_b || !atlas_size_ok(atlas_w, atlas_h) || passes < 1 || passes > 64)
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_dilate: bad argument (a %p, b %p, atlas %d x %d: 1 x 1 .. 2^28 texels, passes %d: 1 .. 64)",
+                    (const void *)d_a, (const void *)d_b, atlas_w, atlas_h, passes);
+    const size_t bytes = (size_t)atlas_w * (size_t)atlas_h * 16;
+    const uintptr_t a = (uintptr_t)d_a, b = (uintptr_t)d_b;
+    if (!aligned16(d_a) || !aligned16(d_b) || (a < b ? b - a : a - b) < bytes)
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_dilate: a %p and b %p must be 16-byte aligned and %zu bytes apart", (const void *)d_a,
+                    (const void *)d_b, bytes);
+    if (int rc = set_device(c))
+        return rc;
+    if (int rc = check_spans(c, "ptrt_atlas_dilate", {{"a", d_a, bytes}, {"b", d_b, bytes}}))
+        return rc;
+    c->touched = true;
+    // atlas_dilate_kernel (pt_atlas.hip.h): a -> b -> a ..., one launch per pass
+    float4 *buf[2] = {reinterpret_cast<float4 *>(d_a), reinterpret_cast<float4 *>(d_b)};
+    for (int p = 0; p < passes; ++p) {
+        hipLaunchKernelGGL(pt::atlas_dilate_kernel, dim3((unsigned)((bytes / 16 + 255) / 256)), dim3(256), 0, c->stream,
+                           (const float4 *)buf[p & 1], buf[(p & 1) ^ 1], atlas_w, atlas_h);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return PTRT_OK;
 }
 
 int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins, float *d_directions) {

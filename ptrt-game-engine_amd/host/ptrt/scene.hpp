@@ -998,6 +998,24 @@ class Scene {
                                light_count < 0 ? (int)lights.size() - light_first : light_count, d_origins, d_dirs, d_tmax, d_weights),
               "Direct rays failed");
     }
+    // A mesh's UV charts rasterised to lightmap texels (ptrt_atlas_texels): d_uv holds the (x, y) of the three corners of every
+    // face of mesh `mesh` in texel units (faces * 6 floats), d_texels gets atlas_w * atlas_h 32-byte ptrt_atlas_texel -- world
+    // position, geometric normal, owning face, mesh -- for the texel centres some face covers, the lowest face winning;
+    // `clear` false keeps what earlier calls put there (several meshes in one atlas).  `mesh` is this scene's mesh id; the
+    // record of what the device holds (Resident) says which uploaded mesh that is.  Commits what queryClosestDevice commits.
+    void atlasTexels(size_t mesh, const float *d_uv, int atlas_w, int atlas_h, bool clear, ptrt_atlas_texel *d_texels) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_atlas_texels(ctx, residentIndex(mesh, "atlasTexels"), d_uv, atlas_w, atlas_h, clear ? 1 : 0, d_texels),
+              "Atlas rasterisation failed");
+    }
+    // `passes` dilation passes over an atlas of float4 {r, g, b, valid} (ptrt_atlas_dilate), d_a -> d_b -> d_a ..: invalid
+    // texels take the mean of their valid 8-neighbours.  Returns the buffer that holds the result.  Needs no scene.
+    float *atlasDilate(float *d_a, float *d_b, int atlas_w, int atlas_h, int passes) {
+        needBackend();
+        check(ptrt_atlas_dilate(ctx, d_a, d_b, atlas_w, atlas_h, passes), "Atlas dilation failed");
+        return (passes & 1) ? d_b : d_a;
+    }
     // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
     // tile rows * width * 3 floats each, in the order of the colour buffer.
     void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {
@@ -1131,6 +1149,13 @@ class Scene {
         void mark(HostTree t) { hostTree = t > hostTree ? t : hostTree; }
     };
     std::vector<Resident> resident;
+    // the uploaded index of this scene's mesh `mesh`: meshes are uploaded in the scene's order, one Resident record each
+    int residentIndex(size_t mesh, const char *who) const {
+        if (mesh >= resident.size() || mesh >= meshes.size() || resident[mesh].faceCount != meshes[mesh]->faces.size())
+            throw std::runtime_error(std::string(who) + ": mesh " + std::to_string(mesh) + " is not on the device (" +
+                                     std::to_string(resident.size()) + " uploaded)");
+        return (int)mesh;
+    }
     // the same for the TLAS: the device refitted it (ptrt_refit_tlas) over root boxes the host has not followed yet, or
     // re-ordered it as well (ptrt_reorder_tlas: the index array is read back with the boxes)
     enum class HostTlas : unsigned char { Current, BoxesStale, OrderStale };

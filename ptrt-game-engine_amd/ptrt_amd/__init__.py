@@ -135,6 +135,11 @@ class Direct(C.Structure):
                 ("reserved", C.c_float * 3)]
 
 
+class AtlasTexel(C.Structure):
+    """`ptrt_atlas_texel`: one texel of a lightmap atlas from ptrt_atlas_texels."""
+    _fields_ = [("position", C.c_float * 3), ("face", C.c_int32), ("normal", C.c_float * 3), ("mesh", C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64),
                 ("shadow_rays_walked", C.c_uint64)]
@@ -173,6 +178,8 @@ IRRADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("mean_distance", "<f4"), (
 assert IRRADIANCE_DTYPE.itemsize == C.sizeof(Irradiance) == 32
 DIRECT_DTYPE = np.dtype([("irradiance", "<f4", 3), ("lit_fraction", "<f4"), ("shadowed_fraction", "<f4"), ("reserved", "<f4", 3)])
 assert DIRECT_DTYPE.itemsize == C.sizeof(Direct) == 32
+ATLAS_TEXEL_DTYPE = np.dtype([("position", "<f4", 3), ("face", "<i4"), ("normal", "<f4", 3), ("mesh", "<i4")])
+assert ATLAS_TEXEL_DTYPE.itemsize == C.sizeof(AtlasTexel) == 32
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
@@ -218,6 +225,8 @@ _sig("ptrt_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp,
 _sig("ptrt_query_irradiance", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("ptrt_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
 _sig("ptrt_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp)
+_sig("ptrt_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("ptrt_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
@@ -350,6 +359,8 @@ _sig("hs_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C
 _sig("hs_light_count", C.c_int, _vp)
 _sig("hs_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp)
 _sig("hs_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
+_sig("hs_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("hs_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -481,6 +492,22 @@ def direct_fields(records):
     for name, (a, b) in DIRECT_COLUMNS.items():
         col = records[:, a:b]
         out[name] = col[:, 0] if b - a == 1 else col
+    return out
+
+
+# columns of the (n, 8) int32 rows of Scene.atlas_texels: the fields of ptrt_atlas_texel / ATLAS_TEXEL_DTYPE
+ATLAS_COLUMNS = dict(position=(0, 3), face=(3, 4), normal=(4, 7), mesh=(7, 8))
+
+
+def atlas_fields(records):
+    """Named views of atlas_texels' (n, 8) int32 rows (a tensor or an array): position and normal reinterpreted as float32,
+    (n, 3); face and mesh int32, (n,)."""
+    import torch
+    f32 = torch.float32 if _is_tensor(records) else np.float32
+    out = {}
+    for name, (a, b) in ATLAS_COLUMNS.items():
+        col = records[:, a:b]
+        out[name] = col[:, 0] if b - a == 1 else col.view(f32)
     return out
 
 
@@ -1197,6 +1224,61 @@ class Scene:
             None if phases is None else _vp(phases.data_ptr()), float(offset), first, count, _vp(o.data_ptr()), _vp(d.data_ptr()),
             _vp(t.data_ptr()), _vp(w.data_ptr()))))
         return o, d, t, w
+
+    def atlas_texels(self, mesh, uv, width, height, out=None, clear=True):
+        """The UV charts of mesh `mesh` (the id addCube and its kin return) rasterised into a `width` x `height` lightmap atlas
+        (ptrt_atlas_texels).  `uv`: an (F, 6) float32 tensor on this scene's device, contiguous, read in place -- the (x, y) of
+        corners v0, v1, v2 of each of the mesh's F faces in TEXEL units (`lightmap.triangle_charts` makes charts for a mesh
+        without UVs, `lightmap.uv_to_texels` scales [0, 1] UVs).  Returns an (height * width, 8) int32 tensor, one 32-byte
+        `ptrt_atlas_texel` per row, texel (i, j) in row j * width + i (`atlas_fields` names the columns): world position (0:3,
+        float32 bits), owning face (3), world geometric normal (4:7, float32 bits), mesh (7; -1 where no face covers the texel's
+        centre (i + 0.5, j + 0.5)).  The lowest face covering a centre owns it.  `out` takes such a tensor; with `clear=False`
+        its texels with mesh >= 0 are kept, so several meshes can share an atlas (the first call wins).
+        `lightmap.atlas_inputs` turns the rows into what query_irradiance and query_direct take.  No synchronisation."""
+        self._device_tensor("atlas_texels: uv", uv, 6, "torch.float32")
+        width, height = int(width), int(height)
+        if width < 1 or height < 1 or width * height > 2 ** 28:
+            raise ValueError(f"atlas_texels: a {width} x {height} atlas (1 x 1 .. 2^28 texels)")
+        faces = self.meshCounts(int(mesh))[1]
+        if uv.shape[0] != faces:
+            raise ValueError(f"atlas_texels: uv has {uv.shape[0]} rows, mesh {mesh} has {faces} faces")
+        import torch
+        if out is None:
+            if not clear:
+                raise ValueError("atlas_texels: clear=False needs the atlas of an earlier call as `out`")
+            out = torch.empty((width * height, 8), dtype=torch.int32, device=uv.device)
+        else:
+            self._device_tensor("atlas_texels: out", out, 8, "torch.int32")
+            if out.shape[0] != width * height:
+                raise ValueError(f"atlas_texels: out has {out.shape[0]} rows for {width} x {height} texels")
+        self._enqueue_between_streams(uv.device, lambda: self._chk(lib.hs_atlas_texels(
+            self._h, int(mesh), _vp(uv.data_ptr()), width, height, 1 if clear else 0, _vp(out.data_ptr()))))
+        return out
+
+    def atlas_dilate(self, image, passes=1):
+        """`passes` (1 .. 64) dilation passes over a baked atlas (ptrt_atlas_dilate).  `image`: an (H, W, 4) float32 tensor on
+        this scene's device, contiguous, {r, g, b, valid} per texel -- `lightmap.scatter(..).reshape(H, W, 4)` makes one.  Each
+        pass gives every invalid texel (valid == 0) that has valid 8-neighbours their mean and marks it valid; texels filled
+        in one pass spread in the next.  The passes alternate between `image` and a second buffer allocated here; returns the
+        tensor that holds the result -- `image` itself for an even `passes` (it is overwritten from the second pass on).  No
+        synchronisation."""
+        if not _is_tensor(image) or image.dim() != 3:
+            raise ValueError("atlas_dilate: image: needs a torch tensor of shape (H, W, 4) on the scene's device")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        if h < 1 or w < 1 or h * w > 2 ** 28:
+            raise ValueError(f"atlas_dilate: a {w} x {h} atlas (1 x 1 .. 2^28 texels)")
+        if not image.is_contiguous():
+            raise ValueError("atlas_dilate: image: tensors must be contiguous")
+        self._device_tensor("atlas_dilate: image", image.view(h * w, -1), 4, "torch.float32")
+        passes = int(passes)
+        if passes < 1 or passes > 64:
+            raise ValueError(f"atlas_dilate: {passes} passes (1 .. 64)")
+        import torch
+        other = torch.empty_like(image)
+        where = []
+        self._enqueue_between_streams(image.device, lambda: where.append(self._chk(lib.hs_atlas_dilate(
+            self._h, _vp(image.data_ptr()), _vp(other.data_ptr()), w, h, passes))))
+        return other if where[0] else image
 
     def camera_rays(self, frame, sample=0):
         """(origins, directions): (rows * width, 3) float32 tensors on this scene's device holding the primary rays

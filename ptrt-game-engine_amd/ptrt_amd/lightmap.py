@@ -6,7 +6,11 @@ A texel's rays are cosine-distributed about its normal, so the mean of their rad
 rays mostly end close by -- inside a wall, under a carpet -- is one a baker fills from its neighbours (`invalid_texels`).
 
 Scene.query_direct adds what the gather cannot see, the analytic lights at the texel itself: `direct_irradiance`,
-`penumbra_texels` and `total_irradiance` read its rows."""
+`penumbra_texels` and `total_irradiance` read its rows.
+
+Scene.atlas_texels makes the texels of an uploaded mesh from its UV charts and Scene.atlas_dilate finishes a baked atlas:
+`triangle_charts` (charts for a mesh that never had UVs), `uv_to_texels`, `covered`, `atlas_inputs` and `scatter` stand between
+them and the queries; these take torch tensors as well as arrays and answer in kind."""
 import math
 
 import numpy as np
@@ -79,7 +83,8 @@ def irradiance(records):
 
 def invalid_texels(records, threshold):
     """(n,) bool: texels whose rays all hit something and on average within `threshold` -- hit_fraction == 1 and
-    mean_distance < threshold: the texel lies inside or right under geometry, and a baker dilates its neighbours over it."""
+    mean_distance < threshold: the texel lies inside or right under geometry, and a baker dilates its neighbours over it --
+    leave such texels out of the indices given to `scatter` and Scene.atlas_dilate fills them with the empty ones."""
     r = _rows(records)
     return (r[:, 5] >= np.float32(1.0)) & (r[:, 3] < np.float32(threshold))
 
@@ -110,3 +115,105 @@ def total_irradiance(direct_rows, gather_rows):
     if d.shape != g.shape:
         raise ValueError(f"total_irradiance: {d.shape[0]} direct rows, {g.shape[0]} gather rows")
     return d + g
+
+
+def triangle_charts(face_count, cell, gutter=1):
+    """(uv (face_count, 6) float32 in texel units, atlas_w, atlas_h): a chart of its own for every face of a mesh without UVs,
+    ready for Scene.atlas_texels.  The atlas is a grid of square cells of `cell` texels; a cell holds two right isosceles
+    triangles with legs of cell - 2 * gutter - 0.5 texels, face 2k at the cell's low corner -- v0 at the right angle (X, Y),
+    v1 along +x, v2 along +y -- and face 2k + 1 turned by half a turn at (X, Y) + cell - gutter.  The legs lie on integer
+    lines and have a half-integer length, so every vertex is a multiple of 0.5 texel and no texel centre lies on a chart's edge
+    (none comes closer than 0.35 texel); charts of different faces are at least `gutter` texels apart in the Chebyshev sense --
+    no point of one is within `gutter` of a point of another in both axes at once --, and every chart holds at least one
+    centre.  ValueError for face_count < 1, gutter < 0 or cell < 2 * gutter + 2 (integers all)."""
+    if int(face_count) != face_count or int(cell) != cell or int(gutter) != gutter:
+        raise ValueError(f"triangle_charts: face_count {face_count!r}, cell {cell!r}, gutter {gutter!r}: integers")
+    face_count, cell, gutter = int(face_count), int(cell), int(gutter)
+    if face_count < 1 or gutter < 0 or cell < 2 * gutter + 2:
+        raise ValueError(f"triangle_charts: {face_count} faces, cells of {cell} texels, a gutter of {gutter} "
+                         "(face_count >= 1, gutter >= 0, cell >= 2 * gutter + 2)")
+    cells = (face_count + 1) // 2
+    cols = int(math.ceil(math.sqrt(cells)))
+    while cols * cols < cells:
+        cols += 1
+    rows = (cells + cols - 1) // cols
+    if cols * cell * rows * cell > 1 << 28:
+        raise ValueError(f"triangle_charts: {face_count} faces in cells of {cell} texels: more than 2^28 texels")
+    leg, side = cell - 2 * gutter - 0.5, float(cell - gutter)
+    f = np.arange(face_count)
+    k = f // 2
+    x, y = (k % cols).astype(np.float64) * cell, (k // cols).astype(np.float64) * cell
+    low = (f % 2 == 0)
+    ax, ay = np.where(low, x, x + side), np.where(low, y, y + side)  # the right angle
+    d = np.where(low, leg, -leg)
+    uv = np.stack([ax, ay, ax + d, ay, ax, ay + d], axis=1)
+    return np.ascontiguousarray(uv.astype(np.float32)), cols * cell, rows * cell
+
+
+def uv_to_texels(uv01, w, h):
+    """(F, 6) float32: UVs in [0, 1]^2 -- (F, 6) or (F, 3, 2), u to the right, v up the rows -- scaled to the texel units of a
+    w x h atlas (u * w, v * h; one float32 product each).  An array or a torch tensor, answered in kind."""
+    w, h = int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError(f"uv_to_texels: a {w} x {h} atlas")
+    if hasattr(uv01, "cpu"):
+        import torch
+        uv = uv01.to(torch.float32).reshape(-1, 3, 2)
+        return (uv * torch.tensor([w, h], dtype=torch.float32, device=uv.device)).reshape(-1, 6).contiguous()
+    uv = np.asarray(uv01, np.float32).reshape(-1, 3, 2)
+    return np.ascontiguousarray((uv * np.float32([w, h])).reshape(-1, 6))
+
+
+def _atlas_rows(records):
+    if records.ndim != 2 or records.shape[1] != 8 or "int32" not in str(records.dtype):
+        raise ValueError(f"lightmap: atlas records of shape {tuple(records.shape)} and {records.dtype}, expected (n, 8) int32")
+    return records
+
+
+def covered(records):
+    """The indices, ascending (row-major: texel (i, j) of a W-wide atlas is j * W + i), of the texels of Scene.atlas_texels'
+    (n, 8) int32 rows that a face covers: mesh >= 0.  int64; a tensor for a tensor (on its device), an array for an array."""
+    r = _atlas_rows(records)
+    if hasattr(r, "cpu"):
+        import torch
+        return torch.nonzero(r[:, 7] >= 0).reshape(-1)
+    return np.flatnonzero(np.asarray(r)[:, 7] >= 0)
+
+
+def atlas_inputs(records):
+    """(positions (n, 3), normals (n, 3)) float32, contiguous: the covered texels of Scene.atlas_texels' rows in the order of
+    `covered`, as Scene.query_irradiance and Scene.query_direct take them (tensors for a tensor, arrays for an array)."""
+    r = _atlas_rows(records)
+    idx = covered(r)
+    if hasattr(r, "cpu"):
+        import torch
+        rows = r[idx].view(torch.float32)
+        return rows[:, 0:3].contiguous(), rows[:, 4:7].contiguous()
+    rows = np.ascontiguousarray(np.asarray(r)[idx]).view(np.float32)
+    return np.ascontiguousarray(rows[:, 0:3]), np.ascontiguousarray(rows[:, 4:7])
+
+
+def scatter(values, indices, w, h):
+    """(h * w, 4) float32 {r, g, b, valid}: values[k] (n, 3) at texel indices[k] with valid = 1, zeros elsewhere -- reshaped to
+    (h, w, 4) the image Scene.atlas_dilate takes.  Tensors give a tensor on their device, arrays an array."""
+    w, h = int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError(f"scatter: a {w} x {h} atlas")
+    if values.ndim != 2 or values.shape[1] != 3 or indices.ndim != 1 or indices.shape[0] != values.shape[0]:
+        raise ValueError(f"scatter: values {tuple(values.shape)}, indices {tuple(indices.shape)}, expected (n, 3) and (n,)")
+    if hasattr(values, "cpu"):
+        import torch
+        idx = torch.as_tensor(indices, dtype=torch.int64, device=values.device)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= w * h):
+            raise ValueError(f"scatter: an index outside the {w} x {h} atlas")
+        img = torch.zeros((h * w, 4), dtype=torch.float32, device=values.device)
+        img[idx, 0:3] = values.to(torch.float32)
+        img[idx, 3] = 1.0
+        return img
+    idx = np.asarray(indices.cpu() if hasattr(indices, "cpu") else indices, np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= w * h):
+        raise ValueError(f"scatter: an index outside the {w} x {h} atlas")
+    img = np.zeros((h * w, 4), np.float32)
+    img[idx, 0:3] = np.asarray(values, np.float32)
+    img[idx, 3] = 1.0
+    return img
