@@ -776,6 +776,41 @@ int ptrt_atlas_texels(ptrt_ctx *ctx, int mesh_index, const float *d_uv, int atla
  * buffers that overlap, memory that is not the context's device memory or too small.  Needs no scene.  (ABI 6, addition only.) */
 int ptrt_atlas_dilate(ptrt_ctx *ctx, float *d_a, float *d_b, int atlas_w, int atlas_h, int passes);
 
+/* Between scatter and dilation: `passes` (1 .. 8) passes of an edge-aware a-trous filter over a baked atlas of float4
+ * {r, g, b, valid} texels in DEVICE memory, guided by the atlas's own records d_texels (ptrt_atlas_texels' output, atlas_w *
+ * atlas_h of them, only read): light is averaged over texels that are close in the world, near the centre's tangent plane and
+ * face the same way, so it does not bleed round a crease or between charts that are neighbours in the atlas only.  The image
+ * goes d_a -> d_b -> d_a ..; the result is in d_b for an odd `passes`, in d_a for an even one (the other buffer holds the pass
+ * before) -- ptrt_atlas_dilate's rule.  Pass s (from 0) has step = 1 << s.
+ * One pass is ONE definition in fp32, every operation rounded on its own (no contraction), `/` the IEEE quotient.  For texel
+ * p = (i, j), G = d_texels[p], C = src[p]:
+ *   G.mesh < 0 or C.valid == 0 (a texel is valid when valid != 0, as for ptrt_atlas_dilate):  dst[p] = C, its 16 bytes copied.
+ *   Otherwise num = (0, 0, 0), den = 0, and the 25 taps dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), in that order, at
+ *   q = (i + dx*step, j + dy*step).  A tap outside the atlas, one with Gq.mesh < 0 and one with Cq.valid == 0 is skipped -- by
+ *   selection, never by a product with zero: a NaN or an infinity in a skipped tap's colour or guide reaches nothing.  Else
+ *       h  = K[|dx|] * K[|dy|]                     K = {0.375, 0.25, 0.0625}: the B3 spline, every product exact
+ *       e  = Gq.position - G.position              per component
+ *       d2 = (e.x*e.x + e.y*e.y) + e.z*e.z         x = 1 - d2 / rr          wd = x > 0 ? x : 0
+ *       pd = (G.n.x*e.x + G.n.y*e.y) + G.n.z*e.z   y = 1 - (pd*pd) / pp     wp = y > 0 ? y : 0
+ *       c  = (G.n.x*Gq.n.x + G.n.y*Gq.n.y) + G.n.z*Gq.n.z      c = c > 0 ? c : 0      then normal_power times  c = c*c
+ *       w  = ((h * wd) * wp) * c
+ *   with rr = r*r, r = sigma_distance * (float)step, and pp = sigma_plane * sigma_plane (not scaled by the step), formed in
+ *   fp32 on the host.  normal_power 0 is the plain cosine, 7 its 128th power.  If !(w > 0) the tap is skipped -- a NaN weight
+ *   ends here --; otherwise num += w * Cq.rgb per channel (the product rounded, then the sum) and den += w.
+ *   den == 0 (a centre with a zero normal):  dst[p] = C copied.  Otherwise dst[p] = {num.r / den, num.g / den, num.b / den,
+ *   C.valid}.
+ * Normals are expected to be unit vectors, as ptrt_atlas_texels writes them: a longer one can take c*c*.. to infinity, and
+ * infinity / infinity is a NaN by the arithmetic above.
+ * tests/atlas_filter_restatement.py states all of it in numpy.  One launch per pass on the context's stream; no allocation,
+ * copy or synchronisation; needs no scene; ordering and side effects are ptrt_atlas_dilate's: generator states, frame buffers,
+ * counters and both timing histories are left alone.  Option "atlas_filter_tile" chooses between two shapes of a pass with the
+ * same bytes.  PTRT_E_INVALID (nothing enqueued, both buffers untouched) for passes outside 1 .. 8, normal_power outside
+ * 0 .. 7, a sigma that is not finite or <= 0, an rr (of any of the passes) or pp that is not finite or is zero in fp32, atlas
+ * sizes outside ptrt_atlas_dilate's, a NULL or not 16-byte aligned pointer, d_a and d_b overlapping each other or d_texels,
+ * memory that is not the context's device memory or too small (byte counts in size_t).  (ABI 6, addition only.) */
+int ptrt_atlas_filter(ptrt_ctx *ctx, const ptrt_atlas_texel *d_texels, float *d_a, float *d_b, int atlas_w, int atlas_h, int passes,
+                      float sigma_distance, float sigma_plane, int normal_power);
+
 /* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
  * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small
  * kernel on the context's stream into DEVICE memory: rows*W*3 floats each (render_w*render_h*3 at a reduced render size),
@@ -975,6 +1010,11 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         slots at a time).  -1 (default): chosen on the host from atlas texels / faces of the mesh (DESIGN.md
  *                         3.28); anything else is PTRT_E_INVALID.  Same bytes under every value.  ptrt_get_option
  *                         "atlas_lanes_eff" says what the last ptrt_atlas_texels ran (0: none yet).
+ *   atlas_filter_tile -1|0|1  ptrt_atlas_filter: 1 stages a workgroup's 16 x 16 texels and their halo of 2 * step -- guides and
+ *                         colours -- in LDS wherever that fits, which is at steps 1, 2 and 4; 0 reads every tap with global loads
+ *                         at every step; -1 (default): per step, whichever was measured faster.  Same bytes
+ *                         under every value.  ptrt_get_option "atlas_filter_tile_eff" says how many passes of the last
+ *                         ptrt_atlas_filter ran the LDS tile (-1: none yet).
  *   tile_run 0..64        the one-tile-per-workgroup kernels' workgroup -> tile map.  Consecutive workgroups go to the eight XCDs in
  *                         turn; with n > 0, of every 8 n consecutive tiles XCD x renders tiles [x n, (x + 1) n) -- neighbours,
  *                         whose rays walk the same part of the trees, share an L2 -- instead of every eighth tile.  8 (default):

@@ -23,6 +23,7 @@
 #include "pt_irradiance.hip.h"
 #include "pt_direct.hip.h"
 #include "pt_atlas.hip.h"
+#include "pt_atlas_filter.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -263,6 +264,8 @@ struct ptrt_ctx {
     int query_pmode = -1;                // traversal of the last ray query (ptrt_get_option "query_pmode"; -1 none yet)
     int atlas_lanes = -1;                // option "atlas_lanes": lanes per triangle of ptrt_atlas_texels, 1 / 4 / 16 / 64, or -1: by the texels per face
     int atlas_lanes_eff = 0;             // ... of the last ptrt_atlas_texels (0 none yet)
+    int atlas_filter_tile = -1;          // option "atlas_filter_tile": ptrt_atlas_filter's LDS tile, 0 never / 1 wherever it fits / -1: by the measured rule
+    int atlas_filter_tile_eff = -1;      // passes of the last ptrt_atlas_filter that ran the LDS tile (-1 none yet)
     bool last_merged_possible = false;   // ... and whether that scene has the two loop shapes to choose from
     bool timed = false;
     bool prev_post = false;              // the previous frame had a denoiser / bloom chain behind its trace (ptrt_render "pipeline")

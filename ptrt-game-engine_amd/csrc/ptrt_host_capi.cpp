@@ -459,6 +459,14 @@ int hs_atlas_dilate(void *s, void *d_a, void *d_b, int atlas_w, int atlas_h, int
     HS_TRY(return static_cast<Scene *>(s)->atlasDilate(static_cast<float *>(d_a), static_cast<float *>(d_b), atlas_w, atlas_h, passes) == d_b
                       ? 1 : 0);
 }
+// 0: the result is in d_a; 1: in d_b
+int hs_atlas_filter(void *s, const void *d_texels, void *d_a, void *d_b, int atlas_w, int atlas_h, int passes, float sigma_distance,
+                    float sigma_plane, int normal_power) {
+    HS_TRY(return static_cast<Scene *>(s)->atlasFilter(static_cast<const ptrt_atlas_texel *>(d_texels), static_cast<float *>(d_a),
+                                                       static_cast<float *>(d_b), atlas_w, atlas_h, passes, sigma_distance, sigma_plane,
+                                                       normal_power) == d_b
+                      ? 1 : 0);
+}
 int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
     HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;

@@ -87,6 +87,7 @@ const Option OPTIONS[] = {
     {"motion_vectors", &ptrt_ctx::mv_active, OPT_BOOL}, // perfSettings.enableMotionVectors
     {"use_graphs", &ptrt_ctx::use_graphs, OPT_BOOL}, // 0: issue the refit / rebuild launches one by one instead of replaying a hipGraph
     {"atlas_lanes", &ptrt_ctx::atlas_lanes, OPT_LANES}, // ptrt_atlas_texels: lanes that share one triangle's texel range (-1: from atlas texels per face)
+    {"atlas_filter_tile", &ptrt_ctx::atlas_filter_tile, OPT_TRISTATE}, // ptrt_atlas_filter: stage a tile's guides and colours in LDS at steps 1, 2 and 4 (-1: the measured rule)
     // read-only facts about the last ptrt_render (so that a measurement can say what ran)
     {"sample_sync_eff", &ptrt_ctx::sample_sync_eff, OPT_READ_ONLY},
     {"pm1_dense_roots_eff", &ptrt_ctx::pm1_dense_roots_eff, OPT_READ_ONLY},
@@ -95,6 +96,7 @@ const Option OPTIONS[] = {
     {"plain_leaf_eff", &ptrt_ctx::plain_leaf_eff, OPT_READ_ONLY}, // ... of the last frame or query, whichever came last
     {"tri_frames_eff", &ptrt_ctx::tri_frames_eff, OPT_READ_ONLY}, // ... of the last frame
     {"atlas_lanes_eff", &ptrt_ctx::atlas_lanes_eff, OPT_READ_ONLY}, // ... of the last ptrt_atlas_texels: 1, 4, 16 or 64 (0: none yet)
+    {"atlas_filter_tile_eff", &ptrt_ctx::atlas_filter_tile_eff, OPT_READ_ONLY}, // passes of the last ptrt_atlas_filter that ran the LDS tile (-1: none yet)
     {"refilled", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->refill_eff ? 1 : 0; }},
     {"split_eff", &ptrt_ctx::split_eff, OPT_READ_ONLY},
     {"pipelined", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->pipelined_last ? 1 : 0; }},

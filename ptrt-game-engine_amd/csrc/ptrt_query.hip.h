@@ -1,7 +1,7 @@
 // ptrt_query.hip.h -- the device queries of the C ABI: closest hit and occlusion (ptrt_trace_rays, ptrt_query_rays), path-traced
 // radiance (ptrt_query_radiance), light probes (ptrt_query_probes), lightmap texels (ptrt_query_irradiance, with
 // ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights), the lightmap
-// atlas around them (ptrt_atlas_texels, ptrt_atlas_dilate: no traversal) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
+// atlas around them (ptrt_atlas_texels, ptrt_atlas_filter, ptrt_atlas_dilate: no traversal) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
 // ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
 // (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
 // check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
@@ -517,6 +517,94 @@ int ptrt_atlas_dilate(ptrt_ctx *c, float *d_a, float *d_b, int atlas_w, int atla
     for (int p = 0; p < passes; ++p) {
         hipLaunchKernelGGL(pt::atlas_dilate_kernel, dim3((unsigned)((bytes / 16 + 255) / 256)), dim3(256), 0, c->stream,
                            (const float4 *)buf[p & 1], buf[(p & 1) ^ 1], atlas_w, atlas_h);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return PTRT_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+// Whether pass `step` of ptrt_atlas_filter runs the LDS-tile shape of atlas_filter_kernel (pt_atlas_filter.hip.h) when option
+// "atlas_filter_tile" is -1.  The tile exists for steps 1, 2 and 4 (atlas_filter_tile_fits: at step 8 its halo no longer fits a
+// workgroup's 64 KB).  Measured on an MI355X (profiles/atlas_filter_time.json): at all three steps the tile
+// was the faster shape at every atlas and image timed -- 8 .. 10 against 12 .. 16 us at 256^2 (both near a launch's latency),
+// 44 .. 50 against 75 .. 92 us at 1024^2, 0.59 .. 0.67 against 1.28 .. 1.40 ms at 4096^2 -- so the rule is: wherever it fits.
+bool atlas_filter_tile_fits(int step) { return step == 1 || step == 2 || step == 4; }
+bool atlas_filter_auto_tile(int step) { return atlas_filter_tile_fits(step); }
+
+} // namespace
+
+extern "C" {
+
+int ptrt_atlas_filter(ptrt_ctx *c, const ptrt_atlas_texel *d_texels, float *d_a, float *d_b, int atlas_w, int atlas_h, int passes,
+                      float sigma_distance, float sigma_plane, int normal_power) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_filter: bad context");
+    if (!d_texels || !d_a || !d_b || !atlas_size_ok(atlas_w, atlas_h) || passes < 1 || passes > 8 || normal_power < 0 || normal_power > 7)
+        return fail(c, PTRT_E_INVALID,
+                    "ptrt_atlas_filter: bad argument (texels %p, a %p, b %p, atlas %d x %d: 1 x 1 .. 2^28 texels, passes %d: 1 .. 8, "
+                    "normal_power %d: 0 .. 7)",
+                    (const void *)d_texels, (const void *)d_a, (const void *)d_b, atlas_w, atlas_h, passes, normal_power);
+    // the two ranges, squared in fp32 as the definition has them: one rr per pass, one pp
+    float rr[8] = {};
+    const float pp = sigma_plane * sigma_plane;
+    bool ranges_ok = std::isfinite(sigma_distance) && std::isfinite(sigma_plane) && sigma_distance > 0.0f && sigma_plane > 0.0f &&
+                     std::isfinite(pp) && pp != 0.0f;
+    for (int p = 0; p < passes && ranges_ok; ++p) {
+        const float r = sigma_distance * (float)(1 << p);
+        rr[p] = r * r;
+        ranges_ok = std::isfinite(rr[p]) && rr[p] != 0.0f;
+    }
+    if (!ranges_ok)
+        return fail(c, PTRT_E_INVALID,
+                    "ptrt_atlas_filter: sigma_distance %g, sigma_plane %g: positive and finite, with finite non-zero squares in fp32 at every "
+                    "step of %d passes",
+                    (double)sigma_distance, (double)sigma_plane, passes);
+    const size_t texels = (size_t)atlas_w * (size_t)atlas_h, bytes = texels * 16, guide_bytes = texels * sizeof(ptrt_atlas_texel);
+    const uintptr_t a = (uintptr_t)d_a, b = (uintptr_t)d_b, g = (uintptr_t)d_texels;
+    if (!aligned16(d_a) || !aligned16(d_b) || !aligned16(d_texels))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_filter: texels %p, a %p and b %p must be 16-byte aligned", (const void *)d_texels,
+                    (const void *)d_a, (const void *)d_b);
+    auto apart = [](uintptr_t x, size_t nx, uintptr_t y, size_t ny) { return x < y ? y - x >= nx : x - y >= ny; };
+    if (!apart(a, bytes, b, bytes) || !apart(a, bytes, g, guide_bytes) || !apart(b, bytes, g, guide_bytes))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_filter: a %p and b %p (%zu bytes each) and texels %p (%zu bytes) must not overlap",
+                    (const void *)d_a, (const void *)d_b, bytes, (const void *)d_texels, guide_bytes);
+    if (int rc = set_device(c))
+        return rc;
+    if (int rc = check_spans(c, "ptrt_atlas_filter", {{"texels", d_texels, guide_bytes}, {"a", d_a, bytes}, {"b", d_b, bytes}}))
+        return rc;
+    c->touched = true;
+    // atlas_filter_kernel (pt_atlas_filter.hip.h): a -> b -> a ..., one launch per pass, step 1 << pass
+    static_assert(sizeof(pt::AtlasTexel) == sizeof(ptrt_atlas_texel), "AtlasTexel must mirror ptrt_atlas_texel");
+    const pt::AtlasTexel *t = reinterpret_cast<const pt::AtlasTexel *>(d_texels);
+    float4 *buf[2] = {reinterpret_cast<float4 *>(d_a), reinterpret_cast<float4 *>(d_b)};
+    const auto tiles = [&](int tw, int th) { return ((size_t)atlas_w + tw - 1) / tw * (((size_t)atlas_h + th - 1) / th); };
+    c->atlas_filter_tile_eff = 0;
+    for (int p = 0; p < passes; ++p) {
+        const int step = 1 << p;
+        const bool tile = atlas_filter_tile_fits(step) && (c->atlas_filter_tile < 0 ? atlas_filter_auto_tile(step) : c->atlas_filter_tile != 0);
+        const float4 *src = buf[p & 1];
+        float4 *dst = buf[(p & 1) ^ 1];
+        if (tile) {
+            const unsigned tx = (unsigned)(((size_t)atlas_w + pt::FILTER_TILE - 1) / pt::FILTER_TILE);
+            const dim3 grid((unsigned)tiles(pt::FILTER_TILE, pt::FILTER_TILE));
+            if (step == 1)
+                hipLaunchKernelGGL(pt::atlas_filter_kernel<1>, grid, dim3(256), 0, c->stream, t, src, dst, atlas_w, atlas_h, step, rr[p], pp,
+                                   normal_power, tx);
+            else if (step == 2)
+                hipLaunchKernelGGL(pt::atlas_filter_kernel<2>, grid, dim3(256), 0, c->stream, t, src, dst, atlas_w, atlas_h, step, rr[p], pp,
+                                   normal_power, tx);
+            else
+                hipLaunchKernelGGL(pt::atlas_filter_kernel<4>, grid, dim3(256), 0, c->stream, t, src, dst, atlas_w, atlas_h, step, rr[p], pp,
+                                   normal_power, tx);
+            ++c->atlas_filter_tile_eff;
+        } else {
+            const unsigned tx = (unsigned)(((size_t)atlas_w + pt::FILTER_ROW - 1) / pt::FILTER_ROW);
+            hipLaunchKernelGGL(pt::atlas_filter_kernel<0>, dim3((unsigned)tiles(pt::FILTER_ROW, pt::FILTER_ROWS)), dim3(256), 0, c->stream, t, src,
+                               dst, atlas_w, atlas_h, step, rr[p], pp, normal_power, tx);
+        }
         HIP_TRY(c, hipGetLastError());
     }
     return PTRT_OK;

@@ -1016,6 +1016,18 @@ class Scene {
         check(ptrt_atlas_dilate(ctx, d_a, d_b, atlas_w, atlas_h, passes), "Atlas dilation failed");
         return (passes & 1) ? d_b : d_a;
     }
+    // `passes` (1 .. 8) passes of the edge-aware a-trous filter over a baked atlas of float4 {r, g, b, valid} (ptrt_atlas_filter),
+    // d_a -> d_b -> d_a .., guided by the atlas's records: pass s weighs the 25 taps of a 5 x 5 B3 kernel at step 1 << s by world
+    // distance (sigma_distance * step), by distance from the centre's tangent plane (sigma_plane) and by the cosine between the
+    // normals squared normal_power (0 .. 7) times.  Between scatter and atlasDilate.  Returns the buffer that holds the result.
+    // Needs no scene.
+    float *atlasFilter(const ptrt_atlas_texel *d_texels, float *d_a, float *d_b, int atlas_w, int atlas_h, int passes,
+                       float sigma_distance, float sigma_plane, int normal_power = 2) {
+        needBackend();
+        check(ptrt_atlas_filter(ctx, d_texels, d_a, d_b, atlas_w, atlas_h, passes, sigma_distance, sigma_plane, normal_power),
+              "Atlas filter failed");
+        return (passes & 1) ? d_b : d_a;
+    }
     // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
     // tile rows * width * 3 floats each, in the order of the colour buffer.
     void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {

@@ -227,6 +227,7 @@ _sig("ptrt_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c
 _sig("ptrt_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp)
 _sig("ptrt_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("ptrt_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
+_sig("ptrt_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
 _sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
@@ -361,6 +362,7 @@ _sig("hs_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_
 _sig("hs_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
 _sig("hs_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("hs_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
+_sig("hs_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -1278,6 +1280,45 @@ class Scene:
         where = []
         self._enqueue_between_streams(image.device, lambda: where.append(self._chk(lib.hs_atlas_dilate(
             self._h, _vp(image.data_ptr()), _vp(other.data_ptr()), w, h, passes))))
+        return other if where[0] else image
+
+    def atlas_filter(self, texels, image, passes, sigma_distance, sigma_plane, normal_power=2):
+        """`passes` (1 .. 8) passes of the edge-aware a-trous filter over a baked atlas (ptrt_atlas_filter), between
+        `lightmap.scatter` and `atlas_dilate`.  `texels`: the (H * W, 8) int32 rows of `atlas_texels` for this atlas, read in
+        place; `image`: an (H, W, 4) float32 tensor on this scene's device, contiguous, {r, g, b, valid} per texel.  Pass s
+        averages the 25 taps of a 5 x 5 B3 kernel at step 2^s, each weighed by its world distance from the centre (nothing
+        beyond `sigma_distance` * step), its distance from the centre's tangent plane (nothing beyond `sigma_plane`) and the
+        cosine between the two normals squared `normal_power` (0 .. 7) times; invalid texels (valid == 0) and uncovered ones
+        (mesh < 0) neither give nor take and are copied.  `lightmap.filter_sigmas(lightmap.texel_pitch(texels, W, H))`
+        recommends the sigmas.  The passes alternate between `image` and a second buffer allocated here; returns the tensor
+        that holds the result -- `image` itself for an even `passes` (it is overwritten from the second pass on).  No
+        synchronisation."""
+        if not _is_tensor(image) or image.dim() != 3:
+            raise ValueError("atlas_filter: image: needs a torch tensor of shape (H, W, 4) on the scene's device")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        if h < 1 or w < 1 or h * w > 2 ** 28:
+            raise ValueError(f"atlas_filter: a {w} x {h} atlas (1 x 1 .. 2^28 texels)")
+        if not image.is_contiguous():
+            raise ValueError("atlas_filter: image: tensors must be contiguous")
+        passes, normal_power = int(passes), int(normal_power)
+        if passes < 1 or passes > 8:
+            raise ValueError(f"atlas_filter: {passes} passes (1 .. 8)")
+        if normal_power < 0 or normal_power > 7:
+            raise ValueError(f"atlas_filter: normal_power {normal_power} (0 .. 7)")
+        sigma_distance, sigma_plane = float(sigma_distance), float(sigma_plane)
+        for name, v in (("sigma_distance", sigma_distance), ("sigma_plane", sigma_plane)):
+            if not (np.isfinite(v) and v > 0.0):
+                raise ValueError(f"atlas_filter: {name} {v} (positive and finite)")
+        self._device_tensor("atlas_filter: image", image.view(h * w, -1), 4, "torch.float32")
+        self._device_tensor("atlas_filter: texels", texels, 8, "torch.int32")
+        if texels.shape[0] != h * w:
+            raise ValueError(f"atlas_filter: texels has {texels.shape[0]} rows for {w} x {h} texels")
+        import torch
+        other = torch.empty_like(image)
+        where = []
+        self._enqueue_between_streams(image.device, lambda: where.append(self._chk(lib.hs_atlas_filter(
+            self._h, _vp(texels.data_ptr()), _vp(image.data_ptr()), _vp(other.data_ptr()), w, h, passes, sigma_distance, sigma_plane,
+            normal_power))))
         return other if where[0] else image
 
     def camera_rays(self, frame, sample=0):

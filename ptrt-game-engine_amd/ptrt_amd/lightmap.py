@@ -10,7 +10,9 @@ Scene.query_direct adds what the gather cannot see, the analytic lights at the t
 
 Scene.atlas_texels makes the texels of an uploaded mesh from its UV charts and Scene.atlas_dilate finishes a baked atlas:
 `triangle_charts` (charts for a mesh that never had UVs), `uv_to_texels`, `covered`, `atlas_inputs` and `scatter` stand between
-them and the queries; these take torch tensors as well as arrays and answer in kind."""
+them and the queries; these take torch tensors as well as arrays and answer in kind.  Scene.atlas_filter stands between
+`scatter` and the dilation -- the order of a bake is scatter, atlas_filter, atlas_dilate -- and `texel_pitch` and
+`filter_sigmas` give it its two ranges."""
 import math
 
 import numpy as np
@@ -110,7 +112,10 @@ def total_irradiance(direct_rows, gather_rows):
     What this sum still LACKS: a gather ray takes no light sample at its first hit (the quirk of a caller's ray, include/ptrt.h),
     so the analytic lights' one-bounce term -- light that reaches the texel after exactly one diffuse reflection off the surface
     a gather ray hits first -- is absent; emissive meshes, the sky and every later bounce are in the gather.  A lit first vertex
-    for the gather is not built."""
+    for the gather is not built.
+
+    The order of a bake from here: `scatter` these values into the atlas, Scene.atlas_filter (the gather's Monte-Carlo noise,
+    edge-aware, covered texels only), then Scene.atlas_dilate (the texels no chart covers)."""
     d, g = direct_irradiance(direct_rows), irradiance(gather_rows)
     if d.shape != g.shape:
         raise ValueError(f"total_irradiance: {d.shape[0]} direct rows, {g.shape[0]} gather rows")
@@ -217,3 +222,45 @@ def scatter(values, indices, w, h):
     img[idx, 0:3] = np.asarray(values, np.float32)
     img[idx, 3] = 1.0
     return img
+
+
+def texel_pitch(records, w, h):
+    """The median world distance between horizontally adjacent covered texels of the same face and mesh of Scene.atlas_texels'
+    (h * w, 8) int32 rows (a tensor or an array; computed where it is, in float32): how far apart in the world neighbouring
+    texels of one chart are, the natural unit for Scene.atlas_filter's two sigmas.  A float -- of an even number of distances the
+    lower of the two middle ones, for tensors and arrays alike --; 0.0 when the atlas has no such pair."""
+    r = _atlas_rows(records)
+    w, h = int(w), int(h)
+    if w < 1 or h < 1 or r.shape[0] != w * h:
+        raise ValueError(f"texel_pitch: {r.shape[0]} records for a {w} x {h} atlas")
+    if hasattr(r, "cpu"):
+        import torch
+        g = r.reshape(h, w, 8)
+        a, b = g[:, :-1], g[:, 1:]
+        pair = (a[..., 7] >= 0) & (a[..., 7] == b[..., 7]) & (a[..., 3] == b[..., 3])
+        if not bool(pair.any()):
+            return 0.0
+        d = b[..., 0:3].contiguous().view(torch.float32)[pair] - a[..., 0:3].contiguous().view(torch.float32)[pair]
+        return float(torch.sqrt((d * d).sum(1)).median())
+    g = np.asarray(r).reshape(h, w, 8)
+    a, b = g[:, :-1], g[:, 1:]
+    pair = (a[..., 7] >= 0) & (a[..., 7] == b[..., 7]) & (a[..., 3] == b[..., 3])
+    if not pair.any():
+        return 0.0
+    d = np.ascontiguousarray(b[..., 0:3]).view(np.float32)[pair] - np.ascontiguousarray(a[..., 0:3]).view(np.float32)[pair]
+    d = np.sort(np.sqrt((d * d).sum(1)))
+    return float(d[(len(d) - 1) // 2])
+
+
+def filter_sigmas(pitch):
+    """(sigma_distance, sigma_plane) for Scene.atlas_filter from `texel_pitch`'s answer: 3 * pitch and pitch / 2.  These are
+    CONVENTIONS, not measurements.  At three pitches the outermost ring of the 5 x 5 footprint -- two texels away along a row,
+    2 * sqrt(2) along a diagonal, times the step -- still has weight (1 - (2 sqrt 2 / 3)^2 = 1/9 at the corners), so a flat
+    chart is smoothed by the whole kernel; half a pitch off the centre's tangent plane is more than the texels of a flat chart
+    ever are and less than the next texel round a right-angled crease.  A scene with fine curved detail wants a larger
+    sigma_plane, a noisier gather a larger sigma_distance.  ValueError for a pitch that is not positive and finite (an atlas
+    without a pair of neighbours has nothing to filter)."""
+    pitch = float(pitch)
+    if not (math.isfinite(pitch) and pitch > 0.0):
+        raise ValueError(f"filter_sigmas: a texel pitch of {pitch} (positive and finite)")
+    return 3.0 * pitch, 0.5 * pitch
