@@ -195,6 +195,15 @@ typedef struct ptrt_atlas_texel {
     int32_t mesh;       /* uploaded mesh index, -1 = no triangle covers this texel's centre              */
 } ptrt_atlas_texel;
 
+/* One ray hit's answer from ptrt_atlas_sample / ptrt_query_lightmap: the baked atlas read at the hit, 32 bytes. */
+typedef struct ptrt_lightmap_sample {
+    float rgb[3];   /* the atlas's colour at the hit: sum of w * texel.rgb over the taps used, divided by `weight`; 0 without a tap */
+    float weight;   /* sum of the weights of the taps used (bilinear: <= about 1; nearest: 1 or 0)                                   */
+    float x, y;     /* the hit in the atlas, texel units (a texel's centre is (i + 0.5, j + 0.5)); 0 without a chart                */
+    int32_t face;   /* mesh-local face of the hit (ptrt_hit.face_index), -1 on a miss                                               */
+    int32_t mesh;   /* ptrt_hit.mesh_index, -1 on a miss                                                                            */
+} ptrt_lightmap_sample;
+
 /* Per-frame counters of the trace stage (Mrays/s numerator). */
 typedef struct ptrt_stats {
     uint64_t extension_rays; /* traceRay calls   (intersection.cuh:526) */
@@ -810,6 +819,57 @@ int ptrt_atlas_dilate(ptrt_ctx *ctx, float *d_a, float *d_b, int atlas_w, int at
  * memory that is not the context's device memory or too small (byte counts in size_t).  (ABI 6, addition only.) */
 int ptrt_atlas_filter(ptrt_ctx *ctx, const ptrt_atlas_texel *d_texels, float *d_a, float *d_b, int atlas_w, int atlas_h, int passes,
                       float sigma_distance, float sigma_plane, int normal_power);
+
+/* The consumer of a bake: the atlas ptrt_atlas_dilate leaves, read back at ray hits.  Everything is in DEVICE memory:
+ *   d_charts       n_chart_faces * 6 floats, the layout of ptrt_atlas_texels' d_uv -- the (x, y) of corners v0, v1, v2 of a face in
+ *                  texel units -- with the charts of several meshes concatenated;
+ *   d_chart_first  one int32 per uploaded mesh: the index in d_charts of that mesh's face 0; negative: the mesh has no lightmap;
+ *   d_image        atlas_w * atlas_h float4 {r, g, b, valid};
+ *   mode           PTRT_LIGHTMAP_NEAREST or PTRT_LIGHTMAP_BILINEAR.
+ * ptrt_atlas_sample answers for n ptrt_hit records H of the kind ptrt_query_rays(PTRT_QUERY_CLOSEST) writes; ptrt_query_lightmap
+ * traces n rays itself, as that query would, and answers for their hits without the 64-byte records ever being written: the
+ * same bytes with one launch less and 128 bytes less traffic per ray.  One ptrt_lightmap_sample per record or ray.
+ * The sample is ONE definition in fp32, every operation rounded on its own (no contraction), `/` the IEEE quotient:
+ *   1. H.hit == 0 (a miss):  {0, 0, 0,  0,  0, 0,  -1, -1}.
+ *   2. m = H.mesh_index, f = H.face_index, first = d_chart_first[m].  If first < 0, f < 0 or first + f >= n_chart_faces (the sum
+ *      in 64 bits) there is no chart:  {0, 0, 0,  0,  0, 0,  f, m}.  The range check is part of the definition -- the table is
+ *      device memory the host cannot vet without a synchronisation, and a bad table must not read outside d_charts.  So is, for
+ *      the same reason, a record of ptrt_atlas_sample whose m is not an uploaded mesh (m < 0 or m >= the mesh count): no chart,
+ *      and d_chart_first is not read.
+ *   3. (x0, y0, x1, y1, x2, y2) = d_charts[(first + f) * 6 ..];  b0 = (1 - H.u) - H.v;  x = (b0*x0 + H.u*x1) + H.v*x2, y likewise.
+ *      H.u belongs to corner v1 and H.v to v2 -- the triangle test's u multiplies e1 -- : the barycentrics ptrt_atlas_texels puts
+ *      through (v0 + b1*e1) + b2*e2, so the texel whose centre a chart maps to a surface point is the one a hit at that point
+ *      finds.  If x or y is not finite:  {0, 0, 0,  0,  x, y,  f, m}.
+ *   4. A tap (i, j) is usable iff 0 <= i < atlas_w, 0 <= j < atlas_h (integers) and d_image[j * atlas_w + i].valid != 0.  Taps are
+ *      skipped by selection, never by a product with zero: a NaN or an infinity in an unusable texel reaches nothing
+ *      (ptrt_atlas_filter's rule).  Taps are NOT clamped at the atlas border; they are skipped and the rest renormalised.
+ *        NEAREST   fi = floor(x), fj = floor(y).  The tap (fi, fj), if usable: rgb = the texel's three words copied, weight = 1;
+ *                  otherwise rgb = 0 and weight = 0.
+ *        BILINEAR  tx = x - 0.5f, ty = y - 0.5f;  fi = floor(tx), fj = floor(ty);  fx = tx - fi, fy = ty - fj;  gx = 1 - fx,
+ *                  gy = 1 - fy.  The taps, in this order: (i0, j0) with w = gx*gy, (i0+1, j0) with fx*gy, (i0, j0+1) with gx*fy,
+ *                  (i0+1, j0+1) with fx*fy.  A usable tap with w > 0 adds num += w * rgb per channel (the product rounded, then
+ *                  the sum) and den += w.  den > 0: rgb = num / den, weight = den; otherwise both are 0.
+ *      Before any conversion to an integer, fi or fj outside [-1, 2^28] -- compared as floats, as the rasteriser does -- means no
+ *      tap is usable: an atlas has at most 2^28 texels, so such a value has none anyway.
+ *   5. The record is {rgb, weight, x, y, f, m}.
+ * A hit on a face's back side samples the same texel as one on its front: the bake's normal is the front side's, and a caller
+ * who cares reads front_face from ptrt_query_rays.  tests/lightmap_sample_restatement.py states all of it in numpy.
+ * Ordering and side effects are ptrt_query_rays': enqueued on the context's stream; no allocation, copy or synchronisation;
+ * generator states, frame buffers, counters and both timing histories are left alone; ptrt_query_lightmap walks the traversal a
+ * frame would (ptrt_get_option "query_pmode" says which).  PTRT_E_INVALID (nothing enqueued, d_out untouched) for n < 0,
+ * n_chart_faces < 1, atlas sizes outside ptrt_atlas_dilate's, a mode other than the two, a NULL pointer, d_image, d_out or d_hits
+ * not 16-byte aligned, d_charts, d_chart_first, d_origins or d_directions not 4-byte aligned, memory that is not the context's
+ * device memory or too small (d_chart_first: one entry per uploaded mesh; byte counts in size_t), d_out overlapping an input.
+ * PTRT_E_NOT_READY before geometry is uploaded (ptrt_atlas_sample needs the scene for the mesh count only); n == 0 is PTRT_OK.
+ * (ABI 6, additions only.) */
+#define PTRT_LIGHTMAP_NEAREST 0
+#define PTRT_LIGHTMAP_BILINEAR 1
+int ptrt_atlas_sample(ptrt_ctx *ctx, const ptrt_hit *d_hits, int n, const float *d_charts, int n_chart_faces,
+                      const int32_t *d_chart_first, const float *d_image, int atlas_w, int atlas_h, int mode,
+                      ptrt_lightmap_sample *d_out);
+int ptrt_query_lightmap(ptrt_ctx *ctx, const float *d_origins, const float *d_directions, int n, const float *d_charts,
+                        int n_chart_faces, const int32_t *d_chart_first, const float *d_image, int atlas_w, int atlas_h,
+                        int mode, ptrt_lightmap_sample *d_out);
 
 /* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
  * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small

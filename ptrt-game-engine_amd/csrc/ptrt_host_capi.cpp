@@ -467,6 +467,21 @@ int hs_atlas_filter(void *s, const void *d_texels, void *d_a, void *d_b, int atl
                                                        normal_power) == d_b
                       ? 1 : 0);
 }
+int hs_atlas_sample(void *s, const void *d_hits, int n, const void *d_charts, int n_chart_faces, const void *d_chart_first,
+                    const void *d_image, int atlas_w, int atlas_h, int mode, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->atlasSample(static_cast<const ptrt_hit *>(d_hits), n, static_cast<const float *>(d_charts), n_chart_faces,
+                                                static_cast<const int32_t *>(d_chart_first), static_cast<const float *>(d_image), atlas_w,
+                                                atlas_h, mode, static_cast<ptrt_lightmap_sample *>(d_out)));
+    return 0;
+}
+int hs_query_lightmap(void *s, const void *d_origins, const void *d_dirs, int n, const void *d_charts, int n_chart_faces,
+                      const void *d_chart_first, const void *d_image, int atlas_w, int atlas_h, int mode, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryLightmap(static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n,
+                                                  static_cast<const float *>(d_charts), n_chart_faces,
+                                                  static_cast<const int32_t *>(d_chart_first), static_cast<const float *>(d_image), atlas_w,
+                                                  atlas_h, mode, static_cast<ptrt_lightmap_sample *>(d_out)));
+    return 0;
+}
 int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
     HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;

@@ -1,7 +1,8 @@
 // ptrt_query.hip.h -- the device queries of the C ABI: closest hit and occlusion (ptrt_trace_rays, ptrt_query_rays), path-traced
 // radiance (ptrt_query_radiance), light probes (ptrt_query_probes), lightmap texels (ptrt_query_irradiance, with
 // ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights), the lightmap
-// atlas around them (ptrt_atlas_texels, ptrt_atlas_filter, ptrt_atlas_dilate: no traversal) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
+// atlas around them (ptrt_atlas_texels, ptrt_atlas_filter, ptrt_atlas_dilate: no traversal), the baked atlas read back at ray hits
+// (ptrt_atlas_sample; ptrt_query_lightmap, which traces the rays itself) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
 // ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
 // (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
 // check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
@@ -608,6 +609,117 @@ int ptrt_atlas_filter(ptrt_ctx *c, const ptrt_atlas_texel *d_texels, float *d_a,
         HIP_TRY(c, hipGetLastError());
     }
     return PTRT_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+// What ptrt_atlas_sample and ptrt_query_lightmap refuse alike, up to the device: the lightmap's four arguments, the output, and
+// the caller's own inputs `ins` (the hit records; the rays), which d_out must not overlap either.  `done`: n == 0, nothing to do.
+int check_lightmap(ptrt_ctx *c, const char *fn, int n, const float *d_charts, int n_chart_faces, const int32_t *d_chart_first,
+                   const float *d_image, int atlas_w, int atlas_h, int mode, ptrt_lightmap_sample *d_out, std::initializer_list<Span> ins,
+                   size_t in_align, pt::LightmapParams &L, bool &done) {
+    static_assert(sizeof(pt::LightmapSample) == sizeof(ptrt_lightmap_sample) && sizeof(ptrt_lightmap_sample) == 32,
+                  "LightmapSample must mirror ptrt_lightmap_sample");
+    static_assert(pt::LIGHTMAP_NEAREST == PTRT_LIGHTMAP_NEAREST && pt::LIGHTMAP_BILINEAR == PTRT_LIGHTMAP_BILINEAR, "the modes");
+    done = false;
+    if (n < 0 || n_chart_faces < 1 || !d_charts || !d_chart_first || !d_image || !d_out || !atlas_size_ok(atlas_w, atlas_h) ||
+        (mode != PTRT_LIGHTMAP_NEAREST && mode != PTRT_LIGHTMAP_BILINEAR))
+        return fail(c, PTRT_E_INVALID,
+                    "%s: bad argument (n %d, charts %p, n_chart_faces %d: >= 1, chart_first %p, image %p, atlas %d x %d: 1 x 1 .. 2^28 "
+                    "texels, mode %d: 0 or 1, out %p)",
+                    fn, n, (const void *)d_charts, n_chart_faces, (const void *)d_chart_first, (const void *)d_image, atlas_w, atlas_h, mode,
+                    (const void *)d_out);
+    for (const Span &s : ins)
+        if (!s.p || ((uintptr_t)s.p & (in_align - 1)))
+            return fail(c, PTRT_E_INVALID, "%s: %s %p must not be NULL and must be %zu-byte aligned", fn, s.name, s.p, in_align);
+    if (!aligned16(d_image) || !aligned16(d_out) || ((uintptr_t)d_charts & 3u) || ((uintptr_t)d_chart_first & 3u))
+        return fail(c, PTRT_E_INVALID, "%s: image %p and out %p must be 16-byte aligned, charts %p and chart_first %p 4-byte", fn,
+                    (const void *)d_image, (const void *)d_out, (const void *)d_charts, (const void *)d_chart_first);
+    if (!c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "%s: geometry not uploaded", fn);
+    if (n == 0) {
+        done = true;
+        return PTRT_OK;
+    }
+    const size_t out_bytes = (size_t)n * sizeof(ptrt_lightmap_sample);
+    const Span fixed[3] = {{"charts", d_charts, (size_t)n_chart_faces * 24},
+                           {"chart_first", d_chart_first, (size_t)c->n_meshes * sizeof(int32_t)},
+                           {"image", d_image, (size_t)atlas_w * (size_t)atlas_h * 16}};
+    const auto apart = [&](const Span &s) {
+        const uintptr_t x = (uintptr_t)d_out, y = (uintptr_t)s.p;
+        return x < y ? y - x >= out_bytes : x - y >= s.bytes;
+    };
+    for (const Span &s : fixed)
+        if (!apart(s))
+            return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, (const void *)d_out, out_bytes, s.name, s.p,
+                        s.bytes);
+    for (const Span &s : ins)
+        if (!apart(s))
+            return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, (const void *)d_out, out_bytes, s.name, s.p,
+                        s.bytes);
+    if (int rc = set_device(c))
+        return rc;
+    if (int rc = check_spans(c, fn, ins))
+        return rc;
+    if (int rc = check_spans(c, fn, {fixed[0], fixed[1], fixed[2], {"out", d_out, out_bytes}}))
+        return rc;
+    L.charts = d_charts;
+    L.chart_first = d_chart_first;
+    L.image = reinterpret_cast<const float4 *>(d_image);
+    L.n_chart_faces = n_chart_faces;
+    L.n_meshes = c->n_meshes;
+    L.aw = atlas_w;
+    L.ah = atlas_h;
+    L.mode = mode;
+    return PTRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ptrt_atlas_sample(ptrt_ctx *c, const ptrt_hit *d_hits, int n, const float *d_charts, int n_chart_faces, const int32_t *d_chart_first,
+                      const float *d_image, int atlas_w, int atlas_h, int mode, ptrt_lightmap_sample *d_out) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_atlas_sample: bad context");
+    pt::LightmapParams L{};
+    bool done = false;
+    if (int rc = check_lightmap(c, "ptrt_atlas_sample", n, d_charts, n_chart_faces, d_chart_first, d_image, atlas_w, atlas_h, mode, d_out,
+                                {{"hits", d_hits, (size_t)(n > 0 ? n : 0) * sizeof(ptrt_hit)}}, 16, L, done))
+        return rc;
+    if (done)
+        return PTRT_OK;
+    c->touched = true;
+    // atlas_sample_kernel (pt_lightmap.hip.h): one thread per record; n < 2^31, so the grid's x extent fits
+    hipLaunchKernelGGL(pt::atlas_sample_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const float4 *>(d_hits), (size_t)n, L, reinterpret_cast<float4 *>(d_out));
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_query_lightmap(ptrt_ctx *c, const float *d_origins, const float *d_directions, int n, const float *d_charts, int n_chart_faces,
+                        const int32_t *d_chart_first, const float *d_image, int atlas_w, int atlas_h, int mode,
+                        ptrt_lightmap_sample *d_out) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_lightmap: bad context");
+    pt::LightmapParams L{};
+    bool done = false;
+    const size_t rays = (size_t)(n > 0 ? n : 0);
+    if (int rc = check_lightmap(c, "ptrt_query_lightmap", n, d_charts, n_chart_faces, d_chart_first, d_image, atlas_w, atlas_h, mode, d_out,
+                                {{"origins", d_origins, rays * 12}, {"directions", d_directions, rays * 12}}, 4, L, done))
+        return rc;
+    if (done)
+        return PTRT_OK;
+    QueryPlan P;
+    if (int rc = plan_query(c, false, 0, 0, P))
+        return rc;
+    // lightmap_query_kernel (pt_lightmap.hip.h): ray_query_kernel's grid, chunks of 64 rays
+    float4 *o = reinterpret_cast<float4 *>(d_out);
+    return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+        return launch_persistent(c, pt::lightmap_query_kernel<G, PM>, P.lds, (rays + 63) / 64, false, P.K, d_origins, d_directions, rays, L, o);
+    });
 }
 
 int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins, float *d_directions) {

@@ -1028,6 +1028,28 @@ class Scene {
               "Atlas filter failed");
         return (passes & 1) ? d_b : d_a;
     }
+    // The baked atlas read back at ray hits (ptrt_atlas_sample): one 32-byte ptrt_lightmap_sample per ptrt_hit record of
+    // queryClosestDevice -- the atlas's colour at the hit, nearest (mode PTRT_LIGHTMAP_NEAREST) or bilinear over its valid taps.
+    // d_charts: the d_uv of atlasTexels for every lightmapped mesh, concatenated (n_chart_faces * 6 floats); d_chart_first: per
+    // UPLOADED mesh (ptrt_hit.mesh_index counts those) the index in d_charts of its face 0, negative for a mesh without a
+    // lightmap; d_image: the atlas_w * atlas_h float4 {r, g, b, valid} atlasDilate leaves.  Needs the scene for its mesh count only.
+    void atlasSample(const ptrt_hit *d_hits, int n, const float *d_charts, int n_chart_faces, const int32_t *d_chart_first,
+                     const float *d_image, int atlas_w, int atlas_h, int mode, ptrt_lightmap_sample *d_out) {
+        needBackend();
+        check(ptrt_atlas_sample(ctx, d_hits, n, d_charts, n_chart_faces, d_chart_first, d_image, atlas_w, atlas_h, mode, d_out),
+              "Atlas sampling failed");
+    }
+    // The same for n rays traced here (ptrt_query_lightmap): what atlasSample gives for queryClosestDevice's records of these
+    // rays, byte for byte, in one launch and without the records.  Commits what queryClosestDevice commits.
+    void queryLightmap(const float *d_origins, const float *d_dirs, int n, const float *d_charts, int n_chart_faces,
+                       const int32_t *d_chart_first, const float *d_image, int atlas_w, int atlas_h, int mode,
+                       ptrt_lightmap_sample *d_out) {
+        needBackend();
+        updateAccelerationStructures();
+        check(ptrt_query_lightmap(ctx, d_origins, d_dirs, n, d_charts, n_chart_faces, d_chart_first, d_image, atlas_w, atlas_h, mode,
+                                  d_out),
+              "Lightmap query failed");
+    }
     // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
     // tile rows * width * 3 floats each, in the order of the colour buffer.
     void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {

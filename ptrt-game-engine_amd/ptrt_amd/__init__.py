@@ -180,6 +180,10 @@ DIRECT_DTYPE = np.dtype([("irradiance", "<f4", 3), ("lit_fraction", "<f4"), ("sh
 assert DIRECT_DTYPE.itemsize == C.sizeof(Direct) == 32
 ATLAS_TEXEL_DTYPE = np.dtype([("position", "<f4", 3), ("face", "<i4"), ("normal", "<f4", 3), ("mesh", "<i4")])
 assert ATLAS_TEXEL_DTYPE.itemsize == C.sizeof(AtlasTexel) == 32
+LIGHTMAP_SAMPLE_DTYPE = np.dtype([("rgb", "<f4", 3), ("weight", "<f4"), ("x", "<f4"), ("y", "<f4"), ("face", "<i4"), ("mesh", "<i4")])
+assert LIGHTMAP_SAMPLE_DTYPE.itemsize == 32
+LIGHTMAP_NEAREST, LIGHTMAP_BILINEAR = 0, 1  # PTRT_LIGHTMAP_*
+LIGHTMAP_MODES = dict(nearest=LIGHTMAP_NEAREST, bilinear=LIGHTMAP_BILINEAR)
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
@@ -228,6 +232,8 @@ _sig("ptrt_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.
 _sig("ptrt_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("ptrt_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("ptrt_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
+_sig("ptrt_atlas_sample", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("ptrt_query_lightmap", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
@@ -363,6 +369,8 @@ _sig("hs_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_f
 _sig("hs_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("hs_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("hs_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
+_sig("hs_atlas_sample", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("hs_query_lightmap", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -510,6 +518,25 @@ def atlas_fields(records):
     for name, (a, b) in ATLAS_COLUMNS.items():
         col = records[:, a:b]
         out[name] = col[:, 0] if b - a == 1 else col.view(f32)
+    return out
+
+
+# columns of the (n, 8) int32 rows of Scene.atlas_sample / query_lightmap: the fields of ptrt_lightmap_sample / LIGHTMAP_SAMPLE_DTYPE
+LIGHTMAP_SAMPLE_COLUMNS = dict(rgb=(0, 3, True), weight=(3, 4, True), x=(4, 5, True), y=(5, 6, True), face=(6, 7, False),
+                               mesh=(7, 8, False))
+
+
+def lightmap_sample_fields(records):
+    """Named views of atlas_sample's and query_lightmap's (n, 8) int32 rows (a tensor or an array): rgb (n, 3), weight, x and y
+    (n,) reinterpreted as float32; face and mesh int32, (n,)."""
+    import torch
+    f32 = torch.float32 if _is_tensor(records) else np.float32
+    out = {}
+    for name, (a, b, is_f) in LIGHTMAP_SAMPLE_COLUMNS.items():
+        col = records[:, a:b]
+        if is_f:
+            col = col.view(f32)
+        out[name] = col[:, 0] if b - a == 1 else col
     return out
 
 
@@ -1320,6 +1347,75 @@ class Scene:
             self._h, _vp(texels.data_ptr()), _vp(image.data_ptr()), _vp(other.data_ptr()), w, h, passes, sigma_distance, sigma_plane,
             normal_power))))
         return other if where[0] else image
+
+    def _lightmap_inputs(self, what, n, charts, chart_first, image, mode, out):
+        self._device_tensor(f"{what}: charts", charts, 6, "torch.float32")
+        if charts.shape[0] < 1:
+            raise ValueError(f"{what}: charts has no rows")
+        if not _is_tensor(chart_first) or chart_first.dim() != 1:
+            raise ValueError(f"{what}: chart_first: needs an (M,) int32 tensor on the scene's device, one entry per uploaded mesh")
+        self._device_tensor(f"{what}: chart_first", chart_first.view(-1, 1) if chart_first.is_contiguous() else chart_first[:, None],
+                            1, "torch.int32")
+        if not _is_tensor(image) or image.dim() != 3:
+            raise ValueError(f"{what}: image: needs a torch tensor of shape (H, W, 4) on the scene's device")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        if h < 1 or w < 1 or h * w > 2 ** 28:
+            raise ValueError(f"{what}: a {w} x {h} atlas (1 x 1 .. 2^28 texels)")
+        if not image.is_contiguous():
+            raise ValueError(f"{what}: image: tensors must be contiguous")
+        self._device_tensor(f"{what}: image", image.view(h * w, -1), 4, "torch.float32")
+        if n >= 2 ** 31:
+            raise ValueError(f"{what}: {n} rows (at most 2^31 - 1 per call)")
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.int32, device=image.device)
+        else:
+            self._device_tensor(f"{what}: out", out, 8, "torch.int32")
+            if out.shape[0] != n:
+                raise ValueError(f"{what}: out has {out.shape[0]} rows for {n}")
+        return w, h, LIGHTMAP_MODES[mode], out
+
+    def atlas_sample(self, hits, charts, chart_first, image, mode="bilinear", out=None):
+        """The baked atlas read at ray hits (ptrt_atlas_sample).  torch tensors on this scene's device, contiguous, read in
+        place: `hits`, query_closest's (n, 16) int32 rows; `charts`, (F, 6) float32, the `uv` of atlas_texels for every
+        lightmapped mesh, concatenated; `chart_first`, (M,) int32, per uploaded mesh the row of `charts` that holds its face 0,
+        negative for a mesh without a lightmap (`lightmap.chart_table` makes both); `image`, the (H, W, 4) float32 atlas
+        {r, g, b, valid} that atlas_dilate leaves.  `mode`: 'nearest' -- the texel the hit falls in -- or 'bilinear' -- the
+        four texels round it, the invalid ones and those outside the atlas skipped and the rest renormalised.  Returns an
+        (n, 8) int32 tensor, one 32-byte `ptrt_lightmap_sample` per row (`lightmap_sample_fields` names the columns): rgb (0:3)
+        and the weight of the taps used (3; 0: nothing to sample) as float32 bits, the hit in the atlas in texel units (4, 5,
+        float32 bits), the hit's face (6) and mesh (7), -1 on a miss; `out` takes such a tensor.  No synchronisation."""
+        if mode not in LIGHTMAP_MODES:
+            raise ValueError(f"atlas_sample: mode {mode!r} ('nearest' or 'bilinear')")
+        self._device_tensor("atlas_sample: hits", hits, 16, "torch.int32")
+        n = int(hits.shape[0])
+        w, h, mode, out = self._lightmap_inputs("atlas_sample", n, charts, chart_first, image, mode, out)
+        if n == 0:
+            return out
+        self._enqueue_between_streams(image.device, lambda: self._chk(lib.hs_atlas_sample(
+            self._h, _vp(hits.data_ptr()), n, _vp(charts.data_ptr()), int(charts.shape[0]), _vp(chart_first.data_ptr()),
+            _vp(image.data_ptr()), w, h, mode, _vp(out.data_ptr()))))
+        return out
+
+    def query_lightmap(self, origins, directions, charts, chart_first, image, mode="bilinear", out=None):
+        """The baked atlas at the closest hit of every ray (ptrt_query_lightmap): what `atlas_sample(query_closest(origins,
+        directions), ..)` returns, byte for byte, from one kernel that never writes the hit records.  origins and directions:
+        (n, 3) float32 tensors on this scene's device, contiguous; the rest as for atlas_sample.  A lightmapped view of the
+        scene is `camera_rays`, then this, then `lightmap.shade_samples`.  No synchronisation."""
+        if mode not in LIGHTMAP_MODES:
+            raise ValueError(f"query_lightmap: mode {mode!r} ('nearest' or 'bilinear')")
+        self._device_tensor("query_lightmap: origins", origins, 3, "torch.float32")
+        self._device_tensor("query_lightmap: directions", directions, 3, "torch.float32")
+        n = int(origins.shape[0])
+        if directions.shape[0] != n:
+            raise ValueError(f"query_lightmap: {n} origins, {directions.shape[0]} directions")
+        w, h, mode, out = self._lightmap_inputs("query_lightmap", n, charts, chart_first, image, mode, out)
+        if n == 0:
+            return out
+        self._enqueue_between_streams(image.device, lambda: self._chk(lib.hs_query_lightmap(
+            self._h, _vp(origins.data_ptr()), _vp(directions.data_ptr()), n, _vp(charts.data_ptr()), int(charts.shape[0]),
+            _vp(chart_first.data_ptr()), _vp(image.data_ptr()), w, h, mode, _vp(out.data_ptr()))))
+        return out
 
     def camera_rays(self, frame, sample=0):
         """(origins, directions): (rows * width, 3) float32 tensors on this scene's device holding the primary rays

@@ -12,7 +12,11 @@ Scene.atlas_texels makes the texels of an uploaded mesh from its UV charts and S
 `triangle_charts` (charts for a mesh that never had UVs), `uv_to_texels`, `covered`, `atlas_inputs` and `scatter` stand between
 them and the queries; these take torch tensors as well as arrays and answer in kind.  Scene.atlas_filter stands between
 `scatter` and the dilation -- the order of a bake is scatter, atlas_filter, atlas_dilate -- and `texel_pitch` and
-`filter_sigmas` give it its two ranges."""
+`filter_sigmas` give it its two ranges.
+
+Scene.atlas_sample and Scene.query_lightmap read the finished atlas back at ray hits: `chart_table` joins the meshes' charts into
+the table they take, `sample_rgb` and `sample_weight` read their rows, `shade_samples` turns them into a Lambertian preview.  A
+lightmapped view of a scene is Scene.camera_rays, then Scene.query_lightmap, then `shade_samples`."""
 import math
 
 import numpy as np
@@ -264,3 +268,100 @@ def filter_sigmas(pitch):
     if not (math.isfinite(pitch) and pitch > 0.0):
         raise ValueError(f"filter_sigmas: a texel pitch of {pitch} (positive and finite)")
     return 3.0 * pitch, 0.5 * pitch
+
+
+def chart_table(charts_per_mesh):
+    """(charts (sum F, 6) float32, chart_first (M,) int32) for Scene.atlas_sample and Scene.query_lightmap from a list with one
+    entry per UPLOADED mesh, in upload order (the order ptrt_hit.mesh_index counts in): the (F_m, 6) charts Scene.atlas_texels
+    took for that mesh -- an array or a tensor --, or None for a mesh without a lightmap, which gets chart_first -1.  Arrays,
+    unless an entry is a tensor: then tensors on that tensor's device.  ValueError for an empty list, a list of Nones, an entry
+    that is not (F, 6) with F >= 1, and more than 2^31 - 1 faces."""
+    entries = list(charts_per_mesh)
+    if not entries:
+        raise ValueError("chart_table: no meshes")
+    like = next((c for c in entries if hasattr(c, "cpu")), None)
+    parts, first, total = [], [], 0
+    for m, c in enumerate(entries):
+        if c is None:
+            first.append(-1)
+            continue
+        if hasattr(c, "cpu"):
+            c = c.detach().cpu().numpy()
+        c = np.asarray(c)
+        if c.ndim != 2 or c.shape[1] != 6 or c.shape[0] < 1:
+            raise ValueError(f"chart_table: mesh {m}: charts of shape {tuple(c.shape)}, expected (F, 6) with F >= 1")
+        first.append(total)
+        total += c.shape[0]
+        parts.append(c.astype(np.float32))
+    if not parts:
+        raise ValueError("chart_table: no mesh has charts")
+    if total >= 2 ** 31:
+        raise ValueError(f"chart_table: {total} faces (at most 2^31 - 1)")
+    charts, chart_first = np.ascontiguousarray(np.concatenate(parts)), np.asarray(first, np.int32)
+    if like is not None:
+        import torch
+        return torch.from_numpy(charts).to(like.device), torch.from_numpy(chart_first).to(like.device)
+    return charts, chart_first
+
+
+def _sample_rows(rows):
+    if rows.ndim != 2 or rows.shape[1] != 8 or "int32" not in str(rows.dtype):
+        raise ValueError(f"lightmap: sample rows of shape {tuple(rows.shape)} and {rows.dtype}, expected (n, 8) int32")
+    return rows
+
+
+def sample_rgb(rows):
+    """(n, 3) float32: the colour columns of Scene.atlas_sample's / query_lightmap's (n, 8) int32 rows -- the atlas at the hit,
+    zeros where weight is 0 (a tensor for a tensor, an array for an array)"""
+    r = _sample_rows(rows)
+    if hasattr(r, "cpu"):
+        import torch
+        return r[:, 0:3].contiguous().view(torch.float32)
+    return np.ascontiguousarray(np.asarray(r)[:, 0:3]).view(np.float32)
+
+
+def sample_weight(rows):
+    """(n,) float32: the weight column of those rows -- the sum of the weights of the taps used, 0 where there was nothing to
+    sample: a miss, a mesh without a chart, a footprint with no valid texel"""
+    r = _sample_rows(rows)
+    if hasattr(r, "cpu"):
+        import torch
+        return r[:, 3].contiguous().view(torch.float32)
+    return np.ascontiguousarray(np.asarray(r)[:, 3]).view(np.float32)
+
+
+def shade_samples(rows, albedo, emission=None, background=(0.0, 0.0, 0.0)):
+    """(n, 3) float32, the Lambertian preview of a bake: for a hit on mesh m  (albedo[m] * rgb) / pi + emission[m]  -- the baked
+    irradiance times the surface's diffuse reflectance over pi, plus what the surface emits --, `background` on a miss (mesh
+    < 0).  Each step is one float32 operation: the product, the quotient by float32(pi), the sum.  albedo and emission: (M, 3),
+    one row per uploaded mesh (emission None: zeros).  Arrays or tensors, answered in the kind of `rows`.
+
+    A lightmapped view of a scene is Scene.camera_rays, then Scene.query_lightmap, then this."""
+    r = _sample_rows(rows)
+    rgb = sample_rgb(r)
+    if hasattr(r, "cpu"):
+        import torch
+        dev = r.device
+        a = torch.as_tensor(albedo, dtype=torch.float32, device=dev)
+        e = torch.zeros_like(a) if emission is None else torch.as_tensor(emission, dtype=torch.float32, device=dev)
+        bg = torch.as_tensor(background, dtype=torch.float32, device=dev)
+        mesh = r[:, 7].to(torch.int64)
+    else:
+        r = np.asarray(r)
+        a = np.asarray(albedo.cpu() if hasattr(albedo, "cpu") else albedo, np.float32)
+        e = np.zeros_like(a) if emission is None else np.asarray(emission.cpu() if hasattr(emission, "cpu") else emission, np.float32)
+        bg = np.asarray(background, np.float32)
+        mesh = r[:, 7].astype(np.int64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1 or tuple(e.shape) != tuple(a.shape) or tuple(bg.shape) != (3,):
+        raise ValueError(f"shade_samples: albedo {tuple(a.shape)}, emission {tuple(e.shape)}, background {tuple(bg.shape)}: "
+                         "expected (M, 3), (M, 3) and (3,)")
+    if mesh.shape[0] and int(mesh.max()) >= a.shape[0]:
+        raise ValueError(f"shade_samples: a hit on mesh {int(mesh.max())}, albedo has {a.shape[0]} rows")
+    hit = mesh >= 0
+    m = mesh * hit  # (a miss reads row 0 and is replaced below)
+    if hasattr(rgb, "cpu"):
+        import torch
+        lit = (a[m] * rgb) / torch.tensor(math.pi, dtype=torch.float32, device=rgb.device) + e[m]
+        return torch.where(hit[:, None], lit, bg[None, :].expand_as(lit)).contiguous()
+    lit = (a[m] * rgb) / np.float32(math.pi) + e[m]
+    return np.ascontiguousarray(np.where(hit[:, None], lit, bg[None, :]).astype(np.float32))
