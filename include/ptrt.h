@@ -187,6 +187,16 @@ typedef struct ptrt_direct {
     float reserved[3];        /* 0.0f                                                                     */
 } ptrt_direct;
 
+/* One lightmap texel's answer from ptrt_query_bounce: the analytic lights' one-bounce term over the texel's n_dirs gather rays
+ * and the Q = light_count * n_shadow light samples at each ray's hit, 32 bytes. */
+typedef struct ptrt_bounce {
+    float radiance[3];        /* mean over k of B(t, k); irradiance = pi * this for cosine-distributed directions */
+    float lit_fraction;       /* terms walked and not blocked, over (float)(n_dirs * Q)                            */
+    float shadowed_fraction;  /* terms blocked, over (float)(n_dirs * Q)                                           */
+    float hit_fraction;       /* mean over k of (the gather ray hit ? 1.0f : 0.0f)                                 */
+    float reserved[2];        /* 0.0f                                                                              */
+} ptrt_bounce;
+
 /* One texel of a lightmap atlas from ptrt_atlas_texels, 32 bytes. */
 typedef struct ptrt_atlas_texel {
     float position[3];  /* world                                                                        */
@@ -652,7 +662,7 @@ int ptrt_query_probes(ptrt_ctx *ctx, const float *d_positions, int n_probes, con
  * L(t,k), the first-hit depth and the object id of ray (t, k) are BY DEFINITION what ptrt_query_radiance puts into ptrt_radiance
  * for that ray and state with the same `samples` and `max_depth` -- the quirk that a caller's ray takes no light sample at its
  * first hit included.  So the direct term of the analytic lights (ptrt_upload_lights) at the texel itself and at a gather ray's
- * first hit is absent, as it is in a frame's first vertex (ptrt_query_direct, below, bakes the term at the texel); emissive meshes, the sky and the environment map are seen, and the
+ * first hit is absent, as it is in a frame's first vertex (ptrt_query_direct, below, bakes the term at the texel, ptrt_query_bounce the term at the gather rays' first hits); emissive meshes, the sky and the environment map are seen, and the
  * lights do light every later vertex of a path.  Texel t's record holds MEANS over k:
  *     radiance[c]       L_c(t, k)                          (pi times it is the irradiance, for cosine-distributed directions)
  *     mean_distance     dist = min(depth, max_distance)    (a miss has depth 1e30f)
@@ -740,6 +750,71 @@ int ptrt_direct_rays(ptrt_ctx *ctx, const float *d_positions, const float *d_nor
 int ptrt_query_direct(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n_texels,
                       const float *d_samples2, int n_shadow, const float *d_phases /* may be NULL */, float offset,
                       int light_first, int light_count, ptrt_direct *d_out);
+
+/* Lightmap texels on DEVICE memory: the analytic lights' ONE-BOUNCE term -- light that reaches the texel after exactly one
+ * reflection off the surface a gather ray hits first.  ptrt_query_irradiance cannot see it (a caller's ray takes no light
+ * sample at its first hit) and ptrt_query_direct lights the texel itself; in a room lit by a point light it is the whole
+ * indirect term at max_depth 1 (ABI 6, addition only; no counterpart in the reference).  The inputs per texel are those of
+ * ptrt_query_irradiance -- positions, normals, `d_samples2` with n_dirs points, `d_phases` or NULL, `offset` -- and
+ * `d_shadow2` (ONE set of n_shadow points in [0,1)^2, used as given), `light_first`, `light_count`; Q = light_count * n_shadow.
+ * Every operation in float32 and separately rounded, in this order:
+ *     ray (t, k)  the origin and direction ptrt_irradiance_rays writes for (t, k); rd its direction
+ *     hit         BY DEFINITION what ptrt_query_rays(PTRT_QUERY_CLOSEST) answers for that ray: point, normal, front_face,
+ *                 mesh_index, t.  A miss adds nothing and walks nothing.
+ *     throughput  (1, 1, 1); on a back-face hit multiplied by the path's Beer-Lambert factor (path_logic.cuh:823-831 with the
+ *                 hit mesh's albedo and hit.t): the first half of a path vertex, its emission discarded
+ *   and for term q = j*n_shadow + s, shadow sample s of light light_first + j:
+ *     u1, u2      shadow2[2s], shadow2[2s+1]; with `d_phases`, u2 becomes u2 + phases[t], minus 1.0f if that sum is >= 1.0f
+ *                 (the rotation ptrt_query_direct gives its samples)
+ *     L, pdf, radiance, att, light_dist
+ *                 the path tracer's own light sample (sample_direct_lighting_with_mat, path_logic.cuh:311-381) seen from the
+ *                 hit, with ONE light in the pick (pdf_pick = 1.0f, as in ptrt_query_direct) and u1, u2 in place of the two
+ *                 draws of sample_cone_direction
+ *     origin      the PATH's shadow origin: hit.point + hit.normal*1e-4f if dot(hit.normal, L) > 0.0f, else
+ *                 hit.point - hit.normal*1e-4f
+ *     tmax        light_dist - 1e-3f
+ *     bsdf        evaluateBSDF(hit, material of hit.mesh_index, L, V = -rd), the material model a frame would use
+ *     direct      ((bsdf * radiance) * att) / pdf per channel -- the reference's operand order --, then
+ *                 clamp_vector_soft(direct, 500).  The soft clamp is KEPT: it belongs to the BSDF product.  The reference's
+ *                 mis_weight is NOT applied: an analytic light has no geometry, so no BSDF-sampled ray can reach it and there
+ *                 is no second estimator to balance against; ptrt_query_direct applies none either.
+ *     value       throughput * direct
+ *     walked      pdf > 0.0f && (direct.x > 0 || direct.y > 0 || direct.z > 0); a NaN is not walked
+ *     blocked     walked && what ptrt_query_rays(PTRT_QUERY_OCCLUDED) answers for (origin, L, tmax)
+ * Ray (t, k) keeps B(t, k)[c] -- the sum over q, in q order from +0.0f, of value[c] of the terms walked and not blocked,
+ * divided by (float)n_shadow --, its count of such (lit) terms and its count of blocked terms, each count converted to float.
+ * Texel t's record holds
+ *     radiance[c]        sum over k of B(t, k)[c] (+0.0f for a miss), divided by (float)n_dirs
+ *     lit_fraction       sum over k of the lit counts, divided by (float)(n_dirs * Q)
+ *     shadowed_fraction  sum over k of the blocked counts, divided by (float)(n_dirs * Q)
+ *     hit_fraction       sum over k of (hit ? 1.0f : 0.0f), divided by (float)n_dirs
+ * and reserved is 0.0f.  The reduction over k is EXACTLY ptrt_query_irradiance's: w, the fold by halves of a chunk padded with
+ * +0.0f, chunk sums in chunk order onto +0.0f, one IEEE division.  tests/bounce_restatement.py states it in numpy.
+ * light_count == 0 gives rows of all-zero bytes and PTRT_OK.
+ * ptrt_bounce_terms writes the terms out for hits the caller holds: `d_hits` and `d_directions` are the n_texels*n_dirs ptrt_hit
+ * records and ray directions (ray t*n_dirs + k) that ptrt_irradiance_rays and ptrt_query_rays(PTRT_QUERY_CLOSEST) make; row
+ * (t*n_dirs + k)*Q + q receives origin and L (3 floats each), tmax (1 float) and value (3 floats) as above -- as computed,
+ * walked or not, NaN included; a miss, or a record whose mesh_index has no uploaded material, gives a row of zeros.  One small
+ * kernel on the context's stream (one thread per term in blocks of 256, at most (2^31 - 1) * 256 rows per call).  It needs
+ * uploaded materials and lights, and no geometry.
+ * Ordering and side effects are those of ptrt_query_direct and ptrt_query_irradiance: enqueued on the context's stream with no
+ * allocation, copy or synchronisation; later frames are ordered behind it; neither call touches the context's generator
+ * states, frame buffers, ptrt_get_stats counters or timing histories; ptrt_get_option "query_pmode" reports the query's
+ * traversal, option "persist" sizes its grid.  PTRT_E_INVALID (nothing enqueued, every output untouched) for n_texels < 0,
+ * n_dirs < 1, n_shadow < 1, light_first < 0, light_count < 0, light_first + light_count beyond the uploaded lights, a NULL
+ * pointer other than d_phases, memory that is not the context's device memory or an allocation too small (byte counts are
+ * formed in size_t), Q or n_dirs * Q beyond 2^31 - 1, a row count beyond the limit above, or an offset that is not finite;
+ * PTRT_E_NOT_READY before geometry and materials are uploaded (ptrt_bounce_terms: materials); n_texels == 0 returns PTRT_OK
+ * and launches nothing.
+ * Not built: a lit first vertex inside ptrt_query_radiance or ptrt_query_probes; compaction of the lanes whose gather ray
+ * missed; RT-context and tile-farm variants; a back-face fraction. */
+int ptrt_bounce_terms(ptrt_ctx *ctx, const ptrt_hit *d_hits, const float *d_directions, int n_texels, int n_dirs,
+                      const float *d_shadow2, int n_shadow, const float *d_phases /* may be NULL */,
+                      int light_first, int light_count,
+                      float *d_origins, float *d_L, float *d_tmax, float *d_values);
+int ptrt_query_bounce(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n_texels,
+                      const float *d_samples2, int n_dirs, const float *d_phases /* may be NULL */, float offset,
+                      const float *d_shadow2, int n_shadow, int light_first, int light_count, ptrt_bounce *d_out);
 
 /* The front of a lightmap bake: the UV charts of uploaded mesh `mesh_index` rasterised into an atlas of atlas_w x atlas_h
  * records in DEVICE memory -- the texels whose positions and normals ptrt_query_irradiance and ptrt_query_direct take.  d_uv
@@ -1014,7 +1089,7 @@ void ptrt_farm_destroy(ptrt_farm *farm);
  *                         2: wherever PMODE 1 runs; 0: never.  ptrt_get_option "refilled" says what the last frame did.
  *                         ticket_tiles 1..16: consecutive tiles per draw from the queue (1; more only pays where the counter
  *                         itself binds -- 1 spp: 0.61 -> 0.49 ms with 4, still behind the one-tile-per-wave kernel's 0.43).
- *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance, ptrt_query_probes, ptrt_query_irradiance and ptrt_query_direct: N one-wave workgroups per CU
+ *                         `persist` N > 0 also sizes the persistent grid of ptrt_query_radiance, ptrt_query_probes, ptrt_query_irradiance, ptrt_query_direct and ptrt_query_bounce: N one-wave workgroups per CU
  *                         instead of what the kernel's occupancy holds (tests: a grid smaller than the batch's chunks).
  *   sample_sync -1|0|1    the lanes of a wave start their samples together (1) instead of each as soon as its path has ended (0):
  *                         the wave's lanes then sit at the same bounce, the light-sample phases are skipped by the whole wave at a
@@ -1103,7 +1178,7 @@ int ptrt_set_option(ptrt_ctx *ctx, const char *name, long long value);
  * timed: render_mode (0 megakernel, 1 wavefront stages, 2 asynchronous lanes), pmode (0 lock-step, 1 pairs over LDS-staged
  * triangles, 2 pair queue, 3 TLAS rounds, 4 merged queue), merged_eff (loop shape of that launch), merged_decided (0 while
  * merged = -1 is still sampling), launches.  ABI 5.  Also read-only (ABI 6): query_pmode, the traversal of the last
- * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes / ptrt_query_irradiance / ptrt_query_direct (-1 none yet), and stream, the hipStream_t the context enqueues on. */
+ * ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes / ptrt_query_irradiance / ptrt_query_direct / ptrt_query_bounce (-1 none yet), and stream, the hipStream_t the context enqueues on. */
 int ptrt_get_option(ptrt_ctx *ctx, const char *name, long long *value);
 
 /* The plan behind option "pm1_lane_groups" for leaves of `leaf_triangles` triangles, as ptrt_upload_geometry builds it; needs

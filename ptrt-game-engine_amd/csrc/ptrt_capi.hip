@@ -22,6 +22,7 @@
 #include "pt_probe.hip.h"
 #include "pt_irradiance.hip.h"
 #include "pt_direct.hip.h"
+#include "pt_bounce.hip.h"
 #include "pt_atlas.hip.h"
 #include "pt_atlas_filter.hip.h"
 #include "pt_lightmap.hip.h"

@@ -449,6 +449,22 @@ int hs_direct_rays(void *s, const void *d_positions, const void *d_normals, int 
                                                static_cast<float *>(d_dirs), static_cast<float *>(d_tmax), static_cast<float *>(d_weights)));
     return 0;
 }
+int hs_query_bounce(void *s, const void *d_positions, const void *d_normals, int n_texels, const void *d_samples2, int n_dirs,
+                    const void *d_phases, float offset, const void *d_shadow2, int n_shadow, int light_first, int light_count, void *d_out) {
+    HS_TRY(static_cast<Scene *>(s)->queryBounce(static_cast<const float *>(d_positions), static_cast<const float *>(d_normals), n_texels,
+                                                static_cast<const float *>(d_samples2), n_dirs, static_cast<const float *>(d_phases),
+                                                offset, static_cast<const float *>(d_shadow2), n_shadow, light_first, light_count,
+                                                static_cast<ptrt_bounce *>(d_out)));
+    return 0;
+}
+int hs_bounce_terms(void *s, const void *d_hits, const void *d_dirs, int n_texels, int n_dirs, const void *d_shadow2, int n_shadow,
+                    const void *d_phases, int light_first, int light_count, void *d_origins, void *d_L, void *d_tmax, void *d_values) {
+    HS_TRY(static_cast<Scene *>(s)->bounceTerms(static_cast<const ptrt_hit *>(d_hits), static_cast<const float *>(d_dirs), n_texels, n_dirs,
+                                                static_cast<const float *>(d_shadow2), n_shadow, static_cast<const float *>(d_phases),
+                                                light_first, light_count, static_cast<float *>(d_origins), static_cast<float *>(d_L),
+                                                static_cast<float *>(d_tmax), static_cast<float *>(d_values)));
+    return 0;
+}
 int hs_atlas_texels(void *s, int mesh, const void *d_uv, int atlas_w, int atlas_h, int clear, void *d_texels) {
     HS_TRY(static_cast<Scene *>(s)->atlasTexels((size_t)mesh, static_cast<const float *>(d_uv), atlas_w, atlas_h, clear != 0,
                                                 static_cast<ptrt_atlas_texel *>(d_texels)));

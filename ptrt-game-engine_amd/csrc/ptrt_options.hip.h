@@ -107,7 +107,7 @@ const Option OPTIONS[] = {
     {"merged_decided", nullptr, OPT_READ_ONLY, 0, 0,
      [](const ptrt_ctx *c) -> long long { return (c->merged >= 0 || c->tune_choice >= 0 || !c->last_merged_possible) ? 1 : 0; }},
     {"launches", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) { return (long long)c->launches; }},
-    {"query_pmode", &ptrt_ctx::query_pmode, OPT_READ_ONLY}, // traversal of the last ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes / ptrt_query_irradiance / ptrt_query_direct: 0 one ray per lane, 1..3 pairs
+    {"query_pmode", &ptrt_ctx::query_pmode, OPT_READ_ONLY}, // traversal of the last ptrt_query_rays / ptrt_trace_rays / ptrt_query_radiance / ptrt_query_probes / ptrt_query_irradiance / ptrt_query_direct / ptrt_query_bounce: 0 one ray per lane, 1..3 pairs
     // the instances' first-pass boxes (PMODE 3) match the device's root boxes and matrices
     {"inst_pre_ok", nullptr, OPT_READ_ONLY, 0, 0, [](const ptrt_ctx *c) -> long long { return c->inst_pre_ok ? 1 : 0; }},
     {"tlas_refits", &ptrt_ctx::tlas_refits, OPT_READ_ONLY}, // ptrt_refit_tlas calls since the last geometry upload

@@ -1,6 +1,7 @@
 // ptrt_query.hip.h -- the device queries of the C ABI: closest hit and occlusion (ptrt_trace_rays, ptrt_query_rays), path-traced
 // radiance (ptrt_query_radiance), light probes (ptrt_query_probes), lightmap texels (ptrt_query_irradiance, with
-// ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights), the lightmap
+// ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights; ptrt_query_bounce, with
+// ptrt_bounce_terms, for their one-bounce term), the lightmap
 // atlas around them (ptrt_atlas_texels, ptrt_atlas_filter, ptrt_atlas_dilate: no traversal), the baked atlas read back at ray hits
 // (ptrt_atlas_sample; ptrt_query_lightmap, which traces the rays itself) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
 // ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
@@ -430,6 +431,137 @@ int ptrt_query_direct(ptrt_ctx *c, const float *d_positions, const float *d_norm
         return launch_persistent(c, pt::direct_query_kernel<G, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels, d_samples2,
                                  n_shadow, d_phases, offset, light_first, (int)S.terms, o);
     });
+}
+
+} // extern "C"
+
+namespace {
+
+// What ptrt_bounce_terms and ptrt_query_bounce refuse alike, and the counts they share: n_texels * n_dirs gather rays, Q terms
+// per ray, rays * Q rows.  `offset`: the query's; NULL for the call without one.
+struct BounceShape {
+    size_t texels = 0, dirs = 0, terms = 0, rays = 0, rows = 0;
+};
+int check_bounce(ptrt_ctx *c, const char *fn, int n_texels, int n_dirs, const float *d_shadow2, int n_shadow, const float *offset,
+                 int light_first, int light_count, BounceShape &S) {
+    if (n_texels < 0 || n_dirs < 1 || n_shadow < 1 || !d_shadow2)
+        return fail(c, PTRT_E_INVALID, "%s: bad argument (n_texels %d, n_dirs %d, n_shadow %d, shadow2 %p)", fn, n_texels, n_dirs, n_shadow,
+                    (const void *)d_shadow2);
+    if (light_first < 0 || light_count < 0 || (long long)light_first + light_count > (long long)c->n_lights)
+        return fail(c, PTRT_E_INVALID, "%s: lights %d .. %d + %d of %d uploaded", fn, light_first, light_first, light_count, c->n_lights);
+    if (offset && !std::isfinite(*offset))
+        return fail(c, PTRT_E_INVALID, "%s: offset=%g (finite)", fn, (double)*offset);
+    // counts in size_t: Q and n_dirs * Q are below 2^62 and have to fit an int; the rows, times 12 bytes, have to fit size_t
+    S.texels = (size_t)n_texels;
+    S.dirs = (size_t)n_dirs;
+    S.terms = (size_t)light_count * (size_t)n_shadow;
+    if (S.terms > (size_t)INT_MAX || S.dirs * S.terms > (size_t)INT_MAX)
+        return fail(c, PTRT_E_INVALID, "%s: %d directions x %d lights x %d shadow samples: more than %d terms per texel", fn, n_dirs,
+                    light_count, n_shadow, INT_MAX);
+    S.rays = S.texels * S.dirs; // (below 2^62)
+    if (S.rays > SIZE_MAX / 64 || (S.terms && S.rays > SIZE_MAX / 12 / S.terms))
+        return fail(c, PTRT_E_INVALID, "%s: %d texels x %d directions x %zu terms: a byte count overflows", fn, n_texels, n_dirs, S.terms);
+    S.rows = S.rays * S.terms;
+    return PTRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ptrt_bounce_terms(ptrt_ctx *c, const ptrt_hit *d_hits, const float *d_directions, int n_texels, int n_dirs, const float *d_shadow2,
+                      int n_shadow, const float *d_phases, int light_first, int light_count, float *d_origins, float *d_L, float *d_tmax,
+                      float *d_values) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_bounce_terms: bad context");
+    if (!d_hits || !d_directions || !d_origins || !d_L || !d_tmax || !d_values)
+        return fail(c, PTRT_E_INVALID, "ptrt_bounce_terms: bad argument (hits %p, directions %p, origins %p, L %p, tmax %p, values %p)",
+                    (const void *)d_hits, (const void *)d_directions, (const void *)d_origins, (const void *)d_L, (const void *)d_tmax,
+                    (const void *)d_values);
+    BounceShape S;
+    if (int rc = check_bounce(c, "ptrt_bounce_terms", n_texels, n_dirs, d_shadow2, n_shadow, nullptr, light_first, light_count, S))
+        return rc;
+    // one thread per term in blocks of 256: the grid's x extent is an int
+    constexpr size_t MAX_ROWS = (size_t)INT_MAX * 256;
+    if (S.rows > MAX_ROWS)
+        return fail(c, PTRT_E_INVALID, "ptrt_bounce_terms: %zu rays x %zu terms: more than %zu rows in one call", S.rays, S.terms, MAX_ROWS);
+    if (!c->have_materials)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_bounce_terms: materials not uploaded");
+    if (S.rows == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const Span sh{"hits", d_hits, S.rays * sizeof(ptrt_hit)}, sd{"directions", d_directions, S.rays * 12},
+        ss{"shadow2", d_shadow2, (size_t)n_shadow * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
+        so{"origins", d_origins, S.rows * 12}, sl{"L", d_L, S.rows * 12}, st{"tmax", d_tmax, S.rows * sizeof(float)},
+        sv{"values", d_values, S.rows * 12};
+    if (int rc = d_phases ? check_spans(c, "ptrt_bounce_terms", {sh, sd, ss, sph, so, sl, st, sv})
+                          : check_spans(c, "ptrt_bounce_terms", {sh, sd, ss, so, sl, st, sv}))
+        return rc;
+    c->touched = true;
+    // bounce_terms_kernel (pt_bounce.hip.h): one thread per term, the material model a frame would use
+    const pt::HitOut *h = reinterpret_cast<const pt::HitOut *>(d_hits);
+    const dim3 grid((unsigned)((S.rows + 255) / 256));
+    if (c->mats_full || c->force_full)
+        hipLaunchKernelGGL(pt::bounce_terms_kernel<true>, grid, dim3(256), 0, c->stream, c->d_lights, c->d_materials, c->n_materials, h,
+                           d_directions, S.rows, n_dirs, d_shadow2, n_shadow, d_phases, light_first, (int)S.terms, d_origins, d_L, d_tmax,
+                           d_values);
+    else
+        hipLaunchKernelGGL(pt::bounce_terms_kernel<false>, grid, dim3(256), 0, c->stream, c->d_lights, c->d_materials, c->n_materials, h,
+                           d_directions, S.rows, n_dirs, d_shadow2, n_shadow, d_phases, light_first, (int)S.terms, d_origins, d_L, d_tmax,
+                           d_values);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_query_bounce(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
+                      const float *d_phases, float offset, const float *d_shadow2, int n_shadow, int light_first, int light_count,
+                      ptrt_bounce *d_out) {
+    static_assert(sizeof(pt::BounceOut) == sizeof(ptrt_bounce) && sizeof(ptrt_bounce) == 32, "BounceOut must mirror ptrt_bounce");
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_bounce: bad context");
+    if (!d_positions || !d_normals || !d_samples2 || !d_out)
+        return fail(c, PTRT_E_INVALID, "ptrt_query_bounce: bad argument (positions %p, normals %p, samples2 %p, out %p)",
+                    (const void *)d_positions, (const void *)d_normals, (const void *)d_samples2, (const void *)d_out);
+    BounceShape S;
+    if (int rc = check_bounce(c, "ptrt_query_bounce", n_texels, n_dirs, d_shadow2, n_shadow, &offset, light_first, light_count, S))
+        return rc;
+    if (!c->have_geometry || !c->have_materials)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_bounce: %s not uploaded", c->have_geometry ? "materials" : "geometry");
+    if (c->n_materials < c->n_meshes)
+        return fail(c, PTRT_E_NOT_READY, "ptrt_query_bounce: %d materials for %d meshes", c->n_materials, c->n_meshes);
+    if (n_texels == 0)
+        return PTRT_OK;
+    if (int rc = set_device(c))
+        return rc;
+    const Span sp{"positions", d_positions, S.texels * 12}, sn{"normals", d_normals, S.texels * 12},
+        ss{"samples2", d_samples2, S.dirs * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
+        ssh{"shadow2", d_shadow2, (size_t)n_shadow * 8}, sout{"out", d_out, S.texels * sizeof(ptrt_bounce)};
+    if (int rc = d_phases ? check_spans(c, "ptrt_query_bounce", {sp, sn, ss, sph, ssh, sout})
+                          : check_spans(c, "ptrt_query_bounce", {sp, sn, ss, ssh, sout}))
+        return rc;
+    if (S.terms == 0) { // no lights asked for: rows of zero bytes, in stream order
+        c->touched = true;
+        HIP_TRY(c, hipMemsetAsync(d_out, 0, S.texels * sizeof(ptrt_bounce), c->stream));
+        return PTRT_OK;
+    }
+    QueryPlan P;
+    if (int rc = plan_query(c, false, 0, 0, P))
+        return rc;
+    // bounce_query_kernel (pt_bounce.hip.h): irradiance_query_kernel's grid -- groups of 64 / w texels, w the smallest power of
+    // two >= n_dirs; beyond 64 directions over texels, one wave per texel
+    size_t w = 1;
+    while (w < 64 && w < S.dirs)
+        w *= 2;
+    const size_t per_group = 64 / w, groups = (S.texels + per_group - 1) / per_group;
+    pt::BounceOut *o = reinterpret_cast<pt::BounceOut *>(d_out);
+    auto launch = [&](auto FULL) {
+        return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+            return launch_persistent(c, pt::bounce_query_kernel<G, FULL, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels,
+                                     d_samples2, n_dirs, d_phases, offset, d_shadow2, n_shadow, light_first, (int)S.terms, o);
+        });
+    };
+    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
 } // extern "C"

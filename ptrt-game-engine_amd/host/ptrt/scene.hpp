@@ -998,6 +998,32 @@ class Scene {
                                light_count < 0 ? (int)lights.size() - light_first : light_count, d_origins, d_dirs, d_tmax, d_weights),
               "Direct rays failed");
     }
+    // The analytic lights' one-bounce term at lightmap texels (ptrt_query_bounce): the gather rays of queryIrradiance, and at
+    // each ray's closest hit n_shadow light samples (the points of d_shadow2, rotated by d_phases[t] if given) of each of the
+    // lights light_first .. light_first + light_count - 1 (light_count < 0: all from light_first on), valued by the hit's BSDF
+    // as a path vertex values them and walked as shadow rays; d_out gets one 32-byte ptrt_bounce per texel -- mean radiance (pi
+    // times it: the irradiance), the fractions of terms lit and shadowed, the hit fraction.  Commits what queryRadiance commits.
+    void queryBounce(const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
+                     const float *d_phases, float offset, const float *d_shadow2, int n_shadow, int light_first, int light_count,
+                     ptrt_bounce *d_out) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_query_bounce(ctx, d_positions, d_normals, n_texels, d_samples2, n_dirs, d_phases, offset, d_shadow2, n_shadow,
+                                light_first, light_count < 0 ? (int)lights.size() - light_first : light_count, d_out),
+              "Bounce query failed");
+    }
+    // The terms queryBounce sums (ptrt_bounce_terms) at hits the caller traced -- d_hits and d_dirs: the n_texels * n_dirs records
+    // and directions of irradianceRays + a closest-hit query --: per row (t * n_dirs + k) * Q + q, Q = light_count * n_shadow, the
+    // shadow ray's origin and direction (3 floats each), its length and the term's value (3 floats), walked or not.
+    void bounceTerms(const ptrt_hit *d_hits, const float *d_dirs, int n_texels, int n_dirs, const float *d_shadow2, int n_shadow,
+                     const float *d_phases, int light_first, int light_count, float *d_origins, float *d_L, float *d_tmax,
+                     float *d_values) {
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_bounce_terms(ctx, d_hits, d_dirs, n_texels, n_dirs, d_shadow2, n_shadow, d_phases, light_first,
+                                light_count < 0 ? (int)lights.size() - light_first : light_count, d_origins, d_L, d_tmax, d_values),
+              "Bounce terms failed");
+    }
     // A mesh's UV charts rasterised to lightmap texels (ptrt_atlas_texels): d_uv holds the (x, y) of the three corners of every
     // face of mesh `mesh` in texel units (faces * 6 floats), d_texels gets atlas_w * atlas_h 32-byte ptrt_atlas_texel -- world
     // position, geometric normal, owning face, mesh -- for the texel centres some face covers, the lowest face winning;

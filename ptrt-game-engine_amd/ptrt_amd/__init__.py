@@ -135,6 +135,12 @@ class Direct(C.Structure):
                 ("reserved", C.c_float * 3)]
 
 
+class Bounce(C.Structure):
+    """`ptrt_bounce`: one lightmap texel's answer from ptrt_query_bounce."""
+    _fields_ = [("radiance", C.c_float * 3), ("lit_fraction", C.c_float), ("shadowed_fraction", C.c_float),
+                ("hit_fraction", C.c_float), ("reserved", C.c_float * 2)]
+
+
 class AtlasTexel(C.Structure):
     """`ptrt_atlas_texel`: one texel of a lightmap atlas from ptrt_atlas_texels."""
     _fields_ = [("position", C.c_float * 3), ("face", C.c_int32), ("normal", C.c_float * 3), ("mesh", C.c_int32)]
@@ -178,6 +184,9 @@ IRRADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("mean_distance", "<f4"), (
 assert IRRADIANCE_DTYPE.itemsize == C.sizeof(Irradiance) == 32
 DIRECT_DTYPE = np.dtype([("irradiance", "<f4", 3), ("lit_fraction", "<f4"), ("shadowed_fraction", "<f4"), ("reserved", "<f4", 3)])
 assert DIRECT_DTYPE.itemsize == C.sizeof(Direct) == 32
+BOUNCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("lit_fraction", "<f4"), ("shadowed_fraction", "<f4"), ("hit_fraction", "<f4"),
+                         ("reserved", "<f4", 2)])
+assert BOUNCE_DTYPE.itemsize == C.sizeof(Bounce) == 32
 ATLAS_TEXEL_DTYPE = np.dtype([("position", "<f4", 3), ("face", "<i4"), ("normal", "<f4", 3), ("mesh", "<i4")])
 assert ATLAS_TEXEL_DTYPE.itemsize == C.sizeof(AtlasTexel) == 32
 LIGHTMAP_SAMPLE_DTYPE = np.dtype([("rgb", "<f4", 3), ("weight", "<f4"), ("x", "<f4"), ("y", "<f4"), ("face", "<i4"), ("mesh", "<i4")])
@@ -229,6 +238,8 @@ _sig("ptrt_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp,
 _sig("ptrt_query_irradiance", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_float, _vp)
 _sig("ptrt_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
 _sig("ptrt_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp)
+_sig("ptrt_bounce_terms", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
+_sig("ptrt_query_bounce", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("ptrt_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("ptrt_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("ptrt_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
@@ -366,6 +377,8 @@ _sig("hs_irradiance_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C
 _sig("hs_light_count", C.c_int, _vp)
 _sig("hs_query_direct", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp)
 _sig("hs_direct_rays", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
+_sig("hs_query_bounce", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("hs_bounce_terms", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp)
 _sig("hs_atlas_texels", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("hs_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("hs_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
@@ -500,6 +513,19 @@ def direct_fields(records):
     """Named views of query_direct's (n, 8) float32 rows (a tensor or an array): irradiance as (n, 3), scalars as (n,)."""
     out = {}
     for name, (a, b) in DIRECT_COLUMNS.items():
+        col = records[:, a:b]
+        out[name] = col[:, 0] if b - a == 1 else col
+    return out
+
+
+# columns of the (n, 8) float32 rows of Scene.query_bounce: the fields of ptrt_bounce / BOUNCE_DTYPE
+BOUNCE_COLUMNS = dict(radiance=(0, 3), lit_fraction=(3, 4), shadowed_fraction=(4, 5), hit_fraction=(5, 6), reserved=(6, 8))
+
+
+def bounce_fields(records):
+    """Named views of query_bounce's (n, 8) float32 rows (a tensor or an array): radiance as (n, 3), scalars as (n,)."""
+    out = {}
+    for name, (a, b) in BOUNCE_COLUMNS.items():
         col = records[:, a:b]
         out[name] = col[:, 0] if b - a == 1 else col
     return out
@@ -1253,6 +1279,97 @@ class Scene:
             None if phases is None else _vp(phases.data_ptr()), float(offset), first, count, _vp(o.data_ptr()), _vp(d.data_ptr()),
             _vp(t.data_ptr()), _vp(w.data_ptr()))))
         return o, d, t, w
+
+    def _light_range(self, what, lights):
+        """`lights` of query_bounce / bounce_terms, checked; returns (first light, light count)"""
+        have = self.lightCount()
+        try:
+            first, count = (0, have) if lights is None else (int(lights[0]), int(lights[1]))
+        except (TypeError, IndexError):
+            raise ValueError(f"{what}: lights={lights!r}, expected None or (first, count)") from None
+        if first < 0 or count < 0 or first + count > have:
+            raise ValueError(f"{what}: lights ({first}, {count}) of the scene's {have}")
+        return first, count
+
+    def _shadow_samples(self, what, device, shadow2, count, k):
+        """the light samples of query_bounce / bounce_terms, checked; returns (shadow2, shadow samples)"""
+        if shadow2 is None:
+            import torch
+            shadow2 = torch.from_numpy(lightmap.hammersley2(1)).to(device)
+        self._device_tensor(f"{what}: shadow2", shadow2, 2, "torch.float32")
+        m = shadow2.shape[0]
+        if m < 1:
+            raise ValueError(f"{what}: no shadow samples")
+        if k * count * m >= 2 ** 31:
+            raise ValueError(f"{what}: {k} directions x {count} lights x {m} shadow samples (at most 2^31 - 1 terms per texel)")
+        return shadow2, m
+
+    def query_bounce(self, positions, normals, samples2, shadow2=None, phases=None, offset=1e-4, lights=None, out=None):
+        """The analytic lights' one-bounce term at lightmap texels -- light that reaches the texel after exactly one reflection
+        off the surface a gather ray hits first, which neither query_irradiance (its rays take no light sample at their first
+        hit) nor query_direct (the lights at the texel itself) sees.  Texel t sends the gather rays of query_irradiance (one
+        per point of `samples2`, rotated by `phases`, from positions[t] + offset * normals[t]); at each ray's closest hit it
+        takes one light sample per point of `shadow2` (m points in [0,1)^2, rotated by `phases` too; None: the one point of
+        `lightmap.hammersley2(1)`) of each light of `lights` ((first, count); None: all), values it by the hit's BSDF as a path
+        vertex does (soft clamp kept, no MIS weight) and walks its shadow ray.  torch tensors on this scene's device,
+        contiguous, read in place.  Returns an (n, 8) float32 tensor, one 32-byte `ptrt_bounce` per row (`bounce_fields` names
+        the columns): the mean radiance (0:3; pi times it is the irradiance, `lightmap.bounce_irradiance`), the fractions of
+        the k * Q terms lit (3) and blocked (4), the fraction of gather rays that hit (5); `out` takes such a tensor to write
+        into.  `lightmap.full_irradiance` adds it to the direct and gathered terms.  No synchronisation."""
+        first, count = self._light_range("query_bounce", lights)
+        n, k = self._texel_inputs("query_bounce", positions, normals, samples2, phases)
+        shadow2, m = self._shadow_samples("query_bounce", positions.device, shadow2, count, k)
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=positions.device)
+        else:
+            self._device_tensor("query_bounce: out", out, 8, "torch.float32")
+            if out.shape[0] != n:
+                raise ValueError(f"query_bounce: out has {out.shape[0]} rows for {n} texels")
+        if n == 0:
+            return out
+        self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_bounce(
+            self._h, _vp(positions.data_ptr()), _vp(normals.data_ptr()), n, _vp(samples2.data_ptr()), k,
+            None if phases is None else _vp(phases.data_ptr()), float(offset), _vp(shadow2.data_ptr()), m, first, count,
+            _vp(out.data_ptr()))))
+        return out
+
+    def bounce_terms(self, hits, directions, n_dirs, shadow2=None, phases=None, lights=None):
+        """(origins, L, tmax, values): (r * Q, 3), (r * Q, 3), (r * Q,) and (r * Q, 3) float32 tensors holding the terms
+        query_bounce sums, for hits the caller traced: `hits` (r, 16) int32 and `directions` (r, 3) float32 are what
+        `query_closest(*irradiance_rays(..))` and `irradiance_rays` return for r = n * n_dirs gather rays, ray (t, k) in row
+        t * n_dirs + k; `phases`: (n,) float32 or None.  Term q = light * m + sample of ray i is row i * Q + q, Q = light count
+        * m: the path's shadow origin, the direction to the light, the ray's length and the term's value (ptrt_bounce_terms)
+        -- for terms query_bounce does not walk too; a miss gives a row of zeros.  No synchronisation."""
+        first, count = self._light_range("bounce_terms", lights)
+        self._device_tensor("bounce_terms: hits", hits, 16, "torch.int32")
+        self._device_tensor("bounce_terms: directions", directions, 3, "torch.float32")
+        r, k = hits.shape[0], int(n_dirs)
+        if directions.shape[0] != r:
+            raise ValueError(f"bounce_terms: {r} hits, {directions.shape[0]} directions")
+        if k < 1 or r % k:
+            raise ValueError(f"bounce_terms: {r} hits are not a multiple of n_dirs = {k}")
+        n = r // k
+        if phases is not None:
+            if not _is_tensor(phases) or phases.dim() != 1:
+                raise ValueError("bounce_terms: phases: needs a torch tensor of shape (n,) on the scene's device")
+            self._device_tensor("bounce_terms: phases", phases.unsqueeze(1), 1, "torch.float32")
+            if phases.shape[0] != n:
+                raise ValueError(f"bounce_terms: {n} texels, {phases.shape[0]} phases")
+        shadow2, m = self._shadow_samples("bounce_terms", hits.device, shadow2, count, k)
+        import torch
+        rows = r * count * m
+        o = torch.empty((rows, 3), dtype=torch.float32, device=hits.device)
+        d = torch.empty((rows, 3), dtype=torch.float32, device=hits.device)
+        t = torch.empty((rows,), dtype=torch.float32, device=hits.device)
+        v = torch.empty((rows, 3), dtype=torch.float32, device=hits.device)
+        if rows == 0:
+            return o, d, t, v
+        self._enqueue_between_streams(hits.device, lambda: self._chk(lib.hs_bounce_terms(
+            self._h, _vp(hits.data_ptr()), _vp(directions.data_ptr()), n, k, _vp(shadow2.data_ptr()), m,
+            None if phases is None else _vp(phases.data_ptr()), first, count, _vp(o.data_ptr()), _vp(d.data_ptr()),
+            _vp(t.data_ptr()), _vp(v.data_ptr()))))
+        return o, d, t, v
 
     def atlas_texels(self, mesh, uv, width, height, out=None, clear=True):
         """The UV charts of mesh `mesh` (the id addCube and its kin return) rasterised into a `width` x `height` lightmap atlas

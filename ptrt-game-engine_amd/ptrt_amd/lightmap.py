@@ -6,7 +6,8 @@ A texel's rays are cosine-distributed about its normal, so the mean of their rad
 rays mostly end close by -- inside a wall, under a carpet -- is one a baker fills from its neighbours (`invalid_texels`).
 
 Scene.query_direct adds what the gather cannot see, the analytic lights at the texel itself: `direct_irradiance`,
-`penumbra_texels` and `total_irradiance` read its rows.
+`penumbra_texels` and `total_irradiance` read its rows.  Scene.query_bounce adds the term both leave out, the lights' one bounce
+off the surface a gather ray hits first: `bounce_irradiance` reads its rows and `full_irradiance` sums all three.
 
 Scene.atlas_texels makes the texels of an uploaded mesh from its UV charts and Scene.atlas_dilate finishes a baked atlas:
 `triangle_charts` (charts for a mesh that never had UVs), `uv_to_texels`, `covered`, `atlas_inputs` and `scatter` stand between
@@ -116,7 +117,7 @@ def total_irradiance(direct_rows, gather_rows):
     What this sum still LACKS: a gather ray takes no light sample at its first hit (the quirk of a caller's ray, include/ptrt.h),
     so the analytic lights' one-bounce term -- light that reaches the texel after exactly one diffuse reflection off the surface
     a gather ray hits first -- is absent; emissive meshes, the sky and every later bounce are in the gather.  A lit first vertex
-    for the gather is not built.
+    for the gather is not built.  `full_irradiance` adds that term from Scene.query_bounce's rows.
 
     The order of a bake from here: `scatter` these values into the atlas, Scene.atlas_filter (the gather's Monte-Carlo noise,
     edge-aware, covered texels only), then Scene.atlas_dilate (the texels no chart covers)."""
@@ -124,6 +125,24 @@ def total_irradiance(direct_rows, gather_rows):
     if d.shape != g.shape:
         raise ValueError(f"total_irradiance: {d.shape[0]} direct rows, {g.shape[0]} gather rows")
     return d + g
+
+
+def bounce_irradiance(rows):
+    """(n, 3) float32: pi times the mean radiance of query_bounce's (n, 8) rows (one float32 product per value) -- the gather
+    rays are cosine-distributed, as for `irradiance`"""
+    return np.float32(math.pi) * _rows(rows)[:, 0:3].astype(np.float32)
+
+
+def full_irradiance(direct_rows, gather_rows, bounce_rows):
+    """(n, 3) float32: (direct_irradiance(direct_rows) + irradiance(gather_rows)) + bounce_irradiance(bounce_rows) -- what
+    `total_irradiance` gives plus the analytic lights' one-bounce term from Scene.query_bounce, the term that sum lacks.  The
+    three terms do not overlap: the lights at the texel; the lights after exactly one reflection; everything a path collects
+    from its second vertex on, and emission, sky and environment at every vertex.  The order of a bake from here is
+    `total_irradiance`'s."""
+    t, b = total_irradiance(direct_rows, gather_rows), bounce_irradiance(bounce_rows)
+    if t.shape != b.shape:
+        raise ValueError(f"full_irradiance: {t.shape[0]} direct and gather rows, {b.shape[0]} bounce rows")
+    return t + b
 
 
 def triangle_charts(face_count, cell, gutter=1):
