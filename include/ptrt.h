@@ -214,6 +214,23 @@ typedef struct ptrt_lightmap_sample {
     int32_t mesh;   /* ptrt_hit.mesh_index, -1 on a miss                                                                            */
 } ptrt_lightmap_sample;
 
+/* A regular grid of light probes for ptrt_probe_sample / ptrt_query_probe_light.  HOST memory, passed by pointer and copied
+ * into the launch. */
+typedef struct ptrt_probe_volume {
+    float origin[3];    /* position of probe (0, 0, 0)                                                                             */
+    float spacing[3];   /* > 0, finite, per axis                                                                                   */
+    int32_t counts[3];  /* nx, ny, nz >= 1; probe (i, j, k) is row i + nx*(j + ny*k) of d_probes: ptrt_amd.probes.probe_grid's order */
+} ptrt_probe_volume;
+
+/* One surface point's answer from ptrt_probe_sample / ptrt_query_probe_light: the probe volume's irradiance there, 32 bytes. */
+typedef struct ptrt_probe_light {
+    float irradiance[3]; /* sum of w * E over the corners used, divided by `weight`; 0 without a corner      */
+    float weight;        /* sum of the weights of the corners used                                           */
+    int32_t cell;        /* row of the footprint's corner 0, -1: no cell                                     */
+    int32_t used;        /* bit c set: corner c contributed                                                  */
+    int32_t face, mesh;  /* the hit's, -1 on a miss; -1, -1 from ptrt_probe_sample                           */
+} ptrt_probe_light;
+
 /* Per-frame counters of the trace stage (Mrays/s numerator). */
 typedef struct ptrt_stats {
     uint64_t extension_rays; /* traceRay calls   (intersection.cuh:526) */
@@ -945,6 +962,57 @@ int ptrt_atlas_sample(ptrt_ctx *ctx, const ptrt_hit *d_hits, int n, const float 
 int ptrt_query_lightmap(ptrt_ctx *ctx, const float *d_origins, const float *d_directions, int n, const float *d_charts,
                         int n_chart_faces, const int32_t *d_chart_first, const float *d_image, int atlas_w, int atlas_h,
                         int mode, ptrt_lightmap_sample *d_out);
+
+/* The consumer of a probe bake: a regular grid of ptrt_probe records -- what ptrt_query_probes leaves for positions laid out as
+ * `volume` says -- read at surface points.  d_probes (nx*ny*nz records) and the arrays are DEVICE memory; `volume` is host memory.
+ * ptrt_probe_sample answers for n points P = d_positions[i] with normals N = d_normals[i] (n*3 floats each); ptrt_query_probe_light
+ * traces n rays itself, as ptrt_query_rays(PTRT_QUERY_CLOSEST) would, and answers for the `point` and `normal` (the face-forwarded
+ * one) that query would have written -- formed by the same device function -- with the hit's face f and mesh m filled in: the bytes
+ * of ptrt_probe_sample over those two columns, in one launch and without the 64-byte records.  One ptrt_probe_light per point.
+ * The record is ONE definition in fp32, every operation rounded on its own (no contraction), `/` and sqrt the IEEE ones, sums in
+ * the written order:
+ *   1. A miss (ptrt_query_probe_light only):  {0, 0, 0,  0,  -1, 0,  -1, -1}.
+ *   2. P has a non-finite component: no cell,  {0, 0, 0,  0,  -1, 0,  f, m}.  Memory safety depends on P alone; N is used as given,
+ *      NOT normalised, and a non-finite N may give non-finite colours but never a read outside d_probes.
+ *   3. The cell.  Per axis a:  g = (P[a] - origin[a]) / spacing[a];  g = min(max(g, 0), (float)(counts[a] - 1));  i0 = (int)floor(g);
+ *      i1 = min(i0 + 1, counts[a] - 1);  f = g - (float)i0.  Points outside the volume are clamped to its faces.  `cell` is the
+ *      row of (i0x, i0y, i0z).
+ *   4. The basis at N, once per point:  B_i = K_i * Y_i(N) with Y_i exactly as ptrt_query_probes has it above (the same six-digit
+ *      constants, the same operation order) and K_0 = 39.478418f (4 pi * pi), K_1..3 = 26.318945f (4 pi * 2 pi / 3),
+ *      K_4..8 = 9.869604f (4 pi * pi / 4): the factor that turns ptrt_query_probes' means into projection integrals, times the
+ *      cosine lobe's per band.
+ *   5. The corners c = 0..7 in that order; bit 0 of c selects i1 on x, bit 1 on y, bit 2 on z.  wt = (wx*wy)*wz, each factor f or
+ *      1 - f of its axis.  A corner with wt <= 0 is skipped BY SELECTION, never by a product with zero -- whatever its record holds
+ *      reaches nothing (ptrt_atlas_filter's rule) and it is not loaded.  On an axis with one probe both corners name the same row
+ *      and the second has weight 0.
+ *        TRILINEAR   w = wt.
+ *        VISIBILITY  Q = origin + (float)idx * spacing (the product rounded, then the sum);  Pb = P + normal_bias * N;  V = Q - Pb;
+ *                    r2 = (Vx*Vx + Vy*Vy) + Vz*Vz;  r = sqrt(r2);  D = r > 0 ? V / r : 0.
+ *                    Facing:      c = (dot(D, N) + 1) * 0.5f, the dot summed as r2 is;  wf = c*c + 0.2f.
+ *                    Visibility:  mean = rec.mean_distance;  var = fabs(rec.mean_distance_sq - mean*mean);  wv = 1 when r <= mean;
+ *                                 otherwise d = r - mean, ch = var / (var + d*d), wv = (ch*ch)*ch  (Chebyshev's bound, cubed).
+ *                    w = wf * wv;  if w < 0.2f then w = w * ((w*w) / 0.04f);  then w = w * wt.
+ *      A corner whose w is not > 0 is skipped by selection (a NaN too).  A used corner: per channel E_c = acc after acc = +0.0f,
+ *      acc = acc + B_i * sh[i][c] for i = 0..8;  num_c += w * E_c;  den += w;  bit c of `used` is set.
+ *   6. den > 0: irradiance_c = num_c / den, replaced by +0.0f where it is < 0 (SH ringing), weight = den; otherwise both are 0.
+ *      The record is {irradiance, weight, cell, used, f, m}.
+ * tests/probe_sample_restatement.py states all of it in numpy.  ptrt_amd.probes.ProbeVolume.positions() forms Q, so probes baked
+ * there sit exactly where the sampler assumes.  Not built: a per-probe validity or back-face state, probe relocation, RT-context
+ * and tile-farm variants.
+ * Ordering and side effects are ptrt_query_rays': enqueued on the context's stream; no allocation, copy or synchronisation;
+ * generator states, frame buffers, counters and both timing histories are left alone; ptrt_query_probe_light walks the traversal a
+ * frame would (ptrt_get_option "query_pmode" says which).  PTRT_E_INVALID (nothing enqueued, d_out untouched) for n < 0, a NULL
+ * pointer, a count < 1 or a product of the counts above 2^24 (formed in 64 bits; (float)idx stays exact), a spacing that is not
+ * positive and finite, a non-finite origin, a normal_bias that is negative or not finite, a mode other than the two, d_probes or
+ * d_out not 16-byte aligned, a float array not 4-byte aligned, memory that is not the context's device memory or too small (byte
+ * counts in size_t), d_out overlapping an input.  PTRT_E_NOT_READY before geometry is uploaded (ptrt_query_probe_light only);
+ * n == 0 is PTRT_OK with no launch.  (ABI 6, additions only.) */
+#define PTRT_PROBES_TRILINEAR 0
+#define PTRT_PROBES_VISIBILITY 1
+int ptrt_probe_sample(ptrt_ctx *ctx, const float *d_positions, const float *d_normals, int n, const ptrt_probe_volume *volume,
+                      const ptrt_probe *d_probes, int mode, float normal_bias, ptrt_probe_light *d_out);
+int ptrt_query_probe_light(ptrt_ctx *ctx, const float *d_origins, const float *d_directions, int n, const ptrt_probe_volume *volume,
+                           const ptrt_probe *d_probes, int mode, float normal_bias, ptrt_probe_light *d_out);
 
 /* The primary rays ptrt_render(frame_index, ..) gives sample `sample` of every pixel of the context's rows -- TAA and
  * blue-noise jitter of frame_index + sample, the context's camera, the render size if one is set -- written by one small

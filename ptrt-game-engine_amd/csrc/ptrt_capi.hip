@@ -26,6 +26,7 @@
 #include "pt_atlas.hip.h"
 #include "pt_atlas_filter.hip.h"
 #include "pt_lightmap.hip.h"
+#include "pt_probe_sample.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>

@@ -498,6 +498,28 @@ int hs_query_lightmap(void *s, const void *d_origins, const void *d_dirs, int n,
                                                   atlas_h, mode, static_cast<ptrt_lightmap_sample *>(d_out)));
     return 0;
 }
+int hs_probe_sample(void *s, const void *d_positions, const void *d_normals, int n, const void *volume, const void *d_probes, int mode,
+                    float normal_bias, void *d_out) {
+    if (!volume) {
+        g_err = "probe_sample: no volume";
+        return -1;
+    }
+    HS_TRY(static_cast<Scene *>(s)->probeSample(static_cast<const float *>(d_positions), static_cast<const float *>(d_normals), n,
+                                                *static_cast<const ptrt_probe_volume *>(volume), static_cast<const ptrt_probe *>(d_probes),
+                                                mode, normal_bias, static_cast<ptrt_probe_light *>(d_out)));
+    return 0;
+}
+int hs_query_probe_light(void *s, const void *d_origins, const void *d_dirs, int n, const void *volume, const void *d_probes, int mode,
+                         float normal_bias, void *d_out) {
+    if (!volume) {
+        g_err = "query_probe_light: no volume";
+        return -1;
+    }
+    HS_TRY(static_cast<Scene *>(s)->queryProbeLight(static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n,
+                                                    *static_cast<const ptrt_probe_volume *>(volume), static_cast<const ptrt_probe *>(d_probes),
+                                                    mode, normal_bias, static_cast<ptrt_probe_light *>(d_out)));
+    return 0;
+}
 int hs_camera_rays(void *s, int frame, int sample, void *d_origins, void *d_dirs) {
     HS_TRY(static_cast<Scene *>(s)->cameraRays(frame, sample, static_cast<float *>(d_origins), static_cast<float *>(d_dirs)));
     return 0;

@@ -3,7 +3,8 @@
 // ptrt_irradiance_rays for the rays alone; ptrt_query_direct, with ptrt_direct_rays, for the analytic lights; ptrt_query_bounce, with
 // ptrt_bounce_terms, for their one-bounce term), the lightmap
 // atlas around them (ptrt_atlas_texels, ptrt_atlas_filter, ptrt_atlas_dilate: no traversal), the baked atlas read back at ray hits
-// (ptrt_atlas_sample; ptrt_query_lightmap, which traces the rays itself) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
+// (ptrt_atlas_sample; ptrt_query_lightmap, which traces the rays itself), a probe volume read at surface points (ptrt_probe_sample;
+// ptrt_query_probe_light, which traces the rays itself) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
 // ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
 // (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
 // check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
@@ -851,6 +852,124 @@ int ptrt_query_lightmap(ptrt_ctx *c, const float *d_origins, const float *d_dire
     float4 *o = reinterpret_cast<float4 *>(d_out);
     return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
         return launch_persistent(c, pt::lightmap_query_kernel<G, PM>, P.lds, (rays + 63) / 64, false, P.K, d_origins, d_directions, rays, L, o);
+    });
+}
+
+} // extern "C"
+
+namespace {
+
+// What ptrt_probe_sample and ptrt_query_probe_light refuse alike, up to the device: the volume, the probes, the mode, the bias,
+// the output, and the caller's own float arrays `ins` (points and normals; the rays), which d_out must not overlap either.
+// `need_geometry`: the fused entry traces.  `done`: n == 0, nothing to do.
+int check_probe_volume(ptrt_ctx *c, const char *fn, int n, const ptrt_probe_volume *volume, const ptrt_probe *d_probes, int mode,
+                       float normal_bias, ptrt_probe_light *d_out, std::initializer_list<Span> ins, bool need_geometry,
+                       pt::ProbeVolumeParams &V, bool &done) {
+    static_assert(sizeof(pt::ProbeLight) == sizeof(ptrt_probe_light) && sizeof(ptrt_probe_light) == 32,
+                  "ProbeLight must mirror ptrt_probe_light");
+    static_assert(sizeof(ptrt_probe) == 128 && offsetof(ptrt_probe, mean_distance) == 27 * 4 && offsetof(ptrt_probe, mean_distance_sq) == 28 * 4,
+                  "probe_light reads a probe row by word");
+    static_assert(pt::PROBES_TRILINEAR == PTRT_PROBES_TRILINEAR && pt::PROBES_VISIBILITY == PTRT_PROBES_VISIBILITY, "the modes");
+    done = false;
+    if (n < 0 || !volume || !d_probes || !d_out || (mode != PTRT_PROBES_TRILINEAR && mode != PTRT_PROBES_VISIBILITY) ||
+        !(normal_bias >= 0.0f) || !std::isfinite(normal_bias))
+        return fail(c, PTRT_E_INVALID, "%s: bad argument (n %d, volume %p, probes %p, mode %d: 0 or 1, normal_bias %g: >= 0 and finite, out %p)",
+                    fn, n, (const void *)volume, (const void *)d_probes, mode, (double)normal_bias, (const void *)d_out);
+    long long rows = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (volume->counts[a] < 1 || !(volume->spacing[a] > 0.0f) || !std::isfinite(volume->spacing[a]) || !std::isfinite(volume->origin[a]))
+            return fail(c, PTRT_E_INVALID, "%s: volume axis %d: count %d (>= 1), spacing %g (positive and finite), origin %g (finite)", fn, a,
+                        volume->counts[a], (double)volume->spacing[a], (double)volume->origin[a]);
+        rows *= volume->counts[a]; // each factor < 2^31 and the product so far <= 2^24: no overflow
+        if (rows > (1ll << 24))
+            return fail(c, PTRT_E_INVALID, "%s: a volume of %d x %d x %d probes (at most 2^24)", fn, volume->counts[0], volume->counts[1],
+                        volume->counts[2]);
+    }
+    for (const Span &s : ins)
+        if (!s.p || ((uintptr_t)s.p & 3u))
+            return fail(c, PTRT_E_INVALID, "%s: %s %p must not be NULL and must be 4-byte aligned", fn, s.name, s.p);
+    if (!aligned16(d_probes) || !aligned16(d_out))
+        return fail(c, PTRT_E_INVALID, "%s: probes %p and out %p must be 16-byte aligned", fn, (const void *)d_probes, (const void *)d_out);
+    if (need_geometry && !c->have_geometry)
+        return fail(c, PTRT_E_NOT_READY, "%s: geometry not uploaded", fn);
+    if (n == 0) {
+        done = true;
+        return PTRT_OK;
+    }
+    const size_t out_bytes = (size_t)n * sizeof(ptrt_probe_light);
+    const Span probes{"probes", d_probes, (size_t)rows * sizeof(ptrt_probe)};
+    const auto apart = [&](const Span &s) {
+        const uintptr_t x = (uintptr_t)d_out, y = (uintptr_t)s.p;
+        return x < y ? y - x >= out_bytes : x - y >= s.bytes;
+    };
+    if (!apart(probes))
+        return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps probes %p (%zu bytes)", fn, (const void *)d_out, out_bytes, probes.p,
+                    probes.bytes);
+    for (const Span &s : ins)
+        if (!apart(s))
+            return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, (const void *)d_out, out_bytes, s.name, s.p,
+                        s.bytes);
+    if (int rc = set_device(c))
+        return rc;
+    if (int rc = check_spans(c, fn, ins))
+        return rc;
+    if (int rc = check_spans(c, fn, {probes, {"out", d_out, out_bytes}}))
+        return rc;
+    V.probes = reinterpret_cast<const float4 *>(d_probes);
+    for (int a = 0; a < 3; ++a) {
+        V.origin[a] = volume->origin[a];
+        V.spacing[a] = volume->spacing[a];
+        V.counts[a] = volume->counts[a];
+    }
+    V.mode = mode;
+    V.bias = normal_bias;
+    return PTRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ptrt_probe_sample(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n, const ptrt_probe_volume *volume,
+                      const ptrt_probe *d_probes, int mode, float normal_bias, ptrt_probe_light *d_out) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_probe_sample: bad context");
+    pt::ProbeVolumeParams V{};
+    bool done = false;
+    const size_t points = (size_t)(n > 0 ? n : 0);
+    if (int rc = check_probe_volume(c, "ptrt_probe_sample", n, volume, d_probes, mode, normal_bias, d_out,
+                                    {{"positions", d_positions, points * 12}, {"normals", d_normals, points * 12}}, false, V, done))
+        return rc;
+    if (done)
+        return PTRT_OK;
+    c->touched = true;
+    // probe_sample_kernel (pt_probe_sample.hip.h): one thread per point; n < 2^31, so the grid's x extent fits
+    hipLaunchKernelGGL(pt::probe_sample_kernel, dim3((unsigned)((points + 255) / 256)), dim3(256), 0, c->stream, d_positions, d_normals,
+                       points, V, reinterpret_cast<float4 *>(d_out));
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+int ptrt_query_probe_light(ptrt_ctx *c, const float *d_origins, const float *d_directions, int n, const ptrt_probe_volume *volume,
+                           const ptrt_probe *d_probes, int mode, float normal_bias, ptrt_probe_light *d_out) {
+    if (!ctx_live(c, false))
+        return fail(c, PTRT_E_INVALID, "ptrt_query_probe_light: bad context");
+    pt::ProbeVolumeParams V{};
+    bool done = false;
+    const size_t rays = (size_t)(n > 0 ? n : 0);
+    if (int rc = check_probe_volume(c, "ptrt_query_probe_light", n, volume, d_probes, mode, normal_bias, d_out,
+                                    {{"origins", d_origins, rays * 12}, {"directions", d_directions, rays * 12}}, true, V, done))
+        return rc;
+    if (done)
+        return PTRT_OK;
+    QueryPlan P;
+    if (int rc = plan_query(c, false, 0, 0, P))
+        return rc;
+    // probe_light_query_kernel (pt_probe_sample.hip.h): ray_query_kernel's grid, chunks of 64 rays
+    float4 *o = reinterpret_cast<float4 *>(d_out);
+    return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+        return launch_persistent(c, pt::probe_light_query_kernel<G, PM>, P.lds, (rays + 63) / 64, false, P.K, d_origins, d_directions, rays, V,
+                                 o);
     });
 }
 

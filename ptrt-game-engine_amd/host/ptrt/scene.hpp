@@ -1076,6 +1076,25 @@ class Scene {
                                   d_out),
               "Lightmap query failed");
     }
+    // A probe volume read at surface points (ptrt_probe_sample): one 32-byte ptrt_probe_light per point -- the irradiance the
+    // grid `volume` of ptrt_probe records d_probes (queryProbes' output, probe (i, j, k) in row i + nx*(j + ny*k)) gives at
+    // d_positions[i] for the normal d_normals[i]: the eight probes round the point, trilinear (mode PTRT_PROBES_TRILINEAR) or
+    // weighted further by facing and a Chebyshev visibility test on the probes' distance moments (PTRT_PROBES_VISIBILITY), from
+    // the point moved normal_bias along its normal.  Needs no scene.
+    void probeSample(const float *d_positions, const float *d_normals, int n, const ptrt_probe_volume &volume, const ptrt_probe *d_probes,
+                     int mode, float normal_bias, ptrt_probe_light *d_out) {
+        needBackend();
+        check(ptrt_probe_sample(ctx, d_positions, d_normals, n, &volume, d_probes, mode, normal_bias, d_out), "Probe sampling failed");
+    }
+    // The same for n rays traced here (ptrt_query_probe_light): what probeSample gives for the point and normal columns of
+    // queryClosestDevice's records of these rays, byte for byte, with the hit's face and mesh, in one launch and without the
+    // records.  Commits what queryClosestDevice commits.
+    void queryProbeLight(const float *d_origins, const float *d_dirs, int n, const ptrt_probe_volume &volume, const ptrt_probe *d_probes,
+                         int mode, float normal_bias, ptrt_probe_light *d_out) {
+        needBackend();
+        updateAccelerationStructures();
+        check(ptrt_query_probe_light(ctx, d_origins, d_dirs, n, &volume, d_probes, mode, normal_bias, d_out), "Probe light query failed");
+    }
     // The primary rays render_to_device would give sample `sample` of frame `frame` (ptrt_camera_rays; pinhole cameras only):
     // tile rows * width * 3 floats each, in the order of the colour buffer.
     void cameraRays(int frame, int sample, float *d_origins, float *d_dirs) {

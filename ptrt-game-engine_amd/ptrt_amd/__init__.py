@@ -12,6 +12,7 @@ and if there is no HIP device ``Scene(..., device>=0)`` raises.  A ``device=-1``
 scene is host-only (build / flatten / inspect) and cannot render.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -146,6 +147,11 @@ class AtlasTexel(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("face", C.c_int32), ("normal", C.c_float * 3), ("mesh", C.c_int32)]
 
 
+class ProbeVolumeDesc(C.Structure):
+    """`ptrt_probe_volume`: a regular grid of light probes for ptrt_probe_sample / ptrt_query_probe_light (host memory)."""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("counts", C.c_int32 * 3)]
+
+
 class Stats(C.Structure):
     _fields_ = [("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64),
                 ("shadow_rays_walked", C.c_uint64)]
@@ -193,6 +199,10 @@ LIGHTMAP_SAMPLE_DTYPE = np.dtype([("rgb", "<f4", 3), ("weight", "<f4"), ("x", "<
 assert LIGHTMAP_SAMPLE_DTYPE.itemsize == 32
 LIGHTMAP_NEAREST, LIGHTMAP_BILINEAR = 0, 1  # PTRT_LIGHTMAP_*
 LIGHTMAP_MODES = dict(nearest=LIGHTMAP_NEAREST, bilinear=LIGHTMAP_BILINEAR)
+PROBE_LIGHT_DTYPE = np.dtype([("irradiance", "<f4", 3), ("weight", "<f4"), ("cell", "<i4"), ("used", "<i4"), ("face", "<i4"), ("mesh", "<i4")])
+assert PROBE_LIGHT_DTYPE.itemsize == 32 and C.sizeof(ProbeVolumeDesc) == 36
+PROBES_TRILINEAR, PROBES_VISIBILITY = 0, 1  # PTRT_PROBES_*
+PROBES_MODES = dict(trilinear=PROBES_TRILINEAR, visibility=PROBES_VISIBILITY)
 TLAS_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("start", "<i4"),
                             ("count", "<i4")])
 assert TLAS_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 40
@@ -245,6 +255,8 @@ _sig("ptrt_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("ptrt_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
 _sig("ptrt_atlas_sample", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("ptrt_query_lightmap", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("ptrt_probe_sample", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, _vp)
+_sig("ptrt_query_probe_light", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, _vp)
 _sig("ptrt_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("ptrt_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("ptrt_get_stats", C.c_int, _vp, C.POINTER(Stats))
@@ -384,6 +396,8 @@ _sig("hs_atlas_dilate", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int)
 _sig("hs_atlas_filter", C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int)
 _sig("hs_atlas_sample", C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
 _sig("hs_query_lightmap", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp)
+_sig("hs_probe_sample", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, _vp)
+_sig("hs_query_probe_light", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, _vp)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
@@ -1532,6 +1546,87 @@ class Scene:
         self._enqueue_between_streams(image.device, lambda: self._chk(lib.hs_query_lightmap(
             self._h, _vp(origins.data_ptr()), _vp(directions.data_ptr()), n, _vp(charts.data_ptr()), int(charts.shape[0]),
             _vp(chart_first.data_ptr()), _vp(image.data_ptr()), w, h, mode, _vp(out.data_ptr()))))
+        return out
+
+    @staticmethod
+    def _probe_volume(what, volume, mode, normal_bias):
+        """what needs no tensor: (ptrt_probe_volume, its row count, the mode's number, the bias)"""
+        if mode not in PROBES_MODES:
+            raise ValueError(f"{what}: mode {mode!r} ('trilinear' or 'visibility')")
+        try:
+            desc = ProbeVolumeDesc((C.c_float * 3)(*[float(x) for x in volume.origin]), (C.c_float * 3)(*[float(x) for x in volume.spacing]),
+                                   (C.c_int32 * 3)(*[int(x) for x in volume.counts]))
+        except (AttributeError, TypeError, IndexError, ValueError) as e:
+            raise ValueError(f"{what}: volume: needs a probes.ProbeVolume (origin, spacing, counts): {e}") from None
+        counts = [int(x) for x in desc.counts]
+        rows = counts[0] * counts[1] * counts[2]
+        if min(counts) < 1 or rows > 2 ** 24:
+            raise ValueError(f"{what}: volume: counts {counts} (each >= 1, at most 2^24 probes)")
+        if not all(math.isfinite(x) and x > 0.0 for x in desc.spacing) or not all(math.isfinite(x) for x in desc.origin):
+            raise ValueError(f"{what}: volume: spacing {list(desc.spacing)} (positive and finite), origin {list(desc.origin)} (finite)")
+        normal_bias = float(normal_bias)
+        if not (normal_bias >= 0.0 and math.isfinite(normal_bias)):
+            raise ValueError(f"{what}: normal_bias {normal_bias} (>= 0 and finite)")
+        return desc, rows, PROBES_MODES[mode], normal_bias
+
+    def _probe_tensors(self, what, n, rows, probes, out):
+        self._device_tensor(f"{what}: probes", probes, 32, "torch.float32")
+        if probes.shape[0] != rows:
+            raise ValueError(f"{what}: probes has {probes.shape[0]} rows for a volume of {rows} probes")
+        if n >= 2 ** 31:
+            raise ValueError(f"{what}: {n} rows (at most 2^31 - 1 per call)")
+        import torch
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.int32, device=probes.device)
+        else:
+            self._device_tensor(f"{what}: out", out, 8, "torch.int32")
+            if out.shape[0] != n:
+                raise ValueError(f"{what}: out has {out.shape[0]} rows for {n}")
+        return out
+
+    def probe_sample(self, positions, normals, volume, probes, mode="visibility", normal_bias=0.0, out=None):
+        """A probe volume read at surface points (ptrt_probe_sample).  torch tensors on this scene's device, contiguous, read
+        in place: `positions` and `normals`, (n, 3) float32 (normals are used as given: pass unit ones); `probes`, the
+        (nx * ny * nz, 32) float32 rows query_probes returns for `volume.positions()`.  `volume`: a `probes.ProbeVolume`.
+        `mode`: 'trilinear' -- the eight probes round the point by their trilinear weights -- or 'visibility' -- each weight
+        multiplied further by how far the probe faces the normal and by a Chebyshev test of the probe's two distance moments
+        against its distance from the point moved `normal_bias` along its normal, so that a probe behind a wall counts for
+        little.  Returns an (n, 8) int32 tensor, one 32-byte `ptrt_probe_light` per row (`probes.probe_light_fields` names the
+        columns): the irradiance (0:3) and the weight of the corners used (3; 0: nothing to light with) as float32 bits, the
+        footprint's first row (4; -1: the point is not finite), the corners used as bits (5), face and mesh (6, 7; -1 here).
+        `out` takes such a tensor.  No synchronisation.  Needs no geometry."""
+        desc, rows, mode, normal_bias = self._probe_volume("probe_sample", volume, mode, normal_bias)
+        self._device_tensor("probe_sample: positions", positions, 3, "torch.float32")
+        self._device_tensor("probe_sample: normals", normals, 3, "torch.float32")
+        n = int(positions.shape[0])
+        if normals.shape[0] != n:
+            raise ValueError(f"probe_sample: {n} positions, {normals.shape[0]} normals")
+        out = self._probe_tensors("probe_sample", n, rows, probes, out)
+        if n == 0:
+            return out
+        self._enqueue_between_streams(probes.device, lambda: self._chk(lib.hs_probe_sample(
+            self._h, _vp(positions.data_ptr()), _vp(normals.data_ptr()), n, C.byref(desc), _vp(probes.data_ptr()), mode, normal_bias,
+            _vp(out.data_ptr()))))
+        return out
+
+    def query_probe_light(self, origins, directions, volume, probes, mode="visibility", normal_bias=0.0, out=None):
+        """The probe volume's irradiance at the closest hit of every ray (ptrt_query_probe_light): what `probe_sample` returns
+        for the point and normal columns of `query_closest(origins, directions)`, byte for byte, from one kernel that never
+        writes the hit records; face and mesh (columns 6, 7) are the hit's, and a miss is the row (0, 0, 0, 0, -1, 0, -1, -1).
+        origins and directions: (n, 3) float32 tensors on this scene's device, contiguous; the rest as for probe_sample.  A
+        probe-lit view of the scene is `camera_rays`, then this, then `probes.shade_probe_light`.  No synchronisation."""
+        desc, rows, mode, normal_bias = self._probe_volume("query_probe_light", volume, mode, normal_bias)
+        self._device_tensor("query_probe_light: origins", origins, 3, "torch.float32")
+        self._device_tensor("query_probe_light: directions", directions, 3, "torch.float32")
+        n = int(origins.shape[0])
+        if directions.shape[0] != n:
+            raise ValueError(f"query_probe_light: {n} origins, {directions.shape[0]} directions")
+        out = self._probe_tensors("query_probe_light", n, rows, probes, out)
+        if n == 0:
+            return out
+        self._enqueue_between_streams(probes.device, lambda: self._chk(lib.hs_query_probe_light(
+            self._h, _vp(origins.data_ptr()), _vp(directions.data_ptr()), n, C.byref(desc), _vp(probes.data_ptr()), mode, normal_bias,
+            _vp(out.data_ptr()))))
         return out
 
     def camera_rays(self, frame, sample=0):
