@@ -1320,7 +1320,9 @@ int ptrt_set_stream(ptrt_ctx *ctx, void *hip_stream);
 
 /* Durations (ms) of the most recent path-trace kernel launches, oldest first, measured with
  * HIP events on the stream the kernel ran on; at most 256 are kept.  Synchronises.  Returns
- * the number written (<= max_n) or a negative error. */
+ * the number written (<= max_n) or a negative error.  A launch's duration is asked of the runtime
+ * once and kept (here, in ptrt_last_kernel_ms and in ptrt_launch_ms_history): the same launch reads
+ * the same float every time, whatever ran in between. */
 int ptrt_kernel_ms_history(ptrt_ctx *ctx, float *out_ms, int max_n);
 
 /* Frames that overlap on the device (option "pipeline") run as `split` launches on auxiliary streams; the events of

@@ -162,6 +162,25 @@ def render(scene_desc_ptr, width, height, spp, max_depth, frame_count, blue_nois
     return out
 
 
+lib.oracle_primary_rays.argtypes = [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _up, _fp]
+lib.oracle_primary_rays.restype = C.c_int
+
+
+def primary_rays(scene_desc_ptr, width, height, frame_index, blue_noise, rng, tile_y0=0, tile_rows=0):
+    """The primary rays of one sample (frame_index = frame_count + s) of a tile's pixels, as oracle_render's pixels make
+    them: dict(jitter (n, 2), uv (n, 2), origin (n, 3), direction (n, 3)).  `rng` advances in place by the lens's draws."""
+    rows = tile_rows if tile_rows > 0 else height
+    n = rows * width
+    assert rng.shape == (n, 6) and rng.dtype == np.uint32 and rng.flags.c_contiguous
+    bn = np.ascontiguousarray(blue_noise, dtype=np.float32)
+    out = np.zeros((n, 10), np.float32)
+    rc = lib.oracle_primary_rays(C.cast(scene_desc_ptr, C.c_void_p), _f(bn), width, height, tile_y0, rows, frame_index,
+                                 _u(rng), _f(out))
+    if rc != 0:
+        raise RuntimeError(f"oracle_primary_rays failed ({rc}); -2 means the CPU lacks FMA")
+    return dict(jitter=out[:, 0:2].copy(), uv=out[:, 2:4].copy(), origin=out[:, 4:7].copy(), direction=out[:, 7:10].copy())
+
+
 def tonemap(accum, width, rows, threads=1):
     acc = np.ascontiguousarray(accum, dtype=np.float32)
     out = np.zeros((rows, width, 3), dtype=np.uint8)

@@ -1507,6 +1507,20 @@ inline Ray camera_get_ray(const ptrt_camera &c, float s, float t, Xorwow &rng) {
     return Ray(origin + offset, normalize(ray_dir), true);
 }
 
+// the primary ray of one sample (scene_kernels.cuh:152-167), with what it was made of: {jitter_x, jitter_y, u, v}
+inline Ray primary_ray_sample(const ptrt_camera &cam, const float *blue_noise, int x, int y, int width, int height,
+                              int frame_index, Xorwow &rng, float made_of[4]) {
+    float tjx, tjy, bnx, bny;
+    getTAAJitter(frame_index, tjx, tjy);
+    next_blue_noise(blue_noise, x, y, frame_index, bnx, bny);
+    float jitter_x = tjx + (bnx - 0.5f) * 0.25f;
+    float jitter_y = tjy + (bny - 0.5f) * 0.25f;
+    const float u = (x + 0.5f + jitter_x) / width;
+    const float v = 1.0f - (y + 0.5f + jitter_y) / height;
+    made_of[0] = jitter_x; made_of[1] = jitter_y; made_of[2] = u; made_of[3] = v;
+    return camera_get_ray(cam, u, v, rng);
+}
+
 // one pixel of path_trace_kernel (scene_kernels.cuh:130-193)
 inline void path_trace_pixel(const ptrt_scene_desc &S, const float *blue_noise, int x, int y, int width,
                              int height, int spp, int max_depth, int frame_count, Xorwow &rng, float *accum3,
@@ -1516,14 +1530,8 @@ inline void path_trace_pixel(const ptrt_scene_desc &S, const float *blue_noise, 
     float first_depth = 1e30f;
     int first_objectId = -1;
     for (int s = 0; s < spp; ++s) {
-        float tjx, tjy, bnx, bny;
-        getTAAJitter(frame_count + s, tjx, tjy);
-        next_blue_noise(blue_noise, x, y, frame_count + s, bnx, bny);
-        float jitter_x = tjx + (bnx - 0.5f) * 0.25f;
-        float jitter_y = tjy + (bny - 0.5f) * 0.25f;
-        const float u = (x + 0.5f + jitter_x) / width;
-        const float v = 1.0f - (y + 0.5f + jitter_y) / height;
-        Ray ray = camera_get_ray(S.camera, u, v, rng);
+        float made_of[4];
+        Ray ray = primary_ray_sample(S.camera, blue_noise, x, y, width, height, frame_count + s, rng, made_of);
         V3 sample_normal;
         float sample_depth = 0.0f;
         int sample_objectId = -1;
@@ -1717,6 +1725,35 @@ int oracle_render(const ptrt_scene_desc *scene, oracle_render_args *a) {
         a->shadow_rays += c.shadow;
         a->paths += c.paths;
         a->shadow_rays_walked += c.shadow - c.shadow_zero;
+    }
+    return 0;
+}
+
+/* The primary rays of ONE sample of a tile's pixels, by the function oracle_render's pixels call: out10 = rows*W rows of
+ * {jitter_x, jitter_y, u, v, origin, direction}; `frame_index` is frame_count + s, `rng` the states at that sample's
+ * head, advanced by the lens's draws.  For tests/frame_truth.py, which measures these against its statement. */
+int oracle_primary_rays(const ptrt_scene_desc *scene, const float *blue_noise, int width, int height, int tile_y0,
+                        int tile_rows, int frame_index, uint32_t *rng, float *out10) {
+    if (!scene || !blue_noise || !rng || !out10 || width <= 0 || height <= 0 || tile_y0 < 0 || tile_rows < 0 ||
+        tile_y0 + tile_rows > height)
+        return -1;
+    if (!oracle_has_fma())
+        return -2;
+    for (int r = 0; r < tile_rows; ++r) {
+        for (int x = 0; x < width; ++x) {
+            const size_t i = (size_t)r * width + x;
+            Xorwow s;
+            s.d = rng[i * 6];
+            for (int k = 0; k < 5; ++k)
+                s.v[k] = rng[i * 6 + 1 + k];
+            float *o = out10 + i * 10;
+            Ray ray = primary_ray_sample(scene->camera, blue_noise, x, tile_y0 + r, width, height, frame_index, s, o);
+            o[4] = ray.orig.x; o[5] = ray.orig.y; o[6] = ray.orig.z;
+            o[7] = ray.dir.x; o[8] = ray.dir.y; o[9] = ray.dir.z;
+            rng[i * 6] = s.d;
+            for (int k = 0; k < 5; ++k)
+                rng[i * 6 + 1 + k] = s.v[k];
+        }
     }
     return 0;
 }

@@ -280,6 +280,13 @@ struct ptrt_ctx {
     int time_launches = 0;
     std::vector<hipEvent_t> launch_ev[MAX_SPLIT]; // 3 * EV_RING per auxiliary stream
     unsigned char launch_timed[EV_RING] = {};     // launches of frame (launches % EV_RING) that carry events (0: none)
+    // An interval between two recorded events is asked of the runtime ONCE and kept until the slot's events are recorded again:
+    // hipEventElapsedTime may read the same pair a nanosecond differently the next time (the runtime re-fits its tick-to-time
+    // conversion now and then), and a history must not move because something else ran in between
+    float ev_ms[EV_RING] = {};                    // ... of ev_ring's pair of a slot
+    bool ev_ms_known[EV_RING] = {};
+    float launch_ms[MAX_SPLIT][EV_RING][2] = {};  // ... of launch_ev's two intervals
+    bool launch_ms_known[MAX_SPLIT][EV_RING] = {};
     // option "tm_prio" (lane refill's tonemap pass): bit 0 = the pass runs on a stream of the highest priority, forked from
     // and joined to the launch's stream by events; bit 1 = its waves raise their issue priority (s_setprio 3)
     int tm_prio = 0;
@@ -1117,6 +1124,8 @@ int ptrt_set_stream(ptrt_ctx *c, void *hip_stream) {
     c->launches = 0;
     c->timed = false;
     memset(c->launch_timed, 0, sizeof c->launch_timed);
+    memset(c->ev_ms_known, 0, sizeof c->ev_ms_known);
+    memset(c->launch_ms_known, 0, sizeof c->launch_ms_known);
     return PTRT_OK;
 }
 

@@ -776,6 +776,9 @@ int ptrt_render(ptrt_ctx *c, int frame_index, int spp, int max_depth, void *out_
             return rc;
     const int slot = (int)(c->launches % EV_RING);
     const bool timing = c->time_kernels || P.tuning;
+    c->ev_ms_known[slot] = false; // (the slot's events are recorded anew: the intervals kept of them are another frame's)
+    for (int i = 0; i < ptrt_ctx::MAX_SPLIT; ++i)
+        c->launch_ms_known[i][slot] = false;
     if (timing)
         HIP_TRY(c, hipEventRecord(c->ev_ring[2 * slot], c->stream));
     // frame pipelining (options "split" / "pipeline"): may this frame's launches follow the previous frame's instead of the stream?
@@ -843,6 +846,20 @@ int ptrt_post_frame(ptrt_ctx *c, const float *accum, const float *normal, const 
     return finish_frame(c, K, frame_rgb8, false, out_rgb8 && out_is_device, out_rgb8, out_is_device);
 }
 
+} // extern "C"
+
+// The duration of the frame whose events slot `slot` of ev_ring holds (both complete): asked of the runtime once, then kept.
+static int slot_ms(ptrt_ctx *c, int slot, float *ms) {
+    if (!c->ev_ms_known[slot]) {
+        HIP_TRY(c, hipEventElapsedTime(&c->ev_ms[slot], c->ev_ring[2 * slot], c->ev_ring[2 * slot + 1]));
+        c->ev_ms_known[slot] = true;
+    }
+    *ms = c->ev_ms[slot];
+    return PTRT_OK;
+}
+
+extern "C" {
+
 int ptrt_last_kernel_ms(ptrt_ctx *c, float *trace_ms, float *tonemap_ms) {
     if (!ctx_live(c) || !c->timed)
         return fail(c, PTRT_E_NOT_READY, "ptrt_last_kernel_ms: nothing rendered yet");
@@ -851,7 +868,8 @@ int ptrt_last_kernel_ms(ptrt_ctx *c, float *trace_ms, float *tonemap_ms) {
     const int slot = (int)((c->launches - 1) % EV_RING);
     HIP_TRY(c, hipEventSynchronize(c->ev_ring[2 * slot + 1]));
     float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_ring[2 * slot], c->ev_ring[2 * slot + 1]));
+    if (int rc = slot_ms(c, slot, &ms))
+        return rc;
     if (trace_ms)
         *trace_ms = ms;
     if (tonemap_ms)
@@ -872,7 +890,8 @@ int ptrt_kernel_ms_history(ptrt_ctx *c, float *out_ms, int max_n) {
         n = max_n;
     for (unsigned long long i = 0; i < n; ++i) {
         const int slot = (int)((c->launches - n + i) % EV_RING);
-        HIP_TRY(c, hipEventElapsedTime(&out_ms[i], c->ev_ring[2 * slot], c->ev_ring[2 * slot + 1]));
+        if (int rc = slot_ms(c, slot, &out_ms[i]))
+            return rc;
     }
     return (int)n;
 }
@@ -898,8 +917,13 @@ int ptrt_launch_ms_history(ptrt_ctx *c, float *trace_ms, float *tail_ms, int max
                 float t = 0.0f, u = 0.0f;
                 hipEvent_t *ev = &c->launch_ev[i][3 * slot];
                 HIP_TRY(c, hipEventSynchronize(ev[2]));
-                HIP_TRY(c, hipEventElapsedTime(&t, ev[0], ev[1]));
-                HIP_TRY(c, hipEventElapsedTime(&u, ev[1], ev[2]));
+                if (!c->launch_ms_known[i][slot]) {
+                    HIP_TRY(c, hipEventElapsedTime(&c->launch_ms[i][slot][0], ev[0], ev[1]));
+                    HIP_TRY(c, hipEventElapsedTime(&c->launch_ms[i][slot][1], ev[1], ev[2]));
+                    c->launch_ms_known[i][slot] = true;
+                }
+                t = c->launch_ms[i][slot][0];
+                u = c->launch_ms[i][slot][1];
                 a.push_back(t);
                 b.push_back(u);
             }
