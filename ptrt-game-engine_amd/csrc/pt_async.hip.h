@@ -136,25 +136,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                     h.slot = gslot;
                     hmesh = gmesh;
                     if (h.mesh < 0) {
-                        if (bounce == 0 && s == 0) {
-                            K.normal[idx * 3 + 0] = 0.0f;
-                            K.normal[idx * 3 + 1] = 0.0f;
-                            K.normal[idx * 3 + 2] = 0.0f;
-                            K.depth[idx] = 1e30f;
-                            K.object_id[idx] = -1;
-                        }
+                        if (bounce == 0 && s == 0) // HitInfo() defaults
+                            FirstHitToFrame{K, idx}(1e30f, mk3(0.0f), -1);
                         add_miss_radiance(K, rd, throughput, acc);
                         end_path = true;
                     } else {
                         run_e = true;
                         hit = make_surface(K, h, ro, rd, nullptr, nullptr);
-                        if (bounce == 0 && s == 0) {
-                            K.normal[idx * 3 + 0] = hit.normal.x;
-                            K.normal[idx * 3 + 1] = hit.normal.y;
-                            K.normal[idx * 3 + 2] = hit.normal.z;
-                            K.depth[idx] = hit.t;
-                            K.object_id[idx] = h.mesh;
-                        }
+                        if (bounce == 0 && s == 0)
+                            FirstHitToFrame{K, idx}(hit.t, hit.normal, h.mesh);
                         const float4 m0 = K.materials[h.mesh * 6 + 0], m2 = K.materials[h.mesh * 6 + 2];
                         absorb_and_emit(m0, m2, hit, bounce == 0 || prev_was_specular, throughput, acc);
                         if (!ray_spec && K.n_lights > 0) {
@@ -190,12 +180,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                     if (s < K.spp) {
                         need_regen = true;
                     } else { // the pixel is complete (scene_kernels.cuh:173-193, tonemap_kernel scene.cuh:2004-2047)
-                        K.rng[idx] = rng.d;
-                        K.rng[npix + idx] = rng.v0;
-                        K.rng[2 * npix + idx] = rng.v1;
-                        K.rng[3 * npix + idx] = rng.v2;
-                        K.rng[4 * npix + idx] = rng.v3;
-                        K.rng[5 * npix + idx] = rng.v4;
+                        store_rng_planes(K.rng, npix, idx, rng);
                         const f3 out = avg_color / (float)K.spp;
                         K.accum[idx * 3 + 0] = out.x;
                         K.accum[idx * 3 + 1] = out.y;
@@ -222,18 +207,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                     const int rank = lane_prefix(takers);
                     if (rank < n_take) {
                         const uint32_t q = ring[(ring_head + rank) & (AS_RING - 1)];
-                        const int tile = (int)(q >> 6), l = (int)(q & 63u);
-                        const int tx = tile % K.tiles_x, ty = tile / K.tiles_x;
-                        x = tx * 8 + (l & 7);
-                        yl = ty * 8 + (l >> 3);
+                        tile_pixel(K.tiles_x, (int)(q >> 6), (int)(q & 63u), x, yl);
                         if (x < K.width && yl < K.rows) { // (a tile on the frame's edge has positions outside it)
                             idx = (size_t)yl * K.width + x;
-                            rng.d = K.rng[idx];
-                            rng.v0 = K.rng[npix + idx];
-                            rng.v1 = K.rng[2 * npix + idx];
-                            rng.v2 = K.rng[3 * npix + idx];
-                            rng.v3 = K.rng[4 * npix + idx];
-                            rng.v4 = K.rng[5 * npix + idx];
+                            load_rng_planes(rng, K.rng, npix, idx);
                             avg_color = mk3(0.0f);
                             s = 0;
                             need_regen = true;
@@ -245,32 +222,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_WAVES_PER
                 ring_head = (ring_head + n_take) & (AS_RING - 1);
                 ring_n -= n_take;
             }
-            if (need_regen) { // ---- [A] primary ray (scene_kernels.cuh:147-167, camera.cuh:156-205)
+            if (need_regen) { // ---- [A] primary ray (scene_kernels.cuh:147-167, camera.cuh:156-205): pt_path.hip.h
                 const int y = global_row(yl, K.y0, K.il_period, K.il_phase);
-                float tjx, tjy, bnx, bny;
-                taa_jitter(K.frame_count + s, tjx, tjy);
-                blue_noise_jitter(K.blue_noise, x, y, K.frame_count + s, bnx, bny);
-                const float jitter_x = tjx + (bnx - 0.5f) * 0.25f;
-                const float jitter_y = tjy + (bny - 0.5f) * 0.25f;
-                const float u = ((float)x + 0.5f + jitter_x) / (float)K.width;
-                const float v = 1.0f - ((float)y + 0.5f + jitter_y) / (float)K.height;
-                if (K.cam.lens_radius <= 0) {
-                    const f3 dir = K.cam.llc + u * K.cam.horizontal + v * K.cam.vertical - K.cam.origin;
-                    ro = K.cam.origin;
-                    rd = normalize(dir);
-                } else {
-                    f3 p;
-                    do {
-                        const float a = rng_uniform(rng);
-                        const float b = rng_uniform(rng);
-                        p = 2.0f * mk3(a, b, 0.0f) - mk3(1.0f, 1.0f, 0.0f);
-                    } while (dot(p, p) >= 1.0f);
-                    const f3 rdisk = K.cam.lens_radius * p;
-                    const f3 offset = K.cam.u * rdisk.x + K.cam.v * rdisk.y;
-                    const f3 dir = K.cam.llc + u * K.cam.horizontal + v * K.cam.vertical - K.cam.origin - offset;
-                    ro = K.cam.origin + offset;
-                    rd = normalize(dir);
-                }
+                float u, v;
+                pixel_uv(K, x, y, K.frame_count + s, u, v);
+                camera_ray(K.cam, u, v, rng, ro, rd);
                 ray_spec = true;
                 prev_was_specular = true;
                 throughput = mk3(1.0f);

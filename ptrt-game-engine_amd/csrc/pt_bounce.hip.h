@@ -13,10 +13,9 @@
 // no second estimator to balance against (ptrt_query_direct applies none either).  The soft clamp is kept: it belongs to the
 // BSDF product.  All of it is stated once, in bounce_sample, for both kernels.
 //
-// The frame is irradiance_query_kernel's: one-wave workgroups, a persistent grid over groups of 64 / w texels (w the smallest
-// power of two >= n_dirs, 64 beyond; chunks of 64 directions beyond), stage_pair_lds, texel_ray, segment_fold_sum.  A lane is
-// gather ray (t, k): ONE closest-hit walk, then a wave-uniform loop over q in which every lane that hit forms its sample and ONE
-// any-hit call runs with `walked` as its live mask, skipped by ballot when no lane walks; a lane adds its unblocked values in q
+// The frame is the queries' one and the bakes' texel frame (pt_query.hip.h: query_stage, walk_closest, walk_occluded,
+// texel_shape, texel_ray, segment_fold_sum); the row store is the kernel's own.  A lane is gather ray (t, k):
+// ONE closest-hit walk, then a wave-uniform loop over q in which every lane that hit forms its sample and ONE any-hit call runs with `walked` as its live mask, skipped by ballot when no lane walks; a lane adds its unblocked values in q
 // order from +0.0f and counts its lit and blocked terms.  Behind the loop the six quantities -- B = sum / (float)n_shadow per
 // channel, the two counts as floats, hit ? 1 : 0 -- are reduced over k exactly as the irradiance query reduces its six.  The
 // lights are read from memory as in direct_query_kernel, the materials as in trace_chunk_samples.
@@ -87,23 +86,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_waves
     const KParams &K = kparams(kp0); // staging
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
+    const LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
-    PL.cyc = &cyc;
-    PL.stat_bounce = 0;
-    __syncthreads();
-    // the work shape (wave-uniform), irradiance_query_kernel's
-    int log2w = 0;
-    while (log2w < 6 && (1 << log2w) < n_dirs)
-        ++log2w;
-    const bool chunked = n_dirs > 64;
-    const int chunks = chunked ? (int)(((uint32_t)n_dirs + 63u) / 64u) : 1;
-    const uint32_t groups = ((uint32_t)n_texels + (64u >> log2w) - 1u) >> (6 - log2w);
+    const PairLds PL = query_stage<PMODE>(K, lds_raw, lane, cyc);
+    const TexelShape S = texel_shape(n_texels, n_dirs);
+    const int log2w = S.log2w;
     const float f_dirs = (float)n_dirs, f_shadow = (float)n_shadow, f_all = (float)(n_dirs * n_terms); // (n_dirs * Q fits an int: the host)
-    for (uint32_t g = blockIdx.x; g < groups; g += gridDim.x) { // (wave-uniform)
+    for (uint32_t g = blockIdx.x; g < S.groups; g += gridDim.x) { // (wave-uniform)
         float total = 0.0f; // beyond 64 directions, lane i: the running total of quantity i
-        for (int c = 0; c < chunks; ++c) { // (wave-uniform)
+        for (int c = 0; c < S.chunks; ++c) { // (wave-uniform)
             f3 ro = mk3(0.0f), rd = mk3(0.0f);
             float phase = 0.0f;
             bool live;
@@ -118,11 +109,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_waves
             }
             // ---- the gather ray's closest hit, all live lanes together
             const KParams &KB = kparams(kp0);
-            int h_order = 0;
-            const Hit h = (PMODE == 1)   ? closest_hit_pairs(KB, PL, lane, live, ro, rd, h_order)
-                          : (PMODE == 2) ? closest_hit_pairs_dyn(KB, PL, lane, live, ro, rd)
-                          : (PMODE == 3) ? closest_hit_pairs_tlas(KB, PL, lane, live, ro, rd, cyc)
-                                         : closest_hit<GEOM>(KB, live, ro, rd, stk);
+            const Hit h = walk_closest<GEOM, PMODE>(KB, PL, stk, cyc, lane, live, ro, rd);
             const KParams &KC = kparams(kp0);
             const bool struck = live && h.mesh >= 0;
             Surface hit;
@@ -155,10 +142,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_waves
                 }
                 if (__builtin_amdgcn_ballot_w64(walked)) { // (wave-uniform)
                     const KParams &KD = kparams(kp0);
-                    const bool blocked = (PMODE == 1)   ? any_hit_pairs(KD, PL, lane, walked, o, L, tm)
-                                         : (PMODE == 2) ? any_hit_pairs_dyn(KD, PL, lane, walked, o, L, tm)
-                                         : (PMODE == 3) ? any_hit_pairs_tlas(KD, PL, lane, walked, o, L, tm, cyc)
-                                                        : any_hit<GEOM>(KD, walked, o, L, tm, stk);
+                    const bool blocked = walk_occluded<GEOM, PMODE>(KD, PL, stk, cyc, lane, walked, o, L, tm);
                     if (walked && !blocked) {
                         sum = sum + value;
                         ++n_lit;
@@ -177,7 +161,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_waves
             const float s_lit = segment_fold_sum((float)n_lit, w);
             const float s_dark = segment_fold_sum((float)n_dark, w);
             const float s_hit = segment_fold_sum(struck ? 1.0f : 0.0f, w);
-            if (!chunked) {
+            if (!S.chunked) {
                 // one chunk: its sum added to a total that starts at +0.0f, divided, stored by the segment's first lane
                 if (r.k == 0 && r.t < (uint32_t)n_texels) {
                     float *row = reinterpret_cast<float *>(out + r.t);
@@ -201,7 +185,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_waves
                 total = total + mine; // chunk sums in chunk order, from +0.0f
             }
         }
-        if (chunked && lane < 8) // the texel's 32-byte row (the group is the texel); reserved is 0.0f
+        if (S.chunked && lane < 8) // the texel's 32-byte row (the group is the texel); reserved is 0.0f
             reinterpret_cast<float *>(out + g)[lane] = (lane == 3 || lane == 4) ? total / f_all : lane < 6 ? total / f_dirs : 0.0f;
     }
     cyc.flush(lane);

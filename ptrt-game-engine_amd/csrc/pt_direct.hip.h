@@ -10,17 +10,15 @@
 // q: the three channels divided by (float)n_shadow -- the sum over the lights of each light's mean --, and the counts of
 // unblocked and of blocked samples divided by (float)Q: one 32-byte DirectOut per texel.
 //
-// The frame is ray_query_kernel's: a persistent grid of one-wave workgroups, the LDS carve and staging by PMODE, six variants.
-// That frame stages no lights (the megakernel's PMODE 1 workgroup does, in a layout of its own), so the records are read from
-// memory: at most light_count * 64 bytes that every lane of the grid shares.  The work shape is irradiance_query_kernel's, with
-// Q in place of n_dirs: with w the smallest power of two >= Q (64 beyond), a wave owns 64 / w consecutive texels, lane l being
-// term l % w of texel slot l / w; beyond 64 terms a wave owns one texel and walks its ceil(Q / 64) chunks.  Per chunk every
-// lane forms its sample, ONE any-hit call runs with `walked` as its live mask -- a lane whose sample adds nothing either way
-// never enters the traversal --, and the five terms are reduced within each segment of w lanes by segment_fold_sum
-// (pt_irradiance.hip.h).  Dead lanes -- q >= Q, or a texel past the end -- take part in the collectives and contribute +0.0f.
-// Up to 64 terms a segment's first lane adds the sum to +0.0f, divides and stores the record; beyond, lane i adds the chunk's
-// sum of quantity i to its running total and lanes 0-7 divide and store at the end.  The sum order is part of the contract
-// (include/ptrt.h, tests/direct_restatement.py).
+// The frame is the queries' one (pt_query.hip.h: query_stage, walk_occluded): a persistent grid of one-wave workgroups, the LDS
+// carve and staging by PMODE, six variants.  That frame stages no lights (the megakernel's PMODE 1 workgroup does, in a layout
+// of its own), so the records are read from memory: at most light_count * 64 bytes that every lane of the grid shares.  The
+// work shape is the bakes' texel frame (pt_query.hip.h: texel_shape, texel_ray, segment_fold_sum) with Q terms per texel.  Per
+// chunk every lane forms its sample, ONE any-hit call runs with `walked` as its live mask -- a lane whose sample adds nothing
+// either way never enters the traversal --, and the five terms are reduced within each segment.  Dead lanes -- q >= Q, or a
+// texel past the end -- take part in the collectives and contribute +0.0f.  Up to 64 terms a segment's first lane adds the sum
+// to +0.0f, divides and stores the record; beyond, lane i adds the chunk's sum of quantity i to its running total and lanes 0-7
+// divide and store at the end.  The sum order is part of the contract (include/ptrt.h, tests/direct_restatement.py).
 #pragma once
 #include "pt_irradiance.hip.h"
 
@@ -74,25 +72,15 @@ __global__ __launch_bounds__(64) void direct_query_kernel(const KParams K, const
                                                           int n_terms, DirectOut *__restrict__ out) {
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
+    const LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
-    PL.cyc = &cyc;
-    PL.stat_bounce = 0;
-    __syncthreads();
-    // the work shape (wave-uniform): segments of w lanes, 64 / w texels per group, `chunks` chunks of 64 terms beyond Q = 64.
-    // Texel and group numbers fit 32 bits (n_texels + 63 < 2^32).
-    int log2w = 0;
-    while (log2w < 6 && (1 << log2w) < n_terms)
-        ++log2w;
-    const int w = 1 << log2w;
-    const bool chunked = n_terms > 64;
-    const int chunks = chunked ? (int)(((uint32_t)n_terms + 63u) / 64u) : 1;
-    const uint32_t groups = ((uint32_t)n_texels + (64u >> log2w) - 1u) >> (6 - log2w);
+    const PairLds PL = query_stage<PMODE>(K, lds_raw, lane, cyc);
+    const TexelShape S = texel_shape(n_texels, n_terms);
+    const int log2w = S.log2w, w = 1 << log2w;
     const float f_shadow = (float)n_shadow, f_terms = (float)n_terms;
-    for (uint32_t g = blockIdx.x; g < groups; g += gridDim.x) { // (wave-uniform)
+    for (uint32_t g = blockIdx.x; g < S.groups; g += gridDim.x) { // (wave-uniform)
         float total = 0.0f; // beyond 64 terms, lane i: the running total of quantity i
-        for (int c = 0; c < chunks; ++c) { // (wave-uniform)
+        for (int c = 0; c < S.chunks; ++c) { // (wave-uniform)
             const TexelRay r = texel_ray(lane, log2w, g, c); // (r.k: the term q)
             const bool live = r.t < (uint32_t)n_texels && r.k < (uint32_t)n_terms;
             f3 o = mk3(0.0f), d = mk3(0.0f), weight = mk3(0.0f);
@@ -110,10 +98,7 @@ __global__ __launch_bounds__(64) void direct_query_kernel(const KParams K, const
             }
             bool blocked = false;
             if (__builtin_amdgcn_ballot_w64(walked)) // (wave-uniform; a wave none of whose samples can add anything walks nothing, as phase [D] of the path loop)
-                blocked = (PMODE == 1)   ? any_hit_pairs(K, PL, lane, walked, o, d, tm)
-                          : (PMODE == 2) ? any_hit_pairs_dyn(K, PL, lane, walked, o, d, tm)
-                          : (PMODE == 3) ? any_hit_pairs_tlas(K, PL, lane, walked, o, d, tm, cyc)
-                                         : any_hit<GEOM>(K, walked, o, d, tm, stk);
+                blocked = walk_occluded<GEOM, PMODE>(K, PL, stk, cyc, lane, walked, o, d, tm);
             // the five terms, selected to +0.0f where the sample adds nothing, each folded within the segment
             const bool lit = walked && !blocked, dark = walked && blocked;
             const float s_r = segment_fold_sum(lit ? weight.x : 0.0f, w);
@@ -121,7 +106,7 @@ __global__ __launch_bounds__(64) void direct_query_kernel(const KParams K, const
             const float s_b = segment_fold_sum(lit ? weight.z : 0.0f, w);
             const float s_lit = segment_fold_sum(lit ? 1.0f : 0.0f, w);
             const float s_dark = segment_fold_sum(dark ? 1.0f : 0.0f, w);
-            if (!chunked) {
+            if (!S.chunked) {
                 // one chunk: its sum added to a total that starts at +0.0f, divided, stored by the segment's first lane
                 if (r.k == 0 && r.t < (uint32_t)n_texels) {
                     float *row = reinterpret_cast<float *>(out + r.t);
@@ -144,7 +129,7 @@ __global__ __launch_bounds__(64) void direct_query_kernel(const KParams K, const
                 total = total + mine; // chunk sums in chunk order, from +0.0f
             }
         }
-        if (chunked && lane < 8) // the texel's 32-byte row (the group is the texel); reserved is 0.0f
+        if (S.chunked && lane < 8) // the texel's 32-byte row (the group is the texel); reserved is 0.0f
             reinterpret_cast<float *>(out + g)[lane] = lane < 3 ? total / f_shadow : lane < 5 ? total / f_terms : 0.0f;
     }
     cyc.flush(lane);

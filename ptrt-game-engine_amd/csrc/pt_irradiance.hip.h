@@ -10,17 +10,15 @@
 // square, and the fraction of rays that hit: one 32-byte IrradianceOut per texel.
 //
 // The frame is probe_query_kernel's: a persistent grid of one-wave workgroups, the LDS carve and staging by PMODE, three waves
-// per SIMD, the parameters through the kernarg pointer.  Texels are many with few directions, so the grid strides over GROUPS
-// of texels: with w the smallest power of two >= n_dirs (64 beyond), a wave owns 64 / w consecutive texels, lane l being ray
-// l % w of texel slot l / w; beyond 64 directions a wave owns one texel and walks its ceil(n_dirs / 64) chunks.  Both shapes
-// are one loop around one call of the path loop, told apart by wave-uniform values.  After a chunk's paths have ended the six
-// terms are reduced within each segment of w lanes by the butterfly v[j] + v[j ^ w/2], .. ^ 1 -- float addition is commutative,
-// so every lane of a segment ends with the bits of the fold v[j] + v[j + w/2], then w/4, .. 1 (for w = 64 the probes' order).
+// per SIMD, the parameters through the kernarg pointer.  The work shape is the bakes' texel frame (pt_query.hip.h: texel_shape,
+// texel_ray, segment_fold_sum: groups of 64 / w texels, or one texel in chunks beyond 64 directions); the row store is the
+// kernel's own.  Both shapes are one loop around one call of the path loop, told apart by wave-uniform values.  After a chunk's
+// paths have ended the six terms are reduced within each segment of w lanes by segment_fold_sum (for w = 64 the probes' order).
 // Dead lanes -- k >= n_dirs, or a texel past the end -- take part in the collectives and contribute +0.0f.  Up to 64 directions
 // a segment's first lane adds the sum to +0.0f, divides by (float)n_dirs and stores the record; nothing but the lane's own ray
-// lives across the path loop -- its texel and direction numbers are formed again behind it (texel_ray).  Beyond, lane q adds the chunk's sum of quantity q to its running total, the one register kept
-// across the path loop, and lanes 0-7 divide and store at the end.  The sum order is part of the contract (include/ptrt.h,
-// tests/irradiance_restatement.py).
+// lives across the path loop -- its texel and direction numbers are formed again behind it (texel_ray).  Beyond, lane q adds
+// the chunk's sum of quantity q to its running total, the one register kept across the path loop, and lanes 0-7 divide and
+// store at the end.  The sum order is part of the contract (include/ptrt.h, tests/irradiance_restatement.py).
 #pragma once
 #include "pt_probe.hip.h"
 
@@ -54,26 +52,6 @@ PT_DEV void irradiance_ray(const float *__restrict__ positions, const float *__r
     o = mk3(P.x + offset * N.x, P.y + offset * N.y, P.z + offset * N.z);
 }
 
-// Lane l of group g in chunk c: ray k of texel t.  The lane number goes through an empty asm, so that each use computes the
-// pair afresh instead of holding it in registers.
-struct TexelRay {
-    uint32_t t, k;
-};
-PT_DEV TexelRay texel_ray(int lane, int log2w, uint32_t g, int c) {
-    int me = lane;
-    asm volatile("" : "+v"(me));
-    return TexelRay{(g << (6 - log2w)) + (uint32_t)(me >> log2w), (uint32_t)c * 64u + (uint32_t)(me & ((1 << log2w) - 1))};
-}
-
-// v[j] + v[j ^ w/2], then ^ w/4, .. ^ 1 within segments of w lanes (w a power of two, wave-uniform), in every lane
-PT_DEV float segment_fold_sum(float v, int w) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        if (off < w) // (wave-uniform)
-            v = v + __shfl_xor(v, off);
-    return v;
-}
-
 template <int GEOM, bool FULL, int PMODE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAVES, 8))) void irradiance_query_kernel(
     const KParams Kin, const float *__restrict__ positions, const float *__restrict__ normals, int n_texels,
@@ -84,23 +62,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
     const KParams &K = kparams(kp0); // staging
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
+    // (query_stage's text, pt_query.hip.h, and not a call of it: behind the call this kernel's allocation moved and the Cornell
+    // bake was 0.6 to 1.0 % slower in every run; with the text here all twelve variants are the ISA they were -- DESIGN 3.33)
     LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
     PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
     PL.cyc = &cyc;
     PL.stat_bounce = 0;
     __syncthreads();
-    // the work shape (wave-uniform): segments of w lanes, 64 / w texels per group, `chunks` chunks of 64 k beyond 64 directions.
-    // Texel and group numbers fit 32 bits (n_texels + 63 < 2^32); the state index does not.
-    int log2w = 0;
-    while (log2w < 6 && (1 << log2w) < n_dirs)
-        ++log2w;
-    const bool chunked = n_dirs > 64;
-    const int chunks = chunked ? (int)(((uint32_t)n_dirs + 63u) / 64u) : 1;
-    const uint32_t groups = ((uint32_t)n_texels + (64u >> log2w) - 1u) >> (6 - log2w);
-    for (uint32_t g = blockIdx.x; g < groups; g += gridDim.x) { // (wave-uniform)
+    const TexelShape S = texel_shape(n_texels, n_dirs); // (the state index does not fit 32 bits; texel and group numbers do)
+    const int log2w = S.log2w;
+    for (uint32_t g = blockIdx.x; g < S.groups; g += gridDim.x) { // (wave-uniform)
         float total = 0.0f; // beyond 64 directions, lane q: the running total of quantity q
-        for (int c = 0; c < chunks; ++c) { // (wave-uniform)
+        for (int c = 0; c < S.chunks; ++c) { // (wave-uniform)
             f3 o0 = mk3(0.0f), d0 = mk3(0.0f);
             Rng rng = {0, 0, 0, 0, 0, 0};
             bool live;
@@ -135,7 +109,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
             const float s_dist = segment_fold_sum(live ? dist : 0.0f, w);
             const float s_dist2 = segment_fold_sum(live ? dist * dist : 0.0f, w);
             const float s_hit = segment_fold_sum(live && object_id >= 0 ? 1.0f : 0.0f, w);
-            if (!chunked) {
+            if (!S.chunked) {
                 // one chunk: its sum added to a total that starts at +0.0f, divided, stored by the segment's first lane
                 if (r.k == 0 && r.t < (uint32_t)n_texels) {
                     const float fn = (float)nd;
@@ -161,7 +135,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
                 total = total + mine; // chunk sums in chunk order, from +0.0f
             }
         }
-        if (chunked) { // the texel's 32-byte row (the group is the texel); reserved is 0.0f
+        if (S.chunked) { // the texel's 32-byte row (the group is the texel); reserved is 0.0f
             int me = lane, nd = n_dirs;
             asm volatile("" : "+v"(me), "+s"(nd));
             if (me < 8)

@@ -1,8 +1,8 @@
 // pt_lightmap.hip.h -- the consumer of a lightmap bake: the baked atlas read back at ray hits.  lightmap_sample is the one
 // definition (include/ptrt.h has it in full); atlas_sample_kernel applies it to ptrt_hit records that lie in device memory
-// (ptrt_atlas_sample), lightmap_query_kernel to the hits of its own traversal (ptrt_query_lightmap) -- the loop of
-// ray_query_kernel<GEOM, PMODE, QUERY_CLOSEST> with the 32-byte sample in place of the 64-byte hit record, so by construction
-// the second equals the first over ptrt_query_rays' records.
+// (ptrt_atlas_sample), lightmap_query_kernel to the hits of its own traversal (ptrt_query_lightmap) -- closest_chunk_loop
+// (pt_query.hip.h), the one loop ray_query_kernel<GEOM, PMODE, QUERY_CLOSEST> is, with the 32-byte sample for a sink in place
+// of the 64-byte hit record, so by construction the second equals the first over ptrt_query_rays' records.
 //
 // The definition in fp32, -ffp-contract=off (every operation rounds on its own), `/` the compiler's IEEE quotient.  For a hit
 // on face f of mesh m at barycentrics (u, v) -- u belongs to corner v1, v to v2, as tri_test has them and as atlas_raster_kernel
@@ -127,45 +127,31 @@ __global__ __launch_bounds__(256) void atlas_sample_kernel(const float4 *__restr
     out[i * 2 + 1] = o1;
 }
 
-// ptrt_query_lightmap: ray_query_kernel's CLOSEST loop -- the persistent grid of one-wave workgroups, the LDS carve and staging
-// by PMODE, the four closest-hit walks, winner_uv for the pair walks -- and, where that kernel forms the 64-byte HitOut, the
-// face of the winning slot, its u and v, and the sample.  The hit point, the normal and the local point are not formed.
+// ptrt_query_lightmap: closest_chunk_loop (pt_query.hip.h) -- the persistent grid of one-wave workgroups, the LDS carve and
+// staging by PMODE, the closest-hit walk, winner_uv for the pair walks -- with, where ray_query_kernel forms the 64-byte HitOut,
+// the face of the winning slot, its u and v, and the sample.  The hit point, the normal and the local point are not formed.
+struct HitToLightmapSample {
+    const KParams &K;
+    const LightmapParams &L;
+    float4 *out;
+    PT_DEV void operator()(size_t i, const Hit &h, f3, f3) const {
+        const bool hit = h.mesh >= 0;
+        float4 o0, o1;
+        lightmap_sample(L, hit, h.mesh, hit ? K.slot_face[h.slot].w : -1, hit ? h.u : 0.0f, hit ? h.v : 0.0f, o0, o1);
+        out[i * 2 + 0] = o0;
+        out[i * 2 + 1] = o1;
+    }
+};
 template <int GEOM, int PMODE>
 __global__ __launch_bounds__(64) void lightmap_query_kernel(const KParams K, const float *__restrict__ origins,
                                                             const float *__restrict__ dirs, size_t n, const LightmapParams L,
                                                             float4 *__restrict__ out) {
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
+    const LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
-    PL.cyc = &cyc;
-    PL.stat_bounce = 0;
-    __syncthreads();
-    const size_t chunks = (n + 63) / 64;
-    for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (wave-uniform)
-        const size_t i = ch * 64 + (size_t)lane;
-        const bool live = i < n;
-        f3 o = mk3(0.0f), d = mk3(0.0f);
-        if (live) {
-            o = mk3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]);
-            d = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
-        }
-        int order;
-        Hit h = (PMODE == 1)   ? closest_hit_pairs(K, PL, lane, live, o, d, order)
-                : (PMODE == 2) ? closest_hit_pairs_dyn(K, PL, lane, live, o, d)
-                : (PMODE == 3) ? closest_hit_pairs_tlas(K, PL, lane, live, o, d, cyc)
-                               : closest_hit<GEOM>(K, live, o, d, stk);
-        if (live) {
-            if (PMODE)
-                winner_uv(K, h, o, d);
-            const bool hit = h.mesh >= 0;
-            float4 o0, o1;
-            lightmap_sample(L, hit, h.mesh, hit ? K.slot_face[h.slot].w : -1, hit ? h.u : 0.0f, hit ? h.v : 0.0f, o0, o1);
-            out[i * 2 + 0] = o0;
-            out[i * 2 + 1] = o1;
-        }
-    }
+    const PairLds PL = query_stage<PMODE>(K, lds_raw, lane, cyc);
+    closest_chunk_loop<GEOM, PMODE>(K, PL, stk, cyc, lane, origins, dirs, n, HitToLightmapSample{K, L, out});
 }
 
 } // namespace pt

@@ -1,4 +1,5 @@
-// pt_path.hip.h -- one vertex of tracePath (path_logic.cuh:782-899), stated once for the loops that are not tuned by their ISA:
+// pt_path.hip.h -- the primary ray and what starts and ends a pixel (scene_kernels.cuh:147-193), then one vertex of tracePath
+// (path_logic.cuh:782-899), stated once for the loops that are not tuned by their ISA:
 // wf_shade_path (pt_wavefront.hip.h), path_trace_async_kernel (pt_async.hip.h) and trace_chunk_samples (pt_radiance.hip.h: the
 // radiance and probe queries).  path_trace_kernel (pt_render.hip.h, phases [C]-[E]) keeps its own text of the same statement:
 // its instantiations are measured, and calling these helpers there moved their registers and scratch.
@@ -13,6 +14,107 @@
 #include "pt_kernels.hip.h"
 
 namespace pt {
+
+// ---- what starts and ends a pixel: phase [A] and the frame's per-pixel planes, stated once for wf_shade_path, the asynchronous
+// lanes and camera_rays_kernel (pt_radiance.hip.h).  path_trace_kernel's [A] keeps its own text of the same statement, as its
+// [C]-[E] do.  tests/frame_truth.py pins every expression.
+
+// Position l of the 8x8 tile `tile` (tiles_x tiles per row): the pixel's column and its row within the context's rows.  A tile
+// on the frame's edge has positions outside it.
+PT_DEV void tile_pixel(const int tiles_x, const int tile, const int l, int &x, int &yl) {
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    x = tx * 8 + (l & 7);
+    yl = ty * 8 + (l >> 3);
+}
+
+// Where pixel (x, y) of sample `frame` = frame_count + s looks through the image plane (scene_kernels.cuh:147-163): the TAA
+// entry, the blue-noise entry, their sum, u and v.
+PT_DEV void pixel_uv(const KParams &K, const int x, const int y, const int frame, float &u, float &v) {
+    float tjx, tjy, bnx, bny;
+    taa_jitter(frame, tjx, tjy);
+    blue_noise_jitter(K.blue_noise, x, y, frame, bnx, bny);
+    const float jitter_x = tjx + (bnx - 0.5f) * 0.25f;
+    const float jitter_y = tjy + (bny - 0.5f) * 0.25f;
+    u = ((float)x + 0.5f + jitter_x) / (float)K.width;
+    v = 1.0f - ((float)y + 0.5f + jitter_y) / (float)K.height;
+}
+
+// Camera::get_ray with a generator (camera.cuh:156-166).  The pinhole (get_ray_simple, camera.cuh:201-205), and the thin lens
+// (camera.cuh:160-165): a point of the unit disk by rejection, two draws per turn, `a` before `b`.
+PT_DEV void pinhole_ray(const Camera &cam, const float u, const float v, f3 &ro, f3 &rd) {
+    const f3 dir = cam.llc + u * cam.horizontal + v * cam.vertical - cam.origin;
+    ro = cam.origin;
+    rd = normalize(dir);
+}
+PT_DEV void camera_ray(const Camera &cam, const float u, const float v, Rng &rng, f3 &ro, f3 &rd) {
+    if (cam.lens_radius <= 0) {
+        pinhole_ray(cam, u, v, ro, rd);
+    } else {
+        f3 p;
+        do {
+            const float a = rng_uniform(rng);
+            const float b = rng_uniform(rng);
+            p = 2.0f * mk3(a, b, 0.0f) - mk3(1.0f, 1.0f, 0.0f);
+        } while (dot(p, p) >= 1.0f);
+        const f3 rdisk = cam.lens_radius * p;
+        const f3 offset = cam.u * rdisk.x + cam.v * rdisk.y;
+        const f3 dir = cam.llc + u * cam.horizontal + v * cam.vertical - cam.origin - offset;
+        ro = cam.origin + offset;
+        rd = normalize(dir);
+    }
+}
+
+// A generator state in memory, six words in the canonical order {d, v0..v4}.  A ray's state in a caller's array (the queries):
+// the words side by side.  A pixel's in the frame's six planes (K.rng, K.rng_plane words each): word k at idx + k * plane.
+PT_DEV void load_rng_state(Rng &rng, const uint32_t *st) {
+    rng.d = st[0];
+    rng.v0 = st[1];
+    rng.v1 = st[2];
+    rng.v2 = st[3];
+    rng.v3 = st[4];
+    rng.v4 = st[5];
+}
+PT_DEV void store_rng_state(uint32_t *st, const Rng &rng) {
+    st[0] = rng.d;
+    st[1] = rng.v0;
+    st[2] = rng.v1;
+    st[3] = rng.v2;
+    st[4] = rng.v3;
+    st[5] = rng.v4;
+}
+PT_DEV void load_rng_planes(Rng &rng, const uint32_t *planes, const size_t plane, const size_t idx) {
+    rng.d = planes[idx];
+    rng.v0 = planes[plane + idx];
+    rng.v1 = planes[2 * plane + idx];
+    rng.v2 = planes[3 * plane + idx];
+    rng.v3 = planes[4 * plane + idx];
+    rng.v4 = planes[5 * plane + idx];
+}
+PT_DEV void store_rng_planes(uint32_t *planes, const size_t plane, const size_t idx, const Rng &rng) {
+    planes[idx] = rng.d;
+    planes[plane + idx] = rng.v0;
+    planes[2 * plane + idx] = rng.v1;
+    planes[3 * plane + idx] = rng.v2;
+    planes[4 * plane + idx] = rng.v3;
+    planes[5 * plane + idx] = rng.v4;
+}
+
+// Where the first hit of a pixel's sample 0 goes in a frame: NORMAL / DEPTH / OBJECT_ID at the pixel (scene_kernels.cuh:
+// 179-193).  A miss stores the HitInfo() defaults: first(1e30f, mk3(0.0f), -1).  (The queries' sinks: FirstHitToRecord,
+// pt_radiance.hip.h; FirstHitToRegs, pt_probe.hip.h.)
+struct FirstHitToFrame {
+    const KParams &K;
+    size_t idx;
+    PT_DEV void operator()(float depth, f3 normal, int object_id) const {
+        K.normal[idx * 3 + 0] = normal.x;
+        K.normal[idx * 3 + 1] = normal.y;
+        K.normal[idx * 3 + 2] = normal.z;
+        K.depth[idx] = depth;
+        K.object_id[idx] = object_id;
+    }
+};
+
+// ---- the vertex
 
 // sampleSky (render_utils.cuh:115-137): the equirect map, or the gradient.  For a scene that has a sky (K.use_sky).
 PT_DEV f3 sample_sky(const KParams &K, const f3 rd) {

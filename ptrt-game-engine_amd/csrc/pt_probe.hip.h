@@ -9,9 +9,10 @@
 // The frame is radiance_query_kernel's: a persistent grid of one-wave workgroups, the LDS carve and staging by PMODE, three
 // waves per SIMD, the parameters through the kernarg pointer.  The grid strides over PROBES: a wave owns a probe and walks its
 // ceil(n_dirs / 64) chunks of 64 consecutive k in order.  After a chunk's paths have ended each lane holds its ray's mean
-// radiance; the 30 terms are formed one at a time, each reduced over the wave by the butterfly v[j] + v[j ^ 32], ^ 16, .. ^ 1
-// -- float addition is commutative, so every lane ends with the bits of the fold v[j] + v[j + 32], then 16, 8, 4, 2, 1 -- and
-// lane q adds the chunk's sum of quantity q to its running total, the one register the projection keeps across the path loop.
+// radiance; the 30 terms are formed one at a time, each reduced over the wave by segment_fold_sum at w = 64 (pt_query.hip.h),
+// the butterfly v[j] + v[j ^ 32], ^ 16, .. ^ 1 -- float addition is commutative, so every lane ends with the bits of the
+// fold v[j] + v[j + 32], then 16, 8, 4, 2, 1 -- and lane q adds the chunk's sum of quantity q to its running total,
+// the one register the projection keeps across the path loop.
 // Dead lanes of the tail chunk take part in the collectives and contribute +0.0f.  At the end lanes 0-31 divide by
 // (float)n_dirs and store the probe's row.  The sum order is part of the contract (include/ptrt.h, tests/probe_restatement.py).
 #pragma once
@@ -34,17 +35,6 @@ struct FirstHitToRegs {
         *object_id = id;
     }
 };
-
-// v[j] + v[j + 32], then + 16, 8, 4, 2, 1, in every lane
-PT_DEV float wave_fold_sum(float v) {
-    v = v + __shfl_xor(v, 32);
-    v = v + __shfl_xor(v, 16);
-    v = v + __shfl_xor(v, 8);
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 2);
-    v = v + __shfl_xor(v, 1);
-    return v;
-}
 
 // Y_i of the direction as given (not normalised), in the operation order include/ptrt.h states
 PT_DEV float sh9_basis(int i, f3 d) {
@@ -70,12 +60,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
     const KParams &K = kparams(kp0); // staging
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
+    const LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
-    PL.cyc = &cyc;
-    PL.stat_bounce = 0;
-    __syncthreads();
+    const PairLds PL = query_stage<PMODE>(K, lds_raw, lane, cyc);
     for (int p = blockIdx.x; p < n_probes; p += gridDim.x) { // (wave-uniform)
         const f3 o0 = mk3(positions[(size_t)p * 3], positions[(size_t)p * 3 + 1], positions[(size_t)p * 3 + 2]);
         float total = 0.0f; // lane q: the running total of quantity q
@@ -109,18 +96,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
 #pragma unroll
             for (int b = 0; b < 9; ++b) {
                 const float y = sh9_basis(b, d0);
-                const float sx = wave_fold_sum(live ? y * mean.x : 0.0f);
+                const float sx = segment_fold_sum(live ? y * mean.x : 0.0f, 64);
                 mine = me == 3 * b ? sx : mine;
-                const float sy = wave_fold_sum(live ? y * mean.y : 0.0f);
+                const float sy = segment_fold_sum(live ? y * mean.y : 0.0f, 64);
                 mine = me == 3 * b + 1 ? sy : mine;
-                const float sz = wave_fold_sum(live ? y * mean.z : 0.0f);
+                const float sz = segment_fold_sum(live ? y * mean.z : 0.0f, 64);
                 mine = me == 3 * b + 2 ? sz : mine;
             }
-            const float s_dist = wave_fold_sum(live ? dist : 0.0f);
+            const float s_dist = segment_fold_sum(live ? dist : 0.0f, 64);
             mine = me == 27 ? s_dist : mine;
-            const float s_dist2 = wave_fold_sum(live ? dist * dist : 0.0f);
+            const float s_dist2 = segment_fold_sum(live ? dist * dist : 0.0f, 64);
             mine = me == 28 ? s_dist2 : mine;
-            const float s_hit = wave_fold_sum(live && object_id >= 0 ? 1.0f : 0.0f);
+            const float s_hit = segment_fold_sum(live && object_id >= 0 ? 1.0f : 0.0f, 64);
             mine = me == 29 ? s_hit : mine;
             total = total + mine; // chunk sums in chunk order, from +0.0f
         }

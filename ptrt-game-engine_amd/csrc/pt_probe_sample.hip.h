@@ -1,10 +1,10 @@
 // pt_probe_sample.hip.h -- the consumer of a probe bake: a regular grid of ptrt_probe records (ptrt_query_probes' output, laid
 // out as ptrt_amd.probes.probe_grid orders them) read back at surface points.  probe_light is the one definition (include/ptrt.h
 // has it in full); probe_sample_kernel applies it to points and normals that lie in device memory (ptrt_probe_sample),
-// probe_light_query_kernel to the hits of its own traversal (ptrt_query_probe_light) -- the loop of
-// ray_query_kernel<GEOM, PMODE, QUERY_CLOSEST> with hit_record's point and normal put through probe_light and the 32-byte
-// ProbeLight written in place of the 64-byte hit record, so by construction the second equals the first over ptrt_query_rays'
-// records.
+// probe_light_query_kernel to the hits of its own traversal (ptrt_query_probe_light) -- closest_chunk_loop
+// (pt_query.hip.h), the one loop ray_query_kernel<GEOM, PMODE, QUERY_CLOSEST> is, with hit_record's point and normal put
+// through probe_light and the 32-byte ProbeLight for a sink in place of the 64-byte hit record, so by construction the second
+// equals the first over ptrt_query_rays' records.
 //
 // The definition in fp32, -ffp-contract=off (every operation rounds on its own), `/` and sqrt the compiler's IEEE ones.  For a
 // point P with normal N (used as given), the hit's face f and mesh m:
@@ -189,48 +189,34 @@ __global__ __launch_bounds__(256) void probe_sample_kernel(const float *__restri
     out[i * 2 + 1] = o1;
 }
 
-// ptrt_query_probe_light: ray_query_kernel's CLOSEST loop -- the persistent grid of one-wave workgroups, the LDS carve and
-// staging by PMODE, the four closest-hit walks, winner_uv for the pair walks -- then hit_record, of which the point, the
-// face-forwarded normal, the face and the mesh are kept, and probe_light.
+// ptrt_query_probe_light: closest_chunk_loop (pt_query.hip.h) -- the persistent grid of one-wave workgroups, the LDS carve and
+// staging by PMODE, the closest-hit walk, winner_uv for the pair walks -- with hit_record, of which the point, the face-forwarded
+// normal, the face and the mesh are kept, and probe_light for a sink.
+struct HitToProbeLight {
+    const KParams &K;
+    const ProbeVolumeParams &V;
+    float4 *out;
+    PT_DEV void operator()(size_t i, const Hit &h, f3 o, f3 d) const {
+        const HitOut r = hit_record(K, h, o, d);
+        float4 o0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float4 o1 = make_float4(__int_as_float(-1), __int_as_float(0), __int_as_float(-1), __int_as_float(-1));
+        if (r.hit)
+            probe_light(V, mk3(r.point[0], r.point[1], r.point[2]), mk3(r.normal[0], r.normal[1], r.normal[2]), r.face_index,
+                        r.mesh_index, o0, o1);
+        out[i * 2 + 0] = o0;
+        out[i * 2 + 1] = o1;
+    }
+};
 template <int GEOM, int PMODE>
 __global__ __launch_bounds__(64) void probe_light_query_kernel(const KParams K, const float *__restrict__ origins,
                                                                const float *__restrict__ dirs, size_t n, const ProbeVolumeParams V,
                                                                float4 *__restrict__ out) {
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
+    const LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
-    PL.cyc = &cyc;
-    PL.stat_bounce = 0;
-    __syncthreads();
-    const size_t chunks = (n + 63) / 64;
-    for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (wave-uniform)
-        const size_t i = ch * 64 + (size_t)lane;
-        const bool live = i < n;
-        f3 o = mk3(0.0f), d = mk3(0.0f);
-        if (live) {
-            o = mk3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]);
-            d = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
-        }
-        int order;
-        Hit h = (PMODE == 1)   ? closest_hit_pairs(K, PL, lane, live, o, d, order)
-                : (PMODE == 2) ? closest_hit_pairs_dyn(K, PL, lane, live, o, d)
-                : (PMODE == 3) ? closest_hit_pairs_tlas(K, PL, lane, live, o, d, cyc)
-                               : closest_hit<GEOM>(K, live, o, d, stk);
-        if (live) {
-            if (PMODE)
-                winner_uv(K, h, o, d);
-            const HitOut r = hit_record(K, h, o, d);
-            float4 o0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            float4 o1 = make_float4(__int_as_float(-1), __int_as_float(0), __int_as_float(-1), __int_as_float(-1));
-            if (r.hit)
-                probe_light(V, mk3(r.point[0], r.point[1], r.point[2]), mk3(r.normal[0], r.normal[1], r.normal[2]), r.face_index,
-                            r.mesh_index, o0, o1);
-            out[i * 2 + 0] = o0;
-            out[i * 2 + 1] = o1;
-        }
-    }
+    const PairLds PL = query_stage<PMODE>(K, lds_raw, lane, cyc);
+    closest_chunk_loop<GEOM, PMODE>(K, PL, stk, cyc, lane, origins, dirs, n, HitToProbeLight{K, V, out});
 }
 
 } // namespace pt

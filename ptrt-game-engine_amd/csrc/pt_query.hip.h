@@ -1,4 +1,5 @@
-// pt_query.hip.h -- ray_query_kernel: batched ray queries straight from device memory (ptrt_query_rays).
+// pt_query.hip.h -- ray_query_kernel: batched ray queries straight from device memory (ptrt_query_rays), and the frame that
+// every device query shares with it: the prologue, the walks by PMODE, the chunk loop, the bakes' texel frame.
 //
 // Two questions, asked of the scene the next frame traces:
 //   CLOSEST   traceRay (intersection.cuh:526-605) + the HitInfo fields of traceSingleRay (scene.cuh:1367-1391): one HitOut
@@ -73,50 +74,149 @@ PT_DEV void winner_uv(const KParams &K, Hit &h, f3 o, f3 d) {
     tri_test(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), r, T_FAR, t, h.u, h.v);
 }
 
+// ---- the frame every device query shares: inlined plain functions, so each kernel keeps its own allocation.
+
+// The wave's prologue: the LDS carve and staging by PMODE, the stats build's hooks, the workgroup's one barrier.  A kernel holds
+// `lane`, `stk` = {lds_raw + lane}, `cyc` and, behind this, a const PairLds.
+template <int PMODE> PT_DEV PairLds query_stage(const KParams &K, uint2 *lds_raw, const int lane, CycleAcc &cyc) {
+    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
+    PL.cyc = &cyc;
+    PL.stat_bounce = 0;
+    __syncthreads();
+    return PL;
+}
+
+// The closest hit and the any hit of the wave's 64 rays by PMODE; a lane that is not `alive` takes part in the collectives and
+// hands the traversal whatever ray it holds (the callers: zeros).  Phases [B] and [D] of path_trace_kernel keep their own text.
+template <int GEOM, int PMODE>
+PT_DEV Hit walk_closest(const KParams &K, const PairLds &PL, const LdsStack stk, CycleAcc &cyc, const int lane, const bool alive,
+                        const f3 o, const f3 d) {
+    int order = 0; // (PMODE 1: the hit mesh's place in the leaf, which no query reads)
+    return (PMODE == 1)   ? closest_hit_pairs(K, PL, lane, alive, o, d, order)
+           : (PMODE == 2) ? closest_hit_pairs_dyn(K, PL, lane, alive, o, d)
+           : (PMODE == 3) ? closest_hit_pairs_tlas(K, PL, lane, alive, o, d, cyc)
+                          : closest_hit<GEOM>(K, alive, o, d, stk);
+}
+template <int GEOM, int PMODE>
+PT_DEV bool walk_occluded(const KParams &K, const PairLds &PL, const LdsStack stk, CycleAcc &cyc, const int lane, const bool alive,
+                          const f3 o, const f3 d, const float tmax) {
+    return (PMODE == 1)   ? any_hit_pairs(K, PL, lane, alive, o, d, tmax)
+           : (PMODE == 2) ? any_hit_pairs_dyn(K, PL, lane, alive, o, d, tmax)
+           : (PMODE == 3) ? any_hit_pairs_tlas(K, PL, lane, alive, o, d, tmax, cyc)
+                          : any_hit<GEOM>(K, alive, o, d, tmax, stk);
+}
+
+// Ray i of the caller's arrays for a chunk lane; a dead lane (i >= n) gets zeros.  (A loop that reads another word per ray -- the
+// OCCLUDED loop its limit, radiance_query_kernel its generator state -- reads it in the same block as the ray and keeps that
+// text: read behind this function it is a second round trip to memory per chunk, 3 to 6 % of the Cornell box's occlusion rate.)
+struct ChunkRay {
+    f3 o, d;
+};
+PT_DEV ChunkRay chunk_ray(const float *origins, const float *dirs, const size_t i, const bool live) {
+    f3 o = mk3(0.0f), d = mk3(0.0f);
+    if (live) {
+        o = mk3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]);
+        d = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
+    }
+    return ChunkRay{o, d};
+}
+
+// The closest-hit loop: the grid strides over chunks of 64 rays; per chunk one walk, the winner's u and v behind a pair walk
+// (winner_uv), and sink(i, h, o, d) for every live lane.  ray_query_kernel<.., QUERY_CLOSEST>, lightmap_query_kernel
+// (pt_lightmap.hip.h) and probe_light_query_kernel (pt_probe_sample.hip.h) are this loop with three sinks, so the latter two
+// equal their samplers over ptrt_query_rays' records by construction.
+template <int GEOM, int PMODE, class Sink>
+PT_DEV void closest_chunk_loop(const KParams &K, const PairLds &PL, const LdsStack stk, CycleAcc &cyc, const int lane,
+                               const float *origins, const float *dirs, const size_t n, const Sink sink) {
+    const size_t chunks = (n + 63) / 64;
+    for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (wave-uniform)
+        const size_t i = ch * 64 + (size_t)lane;
+        const bool live = i < n;
+        const ChunkRay r = chunk_ray(origins, dirs, i, live);
+        const f3 o = r.o, d = r.d;
+        Hit h = walk_closest<GEOM, PMODE>(K, PL, stk, cyc, lane, live, o, d);
+        if (live) {
+            if (PMODE)
+                winner_uv(K, h, o, d);
+            sink(i, h, o, d);
+        }
+    }
+}
+struct HitToRecord { // the 64-byte HitOut of ptrt_query_rays
+    const KParams &K;
+    HitOut *out;
+    PT_DEV void operator()(size_t i, const Hit &h, f3 o, f3 d) const { out[i] = hit_record(K, h, o, d); }
+};
+
 template <int GEOM, int PMODE, int KIND>
 __global__ __launch_bounds__(64) void ray_query_kernel(const KParams K, const float *__restrict__ origins,
                                                        const float *__restrict__ dirs, const float *__restrict__ tmax,
                                                        size_t n, void *__restrict__ out) {
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
+    const LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
-    PL.cyc = &cyc;
-    PL.stat_bounce = 0;
-    __syncthreads();
+    const PairLds PL = query_stage<PMODE>(K, lds_raw, lane, cyc);
+    if (KIND == QUERY_CLOSEST) {
+        closest_chunk_loop<GEOM, PMODE>(K, PL, stk, cyc, lane, origins, dirs, n, HitToRecord{K, (HitOut *)out});
+        return;
+    }
     const size_t chunks = (n + 63) / 64;
     for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (wave-uniform)
         const size_t i = ch * 64 + (size_t)lane;
         const bool live = i < n;
         f3 o = mk3(0.0f), d = mk3(0.0f);
         float tm = 0.0f;
-        if (live) {
+        if (live) { // (the ray and its limit in one block: chunk_ray's comment)
             o = mk3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]);
             d = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
-            if (KIND == QUERY_OCCLUDED)
-                tm = tmax[i];
+            tm = tmax[i];
         }
-        if (KIND == QUERY_CLOSEST) {
-            int order;
-            Hit h = (PMODE == 1)   ? closest_hit_pairs(K, PL, lane, live, o, d, order)
-                    : (PMODE == 2) ? closest_hit_pairs_dyn(K, PL, lane, live, o, d)
-                    : (PMODE == 3) ? closest_hit_pairs_tlas(K, PL, lane, live, o, d, cyc)
-                                   : closest_hit<GEOM>(K, live, o, d, stk);
-            if (live) {
-                if (PMODE)
-                    winner_uv(K, h, o, d);
-                ((HitOut *)out)[i] = hit_record(K, h, o, d);
-            }
-        } else {
-            const bool blocked = (PMODE == 1)   ? any_hit_pairs(K, PL, lane, live, o, d, tm)
-                                 : (PMODE == 2) ? any_hit_pairs_dyn(K, PL, lane, live, o, d, tm)
-                                 : (PMODE == 3) ? any_hit_pairs_tlas(K, PL, lane, live, o, d, tm, cyc)
-                                                : any_hit<GEOM>(K, live, o, d, tm, stk);
-            if (live)
-                ((int *)out)[i] = blocked ? 1 : 0;
-        }
+        const bool blocked = walk_occluded<GEOM, PMODE>(K, PL, stk, cyc, lane, live, o, d, tm);
+        if (live)
+            ((int *)out)[i] = blocked ? 1 : 0;
     }
+}
+
+// ---- the texel frame of the bakes (irradiance_query_kernel, direct_query_kernel, bounce_query_kernel): texels are many with
+// few terms each, so the grid strides over GROUPS of texels.  With w = 1 << log2w the smallest power of two >= n_per (64
+// beyond), a wave owns 64 / w consecutive texels, lane l being term l % w of texel slot l / w; beyond 64 terms a wave owns one
+// texel and walks its ceil(n_per / 64) chunks.  Texel and group numbers fit 32 bits (n_texels + 63 < 2^32).  (wave-uniform)
+struct TexelShape {
+    int log2w, chunks;
+    bool chunked;
+    uint32_t groups;
+};
+PT_DEV TexelShape texel_shape(const int n_texels, const int n_per) {
+    TexelShape S;
+    S.log2w = 0;
+    while (S.log2w < 6 && (1 << S.log2w) < n_per)
+        ++S.log2w;
+    S.chunked = n_per > 64;
+    S.chunks = S.chunked ? (int)(((uint32_t)n_per + 63u) / 64u) : 1;
+    S.groups = ((uint32_t)n_texels + (64u >> S.log2w) - 1u) >> (6 - S.log2w);
+    return S;
+}
+
+// Lane l of group g in chunk c: term k of texel t.  The lane number goes through an empty asm, so that each use computes the
+// pair afresh instead of holding it in registers.
+struct TexelRay {
+    uint32_t t, k;
+};
+PT_DEV TexelRay texel_ray(int lane, int log2w, uint32_t g, int c) {
+    int me = lane;
+    asm volatile("" : "+v"(me));
+    return TexelRay{(g << (6 - log2w)) + (uint32_t)(me >> log2w), (uint32_t)c * 64u + (uint32_t)(me & ((1 << log2w) - 1))};
+}
+
+// v[j] + v[j ^ w/2], then ^ w/4, .. ^ 1 within segments of w lanes (w a power of two, wave-uniform), in every lane.  At w = 64
+// it is the probes' fold over the wave: v[j] + v[j + 32], then + 16, 8, 4, 2, 1.
+PT_DEV float segment_fold_sum(float v, int w) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        if (off < w) // (wave-uniform)
+            v = v + __shfl_xor(v, off);
+    return v;
 }
 
 } // namespace pt

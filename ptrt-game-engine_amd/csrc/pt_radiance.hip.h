@@ -9,12 +9,13 @@
 // query fed a pinhole frame's own primary rays and generator states reproduces that frame bit for bit, states included
 // (tests/test_radiance_query_gpu.py).
 //
-// The frame is ray_query_kernel's (pt_query.hip.h): a persistent grid of one-wave workgroups, a grid-stride loop over chunks of
-// 64 rays, dead lanes of the tail chunk taking part in the wave's collectives, size_t indices, the same LDS carve and staging,
-// the same traversal by PMODE.  Per chunk the 64 lanes run the path loop in lock step -- closest hit, the vertex of tracePath
-// through the functions of pt_path.hip.h in the phases [C], [C2], [D], [E] of path_trace_kernel, the light sample's shadow ray
-// between its value and its addition, the scatter -- until no lane has a path left, then the next sample.  No lane refill, no
-// staged shading inputs, no counters: a lane whose path has ended idles until the chunk's longest path is done.
+// The frame is the queries' one (pt_query.hip.h: query_stage, walk_closest, walk_occluded): a persistent grid of one-wave
+// workgroups, a grid-stride loop over chunks of 64 rays, dead lanes of the tail chunk taking part in the wave's collectives,
+// size_t indices, the LDS carve and staging and the traversal by PMODE.  Per chunk the 64 lanes run the path loop in lock
+// step -- closest hit, the vertex of tracePath through the functions of pt_path.hip.h in the phases [C], [C2], [D], [E] of
+// path_trace_kernel, the light sample's shadow ray between its value and its addition, the scatter -- until no lane has a path
+// left, then the next sample.  No lane refill, no staged shading inputs, no counters: a lane whose path has ended idles until
+// the chunk's longest path is done.
 #pragma once
 #include "pt_path.hip.h"
 #include "pt_query.hip.h"
@@ -61,6 +62,9 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
         while (__builtin_amdgcn_ballot_w64(act)) {
             // ---- [B] closest hit, all lanes that have a path together
             const KParams &KB = kparams(kp0);
+            // (walk_closest's text, pt_query.hip.h, and not a call of it: one more level of inlining around the closest-hit walk
+            // schedules the pair walk's stack push differently, and the PMODE 2 radiance and probe queries were 0.8 to 1.5 %
+            // slower in every run -- DESIGN 3.33; a change there is a change here)
             int h_order = 0;
             const Hit h = (PMODE == 1)   ? closest_hit_pairs(KB, PL, lane, act, ro, rd, h_order)
                           : (PMODE == 2) ? closest_hit_pairs_dyn(KB, PL, lane, act, ro, rd)
@@ -110,10 +114,7 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
             // visibility is known and before anything else touches the path's radiance
             const KParams &KD = kparams(kp0);
             if (__builtin_amdgcn_ballot_w64(lit)) {
-                const bool in_shadow = (PMODE == 1)   ? any_hit_pairs(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
-                                       : (PMODE == 2) ? any_hit_pairs_dyn(KD, PL, lane, lit, shadow_o, L, shadow_tmax)
-                                       : (PMODE == 3) ? any_hit_pairs_tlas(KD, PL, lane, lit, shadow_o, L, shadow_tmax, cyc)
-                                                      : any_hit<GEOM>(KD, lit, shadow_o, L, shadow_tmax, stk);
+                const bool in_shadow = walk_occluded<GEOM, PMODE>(KD, PL, stk, cyc, lane, lit, shadow_o, L, shadow_tmax);
                 if (lit && !in_shadow)
                     acc = acc + lit_now;
             }
@@ -134,24 +135,8 @@ PT_DEV f3 trace_chunk_samples(const kparams_ptr kp0, const PairLds &PL, const Ld
     return sum;
 }
 
-// A ray's generator state in the caller's array: six words in the canonical order {d, v0..v4}, read before the ray's paths
-// and written back advanced behind them (radiance_query_kernel, probe_query_kernel).
-PT_DEV void load_rng_state(Rng &rng, const uint32_t *st) {
-    rng.d = st[0];
-    rng.v0 = st[1];
-    rng.v1 = st[2];
-    rng.v2 = st[3];
-    rng.v3 = st[4];
-    rng.v4 = st[5];
-}
-PT_DEV void store_rng_state(uint32_t *st, const Rng &rng) {
-    st[0] = rng.d;
-    st[1] = rng.v0;
-    st[2] = rng.v1;
-    st[3] = rng.v2;
-    st[4] = rng.v3;
-    st[5] = rng.v4;
-}
+// (A ray's generator state in the caller's array is read before the ray's paths and written back advanced behind them:
+// load_rng_state / store_rng_state, pt_path.hip.h.)
 
 // Waves per SIMD the kernel is built for (its register budget: 512 / waves, in steps of 8): the most at which the pair variants
 // keep a lane's whole path state -- ray, throughput, radiance, sum, generator, hit and light sample across the shadow walk -- in
@@ -170,19 +155,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
     const KParams &K = kparams(kp0); // staging
     extern __shared__ uint2 lds_raw[];
     const int lane = threadIdx.x;
-    LdsStack stk{lds_raw + lane};
+    const LdsStack stk{lds_raw + lane};
     CycleAcc cyc;
-    PairLds PL = stage_pair_lds<PMODE>(K, lds_raw, lane);
-    PL.cyc = &cyc;
-    PL.stat_bounce = 0;
-    __syncthreads();
+    const PairLds PL = query_stage<PMODE>(K, lds_raw, lane, cyc);
     const size_t chunks = (n + 63) / 64;
     for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (wave-uniform)
         const size_t i = ch * 64 + (size_t)lane;
         const bool live = i < n;
         f3 o0 = mk3(0.0f), d0 = mk3(0.0f);
         Rng rng = {0, 0, 0, 0, 0, 0};
-        if (live) {
+        if (live) { // (the ray and its generator state in one block: chunk_ray's comment, pt_query.hip.h)
             o0 = mk3(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]);
             d0 = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
             load_rng_state(rng, rng_states + i * 6);
@@ -202,7 +184,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RADIANCE_WAV
 }
 
 // The primary rays ptrt_render(frame, ..) gives sample `sample` of every pixel of the context's rows, pinhole camera: phase [A]
-// of path_trace_kernel (scene_kernels.cuh:147-167, camera.cuh:156-158) through the same device functions, one thread per pixel,
+// (scene_kernels.cuh:147-167, get_ray_simple) as pt_path.hip.h states it -- pixel_uv, pinhole_ray --, one thread per pixel,
 // ray yl * width + x.  K.frame_count = frame + sample.
 __global__ __launch_bounds__(256) void camera_rays_kernel(const KParams K, float *__restrict__ origins, float *__restrict__ dirs) {
     const size_t npix = (size_t)K.rows * K.width;
@@ -211,16 +193,10 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const KParams K, float
         return;
     const int yl = (int)(i / (size_t)K.width), x = (int)(i % (size_t)K.width);
     const int y = global_row(yl, K.y0, K.il_period, K.il_phase);
-    float tjx, tjy, bnx, bny;
-    taa_jitter(K.frame_count, tjx, tjy);
-    blue_noise_jitter(K.blue_noise, x, y, K.frame_count, bnx, bny);
-    const float jitter_x = tjx + (bnx - 0.5f) * 0.25f;
-    const float jitter_y = tjy + (bny - 0.5f) * 0.25f;
-    const float u = ((float)x + 0.5f + jitter_x) / (float)K.width;
-    const float v = 1.0f - ((float)y + 0.5f + jitter_y) / (float)K.height;
-    const f3 dir = K.cam.llc + u * K.cam.horizontal + v * K.cam.vertical - K.cam.origin;
-    const f3 ro = K.cam.origin;
-    const f3 rd = normalize(dir);
+    float u, v;
+    pixel_uv(K, x, y, K.frame_count, u, v);
+    f3 ro, rd;
+    pinhole_ray(K.cam, u, v, ro, rd);
     origins[i * 3 + 0] = ro.x;
     origins[i * 3 + 1] = ro.y;
     origins[i * 3 + 2] = ro.z;

@@ -2227,7 +2227,9 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         PT_MARK("A");
         const KParams &KA = kparams(kp0);
         const unsigned long long t_pa = TS_NOW();
-        // ---- [A] primary ray (scene_kernels.cuh:147-167, camera.cuh:156-205)
+        // ---- [A] primary ray (scene_kernels.cuh:147-167, camera.cuh:156-205).  pt_path.hip.h states it once -- pixel_uv,
+        // camera_ray -- for the other loops: a change here is a change there.  This kernel keeps its text: its staged inputs come
+        // from LDS, and calling camera_ray behind u, v moved all 19 instantiations and gave one 16 bytes of scratch.
         // K.sample_sync: a lane whose path has ended starts its next sample only when NO lane of the wave is in the middle of one.
         // The lanes then sit at the same bounce: a first hit samples no light (ray_spec), so the light-sample phases [C2] and
         // [D] are skipped by the whole wave in that iteration instead of running for the half of the lanes that are deeper,
@@ -2294,7 +2296,9 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         PT_MARK("B");
         phase_prio<PMODE, 1, 0>();
         const KParams &KB = kparams(kp0);
-        // ---- [B] closest hit, all live lanes together (PMODE 4: and the parked shadow rays in the same traversal)
+        // ---- [B] closest hit, all live lanes together (PMODE 4: and the parked shadow rays in the same traversal).  (The walk by
+        // PMODE is walk_closest of pt_query.hip.h for every other loop; this one keeps its text: PMODE 1 walks dense, <true>,
+        // and keeps h_order.)
         Hit h;
         int h_order = 0; // PMODE 1: the hit mesh's place in the leaf (what the staged tables are indexed by); from the end of [C]
                          // with the hit's record in tri_frames above H_ORDER_BITS
@@ -2520,7 +2524,8 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(waves_p
         phase_prio<PMODE, 4, 3>();
         const KParams &KD = kparams(kp0);
         // ---- [D] shadow rays, all lanes that have one together (bvh_any_hit_tlas); PMODE 4 parks them instead and
-        // walks them with the next extension rays
+        // walks them with the next extension rays.  (The any-hit walk by PMODE is walk_occluded of pt_query.hip.h for every
+        // other loop; this one keeps its text and its dense PMODE 1 walk.)
         const unsigned long long t_sh = TS_NOW();
         if (MERGED) {
             if (lit) {

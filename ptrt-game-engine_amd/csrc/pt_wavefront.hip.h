@@ -275,10 +275,8 @@ template <bool FULL> PT_DEV void wf_shade_path(const KParams &K, const WfParams 
     uint32_t &n_ext = cn.n_ext, &n_shadow = cn.n_shadow, &n_paths = cn.n_paths, &n_zero = cn.n_zero;
     bool &alive_after = cn.alive_after;
     if (q < W.n_items) {
-        const int tile = q >> 6, l = q & 63;
-        const int tx = tile % K.tiles_x, ty = tile / K.tiles_x;
-        const int x = tx * 8 + (l & 7);
-        const int yl = ty * 8 + (l >> 3);
+        int x, yl;
+        tile_pixel(K.tiles_x, q >> 6, q & 63, x, yl);
         const bool inside = (x < K.width) && (yl < K.rows);
         const int y = global_row(yl, K.y0, K.il_period, K.il_phase);
         const size_t npix = K.rng_plane;
@@ -290,12 +288,7 @@ template <bool FULL> PT_DEV void wf_shade_path(const KParams &K, const WfParams 
             int s = (int)(st & 0xffu), bounce = (int)((st >> 8) & 0xffu);
             bool ray_spec = (st & WF_SPEC) != 0u, prev_was_specular = (st & WF_PREV_SPEC) != 0u;
             Rng rng;
-            rng.d = K.rng[idx];
-            rng.v0 = K.rng[npix + idx];
-            rng.v1 = K.rng[2 * npix + idx];
-            rng.v2 = K.rng[3 * npix + idx];
-            rng.v3 = K.rng[4 * npix + idx];
-            rng.v4 = K.rng[5 * npix + idx];
+            load_rng_planes(rng, K.rng, npix, idx);
             f3 throughput = mk3(1.0f), acc = mk3(0.0f);
             f3 ro = mk3(0.0f), rd = mk3(0.0f);
             bool regen = first;
@@ -321,24 +314,14 @@ template <bool FULL> PT_DEV void wf_shade_path(const KParams &K, const WfParams 
                     ++n_ext;
                     bool end_path = false, want_shadow = false;
                     if (h.mesh < 0) {
-                        if (bounce == 0 && s == 0) {
-                            K.normal[idx * 3 + 0] = 0.0f;
-                            K.normal[idx * 3 + 1] = 0.0f;
-                            K.normal[idx * 3 + 2] = 0.0f;
-                            K.depth[idx] = 1e30f;
-                            K.object_id[idx] = -1;
-                        }
+                        if (bounce == 0 && s == 0) // HitInfo() defaults
+                            FirstHitToFrame{K, idx}(1e30f, mk3(0.0f), -1);
                         add_miss_radiance(K, rd, throughput, acc);
                         end_path = true;
                     } else {
                         const Surface hit = make_surface(K, h, ro, rd, nullptr, nullptr);
-                        if (bounce == 0 && s == 0) {
-                            K.normal[idx * 3 + 0] = hit.normal.x;
-                            K.normal[idx * 3 + 1] = hit.normal.y;
-                            K.normal[idx * 3 + 2] = hit.normal.z;
-                            K.depth[idx] = hit.t;
-                            K.object_id[idx] = h.mesh;
-                        }
+                        if (bounce == 0 && s == 0)
+                            FirstHitToFrame{K, idx}(hit.t, hit.normal, h.mesh);
                         const float4 m0 = K.materials[h.mesh * 6 + 0], m2 = K.materials[h.mesh * 6 + 2];
                         absorb_and_emit(m0, m2, hit, bounce == 0 || prev_was_specular, throughput, acc);
                         const Material mat = load_material(K.materials, h.mesh);
@@ -395,31 +378,10 @@ template <bool FULL> PT_DEV void wf_shade_path(const KParams &K, const WfParams 
                 }
                 if (s >= K.spp) {
                     done = true;
-                } else { // primary ray (scene_kernels.cuh:147-167, camera.cuh:156-205)
-                    float tjx, tjy, bnx, bny;
-                    taa_jitter(K.frame_count + s, tjx, tjy);
-                    blue_noise_jitter(K.blue_noise, x, y, K.frame_count + s, bnx, bny);
-                    const float jitter_x = tjx + (bnx - 0.5f) * 0.25f;
-                    const float jitter_y = tjy + (bny - 0.5f) * 0.25f;
-                    const float u = ((float)x + 0.5f + jitter_x) / (float)K.width;
-                    const float v = 1.0f - ((float)y + 0.5f + jitter_y) / (float)K.height;
-                    if (K.cam.lens_radius <= 0) {
-                        const f3 dir = K.cam.llc + u * K.cam.horizontal + v * K.cam.vertical - K.cam.origin;
-                        ro = K.cam.origin;
-                        rd = normalize(dir);
-                    } else {
-                        f3 p;
-                        do {
-                            const float a = rng_uniform(rng);
-                            const float b = rng_uniform(rng);
-                            p = 2.0f * mk3(a, b, 0.0f) - mk3(1.0f, 1.0f, 0.0f);
-                        } while (dot(p, p) >= 1.0f);
-                        const f3 rdisk = K.cam.lens_radius * p;
-                        const f3 offset = K.cam.u * rdisk.x + K.cam.v * rdisk.y;
-                        const f3 dir = K.cam.llc + u * K.cam.horizontal + v * K.cam.vertical - K.cam.origin - offset;
-                        ro = K.cam.origin + offset;
-                        rd = normalize(dir);
-                    }
+                } else { // primary ray (scene_kernels.cuh:147-167, camera.cuh:156-205): pt_path.hip.h
+                    float u, v;
+                    pixel_uv(K, x, y, K.frame_count + s, u, v);
+                    camera_ray(K.cam, u, v, rng, ro, rd);
                     ray_spec = true;
                     prev_was_specular = true;
                     throughput = mk3(1.0f);
@@ -428,12 +390,7 @@ template <bool FULL> PT_DEV void wf_shade_path(const KParams &K, const WfParams 
                     flags |= WF_EXT;
                 }
             }
-            K.rng[idx] = rng.d;
-            K.rng[npix + idx] = rng.v0;
-            K.rng[2 * npix + idx] = rng.v1;
-            K.rng[3 * npix + idx] = rng.v2;
-            K.rng[4 * npix + idx] = rng.v3;
-            K.rng[5 * npix + idx] = rng.v4;
+            store_rng_planes(K.rng, npix, idx, rng);
             if (done) {
                 n_paths += (uint32_t)K.spp;
                 const f3 out = mk3(W.avg[q], W.avg[N + q], W.avg[2 * N + q]) / (float)K.spp;

@@ -44,6 +44,24 @@ def test_showcase_all_material_branches(P, O, blue_noise, fetch_min, wf_sort):
     s.close()
 
 
+@pytest.mark.parametrize("full", [0, 1], ids=["force_full=0", "force_full=1"])
+@pytest.mark.parametrize("wf_sort", [2, 4])
+def test_wider_sorting_groups(P, O, blue_noise, wf_sort, full):
+    """wf_sort = 2 and 4 -- the shade stage with two and four paths per thread, which no other test renders -- with the simple
+    and with the full material model, on a ragged frame (tiles on the frame's edge have positions outside it) through a thin
+    lens, so that the regenerate step draws its lens sample from the pixel's generator."""
+    s = P.Scene(61, 45)
+    P.scenes.cornell(s)
+    s.setCamera((0, 0, 5), (0, 0, -5), (0, 1, 0), 40.0, 0.1, 10.0)
+    s.set_option("wavefront", 1)
+    s.set_option("wf_sort", wf_sort)
+    s.set_option("force_full", full)
+    gpu, cpu = render_both(P, O, s, blue_noise, 2, 3, 2)
+    assert mode(P, s) == 1 and s.get_option("wf_sort") == wf_sort and s.get_option("force_full") == full
+    assert_frames_equal(gpu, cpu)
+    s.close()
+
+
 def test_instanced_meshes_and_thin_lens(P, O, blue_noise):
     """has_transform instances (local-space rays, t rescaling) and a lens that draws random numbers in
     the regenerate step."""
