@@ -187,7 +187,7 @@ struct TexelShape {
     bool chunked;
     uint32_t groups;
 };
-PT_DEV TexelShape texel_shape(const int n_texels, const int n_per) {
+__host__ PT_DEV TexelShape texel_shape(const int n_texels, const int n_per) {
     TexelShape S;
     S.log2w = 0;
     while (S.log2w < 6 && (1 << S.log2w) < n_per)

@@ -6,9 +6,10 @@
 // (ptrt_atlas_sample; ptrt_query_lightmap, which traces the rays itself), a probe volume read at surface points (ptrt_probe_sample;
 // ptrt_query_probe_light, which traces the rays itself) and the two kernels that let a caller start where a frame starts (ptrt_camera_rays,
 // ptrt_init_rng_states).  What the traversing queries share is decided once each: the traversal
-// (plan_query), the kernel variant of it (with_variant), the persistent grid (launch_persistent), the refusals (check_spans,
-// check_shading_query).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom, pair_mode, trace_lds_bytes,
-// refresh_tlas_heads) and the helpers every entry point shares.
+// (plan_query), the kernel variant of it (with_variant, with_full), the persistent grid (launch_persistent) and the texel bakes'
+// units of it (texel_groups), the refusals (check_spans, spans_apart, check_out_apart, check_shading_query); the calls without
+// a traversal launch one thread per item (launch_per_item).  Included by ptrt_capi.hip behind ptrt_render.hip.h (pick_geom,
+// pair_mode, trace_lds_bytes, refresh_tlas_heads) and the helpers every entry point shares.
 #pragma once
 
 #include <initializer_list>
@@ -64,6 +65,10 @@ template <class F> int with_variant(int geom, int pmode, F &&f) {
     }
 }
 
+// f(FULL) with the material model as a compile-time constant (std::true_type / std::false_type): QueryPlan::full, or the
+// context's own where a call has no plan.
+template <class F> int with_full(bool full, F &&f) { return full ? f(std::true_type{}) : f(std::false_type{}); }
+
 // A persistent grid of one-wave workgroups: about one per wave slot of the chip, and no more than there are `units` of work for
 // the grid-stride loop (chunks of 64 rays, probes, or groups of texels). `honour_persist`: option "persist" (persistent waves per CU) overrides
 // the occupancy the runtime reports -- the shading queries, not the ray queries (include/ptrt.h).
@@ -80,16 +85,43 @@ int launch_persistent(ptrt_ctx *c, Kernel kernel, size_t lds, size_t units, bool
     return PTRT_OK;
 }
 
+// One thread per item in blocks of 256, on the context's stream; the callers keep `items` at or below INT_MAX * 256, the grid's
+// x extent being an int.  A path frame that follows is ordered behind it: `touched`.
+template <class Kernel, class... Args> int launch_per_item(ptrt_ctx *c, Kernel kernel, size_t items, const Args &...args) {
+    c->touched = true;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, c->stream, args...);
+    HIP_TRY(c, hipGetLastError());
+    return PTRT_OK;
+}
+
+// The persistent grid of the texel bakes: groups of 64 / w texels, w the smallest power of two >= the `per_texel` rays or terms
+// of one; beyond 64 of them, one wave per texel.  The kernels' own statement of it (texel_shape, pt_query.hip.h).
+size_t texel_groups(int n_texels, int per_texel) { return pt::texel_shape(n_texels, per_texel).groups; }
+
 // Every span is `bytes` of device memory on the context's device (device_span), or the first that is not is refused by name.
+// `optional`: a span whose pointer may be NULL, and is skipped then.
 struct Span {
     const char *name;
     const void *p;
     size_t bytes;
+    bool optional = false;
 };
 int check_spans(ptrt_ctx *c, const char *fn, std::initializer_list<Span> spans) {
     for (const Span &s : spans)
-        if (!device_span(c, s.p, s.bytes))
+        if (!(s.optional && !s.p) && !device_span(c, s.p, s.bytes))
             return fail(c, PTRT_E_INVALID, "%s: %s is not %zu bytes of device memory on device %d", fn, s.name, s.bytes, c->device);
+    return PTRT_OK;
+}
+
+// Whether two spans share no byte, and `out` against every span of `spans` in turn: the first it overlaps is refused by name.
+bool spans_apart(const Span &a, const Span &b) {
+    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+    return x < y ? y - x >= a.bytes : x - y >= b.bytes;
+}
+int check_out_apart(ptrt_ctx *c, const char *fn, const Span &out, std::initializer_list<Span> spans) {
+    for (const Span &s : spans)
+        if (!spans_apart(out, s))
+            return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, out.p, out.bytes, s.name, s.p, s.bytes);
     return PTRT_OK;
 }
 
@@ -168,9 +200,9 @@ int ptrt_query_rays(ptrt_ctx *c, int kind, const float *origins, const float *di
     if (int rc = set_device(c))
         return rc;
     const size_t rays = (size_t)n;
-    const Span so{"origins", origins, rays * 12}, sd{"directions", directions, rays * 12}, st{"tmax", tmax, rays * sizeof(float)},
-        sout{"out", out, rays * (kind == PTRT_QUERY_CLOSEST ? sizeof(pt::HitOut) : sizeof(int32_t))};
-    if (int rc = tmax ? check_spans(c, "ptrt_query_rays", {so, sd, st, sout}) : check_spans(c, "ptrt_query_rays", {so, sd, sout}))
+    if (int rc = check_spans(c, "ptrt_query_rays",
+                             {{"origins", origins, rays * 12}, {"directions", directions, rays * 12}, {"tmax", tmax, rays * sizeof(float), true},
+                              {"out", out, rays * (kind == PTRT_QUERY_CLOSEST ? sizeof(pt::HitOut) : sizeof(int32_t))}}))
         return rc;
     return launch_ray_query(c, kind, origins, directions, tmax, rays, out);
 }
@@ -198,13 +230,12 @@ int ptrt_query_radiance(ptrt_ctx *c, const float *origins, const float *directio
         return rc;
     // radiance_query_kernel (pt_radiance.hip.h) over the n rays and their generator states
     pt::RadianceOut *o = reinterpret_cast<pt::RadianceOut *>(out);
-    auto launch = [&](auto FULL) {
+    return with_full(P.full, [&](auto FULL) {
         return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
             return launch_persistent(c, pt::radiance_query_kernel<G, FULL, PM>, P.lds, (rays + 63) / 64, true, P.K, origins, directions,
                                      rng_states, rays, o);
         });
-    };
-    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
 
 int ptrt_query_probes(ptrt_ctx *c, const float *d_positions, int n_probes, const float *d_directions, int n_dirs,
@@ -233,13 +264,12 @@ int ptrt_query_probes(ptrt_ctx *c, const float *d_positions, int n_probes, const
         return rc;
     // probe_query_kernel (pt_probe.hip.h): the grid strides over probes, one wave per probe
     pt::ProbeOut *o = reinterpret_cast<pt::ProbeOut *>(d_out);
-    auto launch = [&](auto FULL) {
+    return with_full(P.full, [&](auto FULL) {
         return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
             return launch_persistent(c, pt::probe_query_kernel<G, FULL, PM>, P.lds, probes, true, P.K, d_positions, n_probes, d_directions,
                                      n_dirs, d_rng_states, max_distance, o);
         });
-    };
-    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
 
 int ptrt_irradiance_rays(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
@@ -264,17 +294,14 @@ int ptrt_irradiance_rays(ptrt_ctx *c, const float *d_positions, const float *d_n
     if (rays > MAX_RAYS)
         return fail(c, PTRT_E_INVALID, "ptrt_irradiance_rays: %d texels x %d directions: more than %zu rays in one call", n_texels, n_dirs,
                     MAX_RAYS);
-    const Span sp{"positions", d_positions, texels * 12}, sn{"normals", d_normals, texels * 12}, ss{"samples2", d_samples2, ndirs * 8},
-        sph{"phases", d_phases, texels * sizeof(float)}, so{"origins", d_origins, rays * 12}, sd{"directions", d_directions, rays * 12};
-    if (int rc = d_phases ? check_spans(c, "ptrt_irradiance_rays", {sp, sn, ss, sph, so, sd})
-                          : check_spans(c, "ptrt_irradiance_rays", {sp, sn, ss, so, sd}))
+    if (int rc = check_spans(c, "ptrt_irradiance_rays",
+                             {{"positions", d_positions, texels * 12}, {"normals", d_normals, texels * 12}, {"samples2", d_samples2, ndirs * 8},
+                              {"phases", d_phases, texels * sizeof(float), true}, {"origins", d_origins, rays * 12},
+                              {"directions", d_directions, rays * 12}}))
         return rc;
-    c->touched = true;
     // irradiance_rays_kernel (pt_irradiance.hip.h): one thread per ray
-    hipLaunchKernelGGL(pt::irradiance_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, c->stream, d_positions, d_normals, rays,
-                       d_samples2, n_dirs, d_phases, offset, d_origins, d_directions);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
+    return launch_per_item(c, pt::irradiance_rays_kernel, rays, d_positions, d_normals, rays, d_samples2, n_dirs, d_phases, offset, d_origins,
+                           d_directions);
 }
 
 int ptrt_query_irradiance(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
@@ -300,29 +327,23 @@ int ptrt_query_irradiance(ptrt_ctx *c, const float *d_positions, const float *d_
     const size_t texels = (size_t)n_texels, ndirs = (size_t)n_dirs, rays = texels * ndirs;
     if (rays > SIZE_MAX / 24)
         return fail(c, PTRT_E_INVALID, "ptrt_query_irradiance: %d texels x %d directions: the states' byte count overflows", n_texels, n_dirs);
-    const Span sp{"positions", d_positions, texels * 12}, sn{"normals", d_normals, texels * 12}, ss{"samples2", d_samples2, ndirs * 8},
-        sph{"phases", d_phases, texels * sizeof(float)}, sst{"rng_states", d_rng_states, rays * 24},
-        sout{"out", d_out, texels * sizeof(ptrt_irradiance)};
-    if (int rc = d_phases ? check_spans(c, "ptrt_query_irradiance", {sp, sn, ss, sph, sst, sout})
-                          : check_spans(c, "ptrt_query_irradiance", {sp, sn, ss, sst, sout}))
+    if (int rc = check_spans(c, "ptrt_query_irradiance",
+                             {{"positions", d_positions, texels * 12}, {"normals", d_normals, texels * 12}, {"samples2", d_samples2, ndirs * 8},
+                              {"phases", d_phases, texels * sizeof(float), true}, {"rng_states", d_rng_states, rays * 24},
+                              {"out", d_out, texels * sizeof(ptrt_irradiance)}}))
         return rc;
     QueryPlan P;
     if (int rc = plan_query(c, true, samples, max_depth, P))
         return rc;
-    // irradiance_query_kernel (pt_irradiance.hip.h): the grid strides over groups of 64 / w texels, w the smallest power of two
-    // >= n_dirs; beyond 64 directions over texels, one wave per texel
-    int w = 1;
-    while (w < 64 && w < n_dirs)
-        w *= 2;
-    const size_t per_group = (size_t)(64 / w), groups = (texels + per_group - 1) / per_group;
+    // irradiance_query_kernel (pt_irradiance.hip.h): the grid strides over the texel groups of n_dirs rays a texel
+    const size_t groups = texel_groups(n_texels, n_dirs);
     pt::IrradianceOut *o = reinterpret_cast<pt::IrradianceOut *>(d_out);
-    auto launch = [&](auto FULL) {
+    return with_full(P.full, [&](auto FULL) {
         return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
             return launch_persistent(c, pt::irradiance_query_kernel<G, FULL, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels,
                                      d_samples2, n_dirs, d_phases, offset, d_rng_states, max_distance, o);
         });
-    };
-    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
 
 } // extern "C"
@@ -376,20 +397,15 @@ int ptrt_direct_rays(ptrt_ctx *c, const float *d_positions, const float *d_norma
         return PTRT_OK;
     if (int rc = set_device(c))
         return rc;
-    const Span sp{"positions", d_positions, S.texels * 12}, sn{"normals", d_normals, S.texels * 12},
-        ss{"samples2", d_samples2, (size_t)n_shadow * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
-        so{"origins", d_origins, S.rays * 12}, sd{"directions", d_directions, S.rays * 12}, st{"tmax", d_tmax, S.rays * sizeof(float)},
-        sw{"weights", d_weights, S.rays * 12};
-    if (int rc = d_phases ? check_spans(c, "ptrt_direct_rays", {sp, sn, ss, sph, so, sd, st, sw})
-                          : check_spans(c, "ptrt_direct_rays", {sp, sn, ss, so, sd, st, sw}))
+    if (int rc = check_spans(c, "ptrt_direct_rays",
+                             {{"positions", d_positions, S.texels * 12}, {"normals", d_normals, S.texels * 12},
+                              {"samples2", d_samples2, (size_t)n_shadow * 8}, {"phases", d_phases, S.texels * sizeof(float), true},
+                              {"origins", d_origins, S.rays * 12}, {"directions", d_directions, S.rays * 12},
+                              {"tmax", d_tmax, S.rays * sizeof(float)}, {"weights", d_weights, S.rays * 12}}))
         return rc;
-    c->touched = true;
     // direct_rays_kernel (pt_direct.hip.h): one thread per ray
-    hipLaunchKernelGGL(pt::direct_rays_kernel, dim3((unsigned)((S.rays + 255) / 256)), dim3(256), 0, c->stream, c->d_lights, d_positions,
-                       d_normals, S.rays, d_samples2, n_shadow, d_phases, offset, light_first, (int)S.terms, d_origins, d_directions,
-                       d_tmax, d_weights);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
+    return launch_per_item(c, pt::direct_rays_kernel, S.rays, c->d_lights, d_positions, d_normals, S.rays, d_samples2, n_shadow, d_phases,
+                           offset, light_first, (int)S.terms, d_origins, d_directions, d_tmax, d_weights);
 }
 
 int ptrt_query_direct(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_shadow,
@@ -408,10 +424,10 @@ int ptrt_query_direct(ptrt_ctx *c, const float *d_positions, const float *d_norm
         return PTRT_OK;
     if (int rc = set_device(c))
         return rc;
-    const Span sp{"positions", d_positions, S.texels * 12}, sn{"normals", d_normals, S.texels * 12},
-        ss{"samples2", d_samples2, (size_t)n_shadow * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
-        sout{"out", d_out, S.texels * sizeof(ptrt_direct)};
-    if (int rc = d_phases ? check_spans(c, "ptrt_query_direct", {sp, sn, ss, sph, sout}) : check_spans(c, "ptrt_query_direct", {sp, sn, ss, sout}))
+    if (int rc = check_spans(c, "ptrt_query_direct",
+                             {{"positions", d_positions, S.texels * 12}, {"normals", d_normals, S.texels * 12},
+                              {"samples2", d_samples2, (size_t)n_shadow * 8}, {"phases", d_phases, S.texels * sizeof(float), true},
+                              {"out", d_out, S.texels * sizeof(ptrt_direct)}}))
         return rc;
     if (S.terms == 0) { // no lights asked for: rows of zero bytes, in stream order
         c->touched = true;
@@ -421,12 +437,8 @@ int ptrt_query_direct(ptrt_ctx *c, const float *d_positions, const float *d_norm
     QueryPlan P;
     if (int rc = plan_query(c, false, 0, 0, P))
         return rc;
-    // direct_query_kernel (pt_direct.hip.h): the grid strides over groups of 64 / w texels, w the smallest power of two >= Q;
-    // beyond 64 terms over texels, one wave per texel
-    size_t w = 1;
-    while (w < 64 && w < S.terms)
-        w *= 2;
-    const size_t per_group = 64 / w, groups = (S.texels + per_group - 1) / per_group;
+    // direct_query_kernel (pt_direct.hip.h): the grid strides over the texel groups of Q terms a texel
+    const size_t groups = texel_groups(n_texels, (int)S.terms);
     pt::DirectOut *o = reinterpret_cast<pt::DirectOut *>(d_out);
     return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
         return launch_persistent(c, pt::direct_query_kernel<G, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels, d_samples2,
@@ -492,27 +504,18 @@ int ptrt_bounce_terms(ptrt_ctx *c, const ptrt_hit *d_hits, const float *d_direct
         return PTRT_OK;
     if (int rc = set_device(c))
         return rc;
-    const Span sh{"hits", d_hits, S.rays * sizeof(ptrt_hit)}, sd{"directions", d_directions, S.rays * 12},
-        ss{"shadow2", d_shadow2, (size_t)n_shadow * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
-        so{"origins", d_origins, S.rows * 12}, sl{"L", d_L, S.rows * 12}, st{"tmax", d_tmax, S.rows * sizeof(float)},
-        sv{"values", d_values, S.rows * 12};
-    if (int rc = d_phases ? check_spans(c, "ptrt_bounce_terms", {sh, sd, ss, sph, so, sl, st, sv})
-                          : check_spans(c, "ptrt_bounce_terms", {sh, sd, ss, so, sl, st, sv}))
+    if (int rc = check_spans(c, "ptrt_bounce_terms",
+                             {{"hits", d_hits, S.rays * sizeof(ptrt_hit)}, {"directions", d_directions, S.rays * 12},
+                              {"shadow2", d_shadow2, (size_t)n_shadow * 8}, {"phases", d_phases, S.texels * sizeof(float), true},
+                              {"origins", d_origins, S.rows * 12}, {"L", d_L, S.rows * 12}, {"tmax", d_tmax, S.rows * sizeof(float)},
+                              {"values", d_values, S.rows * 12}}))
         return rc;
-    c->touched = true;
     // bounce_terms_kernel (pt_bounce.hip.h): one thread per term, the material model a frame would use
     const pt::HitOut *h = reinterpret_cast<const pt::HitOut *>(d_hits);
-    const dim3 grid((unsigned)((S.rows + 255) / 256));
-    if (c->mats_full || c->force_full)
-        hipLaunchKernelGGL(pt::bounce_terms_kernel<true>, grid, dim3(256), 0, c->stream, c->d_lights, c->d_materials, c->n_materials, h,
-                           d_directions, S.rows, n_dirs, d_shadow2, n_shadow, d_phases, light_first, (int)S.terms, d_origins, d_L, d_tmax,
-                           d_values);
-    else
-        hipLaunchKernelGGL(pt::bounce_terms_kernel<false>, grid, dim3(256), 0, c->stream, c->d_lights, c->d_materials, c->n_materials, h,
-                           d_directions, S.rows, n_dirs, d_shadow2, n_shadow, d_phases, light_first, (int)S.terms, d_origins, d_L, d_tmax,
-                           d_values);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
+    return with_full(c->mats_full || c->force_full, [&](auto FULL) {
+        return launch_per_item(c, pt::bounce_terms_kernel<FULL>, S.rows, c->d_lights, c->d_materials, c->n_materials, h, d_directions, S.rows,
+                               n_dirs, d_shadow2, n_shadow, d_phases, light_first, (int)S.terms, d_origins, d_L, d_tmax, d_values);
+    });
 }
 
 int ptrt_query_bounce(ptrt_ctx *c, const float *d_positions, const float *d_normals, int n_texels, const float *d_samples2, int n_dirs,
@@ -535,11 +538,10 @@ int ptrt_query_bounce(ptrt_ctx *c, const float *d_positions, const float *d_norm
         return PTRT_OK;
     if (int rc = set_device(c))
         return rc;
-    const Span sp{"positions", d_positions, S.texels * 12}, sn{"normals", d_normals, S.texels * 12},
-        ss{"samples2", d_samples2, S.dirs * 8}, sph{"phases", d_phases, S.texels * sizeof(float)},
-        ssh{"shadow2", d_shadow2, (size_t)n_shadow * 8}, sout{"out", d_out, S.texels * sizeof(ptrt_bounce)};
-    if (int rc = d_phases ? check_spans(c, "ptrt_query_bounce", {sp, sn, ss, sph, ssh, sout})
-                          : check_spans(c, "ptrt_query_bounce", {sp, sn, ss, ssh, sout}))
+    if (int rc = check_spans(c, "ptrt_query_bounce",
+                             {{"positions", d_positions, S.texels * 12}, {"normals", d_normals, S.texels * 12},
+                              {"samples2", d_samples2, S.dirs * 8}, {"phases", d_phases, S.texels * sizeof(float), true},
+                              {"shadow2", d_shadow2, (size_t)n_shadow * 8}, {"out", d_out, S.texels * sizeof(ptrt_bounce)}}))
         return rc;
     if (S.terms == 0) { // no lights asked for: rows of zero bytes, in stream order
         c->touched = true;
@@ -549,20 +551,15 @@ int ptrt_query_bounce(ptrt_ctx *c, const float *d_positions, const float *d_norm
     QueryPlan P;
     if (int rc = plan_query(c, false, 0, 0, P))
         return rc;
-    // bounce_query_kernel (pt_bounce.hip.h): irradiance_query_kernel's grid -- groups of 64 / w texels, w the smallest power of
-    // two >= n_dirs; beyond 64 directions over texels, one wave per texel
-    size_t w = 1;
-    while (w < 64 && w < S.dirs)
-        w *= 2;
-    const size_t per_group = 64 / w, groups = (S.texels + per_group - 1) / per_group;
+    // bounce_query_kernel (pt_bounce.hip.h): irradiance_query_kernel's grid, the texel groups of n_dirs rays a texel
+    const size_t groups = texel_groups(n_texels, n_dirs);
     pt::BounceOut *o = reinterpret_cast<pt::BounceOut *>(d_out);
-    auto launch = [&](auto FULL) {
+    return with_full(P.full, [&](auto FULL) {
         return with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
             return launch_persistent(c, pt::bounce_query_kernel<G, FULL, PM>, P.lds, groups, true, P.K, d_positions, d_normals, n_texels,
                                      d_samples2, n_dirs, d_phases, offset, d_shadow2, n_shadow, light_first, (int)S.terms, o);
         });
-    };
-    return P.full ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
 
 } // extern "C"
@@ -608,14 +605,12 @@ int ptrt_atlas_texels(ptrt_ctx *c, int mesh_index, const float *d_uv, int atlas_
     const int faces = c->mesh_face_count[(size_t)mesh_index], slots = c->mesh_slot_count[(size_t)mesh_index];
     if (int rc = check_spans(c, "ptrt_atlas_texels", {{"uv", d_uv, (size_t)faces * 24}, {"texels", d_texels, texels * sizeof(ptrt_atlas_texel)}}))
         return rc;
-    c->touched = true;
     const int g = c->atlas_lanes > 0 ? c->atlas_lanes : atlas_auto_lanes((long long)texels, faces);
     const int log2g = g == 64 ? 6 : g == 16 ? 4 : g == 4 ? 2 : 0;
     c->atlas_lanes_eff = 1 << log2g;
     pt::AtlasTexel *t = reinterpret_cast<pt::AtlasTexel *>(d_texels);
-    hipLaunchKernelGGL(pt::atlas_prime_kernel, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, c->stream, t, (uint32_t)texels,
-                       clear ? 1 : 0);
-    HIP_TRY(c, hipGetLastError());
+    if (int rc = launch_per_item(c, pt::atlas_prime_kernel, texels, t, (uint32_t)texels, clear ? 1 : 0))
+        return rc;
     if (slots <= 0)
         return PTRT_OK;
     // atlas_raster_kernel (pt_atlas.hip.h) twice over units of 64 / g leaf slots: the minimum face per texel, then -- behind
@@ -637,22 +632,18 @@ int ptrt_atlas_dilate(ptrt_ctx *c, float *d_a, float *d_b, int atlas_w, int atla
         return fail(c, PTRT_E_INVALID, "ptrt_atlas_dilate: bad argument (a %p, b %p, atlas %d x %d: 1 x 1 .. 2^28 texels, passes %d: 1 .. 64)",
                     (const void *)d_a, (const void *)d_b, atlas_w, atlas_h, passes);
     const size_t bytes = (size_t)atlas_w * (size_t)atlas_h * 16;
-    const uintptr_t a = (uintptr_t)d_a, b = (uintptr_t)d_b;
-    if (!aligned16(d_a) || !aligned16(d_b) || (a < b ? b - a : a - b) < bytes)
+    if (!aligned16(d_a) || !aligned16(d_b) || !spans_apart({"a", d_a, bytes}, {"b", d_b, bytes}))
         return fail(c, PTRT_E_INVALID, "ptrt_atlas_dilate: a %p and b %p must be 16-byte aligned and %zu bytes apart", (const void *)d_a,
                     (const void *)d_b, bytes);
     if (int rc = set_device(c))
         return rc;
     if (int rc = check_spans(c, "ptrt_atlas_dilate", {{"a", d_a, bytes}, {"b", d_b, bytes}}))
         return rc;
-    c->touched = true;
     // atlas_dilate_kernel (pt_atlas.hip.h): a -> b -> a ..., one launch per pass
     float4 *buf[2] = {reinterpret_cast<float4 *>(d_a), reinterpret_cast<float4 *>(d_b)};
-    for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(pt::atlas_dilate_kernel, dim3((unsigned)((bytes / 16 + 255) / 256)), dim3(256), 0, c->stream,
-                           (const float4 *)buf[p & 1], buf[(p & 1) ^ 1], atlas_w, atlas_h);
-        HIP_TRY(c, hipGetLastError());
-    }
+    for (int p = 0; p < passes; ++p)
+        if (int rc = launch_per_item(c, pt::atlas_dilate_kernel, bytes / 16, (const float4 *)buf[p & 1], buf[(p & 1) ^ 1], atlas_w, atlas_h))
+            return rc;
     return PTRT_OK;
 }
 
@@ -697,17 +688,16 @@ int ptrt_atlas_filter(ptrt_ctx *c, const ptrt_atlas_texel *d_texels, float *d_a,
                     "step of %d passes",
                     (double)sigma_distance, (double)sigma_plane, passes);
     const size_t texels = (size_t)atlas_w * (size_t)atlas_h, bytes = texels * 16, guide_bytes = texels * sizeof(ptrt_atlas_texel);
-    const uintptr_t a = (uintptr_t)d_a, b = (uintptr_t)d_b, g = (uintptr_t)d_texels;
+    const Span sa{"a", d_a, bytes}, sb{"b", d_b, bytes}, sg{"texels", d_texels, guide_bytes};
     if (!aligned16(d_a) || !aligned16(d_b) || !aligned16(d_texels))
         return fail(c, PTRT_E_INVALID, "ptrt_atlas_filter: texels %p, a %p and b %p must be 16-byte aligned", (const void *)d_texels,
                     (const void *)d_a, (const void *)d_b);
-    auto apart = [](uintptr_t x, size_t nx, uintptr_t y, size_t ny) { return x < y ? y - x >= nx : x - y >= ny; };
-    if (!apart(a, bytes, b, bytes) || !apart(a, bytes, g, guide_bytes) || !apart(b, bytes, g, guide_bytes))
+    if (!spans_apart(sa, sb) || !spans_apart(sa, sg) || !spans_apart(sb, sg))
         return fail(c, PTRT_E_INVALID, "ptrt_atlas_filter: a %p and b %p (%zu bytes each) and texels %p (%zu bytes) must not overlap",
                     (const void *)d_a, (const void *)d_b, bytes, (const void *)d_texels, guide_bytes);
     if (int rc = set_device(c))
         return rc;
-    if (int rc = check_spans(c, "ptrt_atlas_filter", {{"texels", d_texels, guide_bytes}, {"a", d_a, bytes}, {"b", d_b, bytes}}))
+    if (int rc = check_spans(c, "ptrt_atlas_filter", {sg, sa, sb}))
         return rc;
     c->touched = true;
     // atlas_filter_kernel (pt_atlas_filter.hip.h): a -> b -> a ..., one launch per pass, step 1 << pass
@@ -776,27 +766,18 @@ int check_lightmap(ptrt_ctx *c, const char *fn, int n, const float *d_charts, in
         done = true;
         return PTRT_OK;
     }
-    const size_t out_bytes = (size_t)n * sizeof(ptrt_lightmap_sample);
-    const Span fixed[3] = {{"charts", d_charts, (size_t)n_chart_faces * 24},
-                           {"chart_first", d_chart_first, (size_t)c->n_meshes * sizeof(int32_t)},
-                           {"image", d_image, (size_t)atlas_w * (size_t)atlas_h * 16}};
-    const auto apart = [&](const Span &s) {
-        const uintptr_t x = (uintptr_t)d_out, y = (uintptr_t)s.p;
-        return x < y ? y - x >= out_bytes : x - y >= s.bytes;
-    };
-    for (const Span &s : fixed)
-        if (!apart(s))
-            return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, (const void *)d_out, out_bytes, s.name, s.p,
-                        s.bytes);
-    for (const Span &s : ins)
-        if (!apart(s))
-            return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, (const void *)d_out, out_bytes, s.name, s.p,
-                        s.bytes);
+    const Span charts{"charts", d_charts, (size_t)n_chart_faces * 24},
+        chart_first{"chart_first", d_chart_first, (size_t)c->n_meshes * sizeof(int32_t)},
+        image{"image", d_image, (size_t)atlas_w * (size_t)atlas_h * 16}, out{"out", d_out, (size_t)n * sizeof(ptrt_lightmap_sample)};
+    if (int rc = check_out_apart(c, fn, out, {charts, chart_first, image}))
+        return rc;
+    if (int rc = check_out_apart(c, fn, out, ins))
+        return rc;
     if (int rc = set_device(c))
         return rc;
     if (int rc = check_spans(c, fn, ins))
         return rc;
-    if (int rc = check_spans(c, fn, {fixed[0], fixed[1], fixed[2], {"out", d_out, out_bytes}}))
+    if (int rc = check_spans(c, fn, {charts, chart_first, image, out}))
         return rc;
     L.charts = d_charts;
     L.chart_first = d_chart_first;
@@ -824,12 +805,9 @@ int ptrt_atlas_sample(ptrt_ctx *c, const ptrt_hit *d_hits, int n, const float *d
         return rc;
     if (done)
         return PTRT_OK;
-    c->touched = true;
-    // atlas_sample_kernel (pt_lightmap.hip.h): one thread per record; n < 2^31, so the grid's x extent fits
-    hipLaunchKernelGGL(pt::atlas_sample_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream,
-                       reinterpret_cast<const float4 *>(d_hits), (size_t)n, L, reinterpret_cast<float4 *>(d_out));
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
+    // atlas_sample_kernel (pt_lightmap.hip.h): one thread per record
+    return launch_per_item(c, pt::atlas_sample_kernel, (size_t)n, reinterpret_cast<const float4 *>(d_hits), (size_t)n, L,
+                           reinterpret_cast<float4 *>(d_out));
 }
 
 int ptrt_query_lightmap(ptrt_ctx *c, const float *d_origins, const float *d_directions, int n, const float *d_charts, int n_chart_faces,
@@ -896,24 +874,16 @@ int check_probe_volume(ptrt_ctx *c, const char *fn, int n, const ptrt_probe_volu
         done = true;
         return PTRT_OK;
     }
-    const size_t out_bytes = (size_t)n * sizeof(ptrt_probe_light);
-    const Span probes{"probes", d_probes, (size_t)rows * sizeof(ptrt_probe)};
-    const auto apart = [&](const Span &s) {
-        const uintptr_t x = (uintptr_t)d_out, y = (uintptr_t)s.p;
-        return x < y ? y - x >= out_bytes : x - y >= s.bytes;
-    };
-    if (!apart(probes))
-        return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps probes %p (%zu bytes)", fn, (const void *)d_out, out_bytes, probes.p,
-                    probes.bytes);
-    for (const Span &s : ins)
-        if (!apart(s))
-            return fail(c, PTRT_E_INVALID, "%s: out %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, (const void *)d_out, out_bytes, s.name, s.p,
-                        s.bytes);
+    const Span probes{"probes", d_probes, (size_t)rows * sizeof(ptrt_probe)}, out{"out", d_out, (size_t)n * sizeof(ptrt_probe_light)};
+    if (int rc = check_out_apart(c, fn, out, {probes}))
+        return rc;
+    if (int rc = check_out_apart(c, fn, out, ins))
+        return rc;
     if (int rc = set_device(c))
         return rc;
     if (int rc = check_spans(c, fn, ins))
         return rc;
-    if (int rc = check_spans(c, fn, {probes, {"out", d_out, out_bytes}}))
+    if (int rc = check_spans(c, fn, {probes, out}))
         return rc;
     V.probes = reinterpret_cast<const float4 *>(d_probes);
     for (int a = 0; a < 3; ++a) {
@@ -942,12 +912,8 @@ int ptrt_probe_sample(ptrt_ctx *c, const float *d_positions, const float *d_norm
         return rc;
     if (done)
         return PTRT_OK;
-    c->touched = true;
-    // probe_sample_kernel (pt_probe_sample.hip.h): one thread per point; n < 2^31, so the grid's x extent fits
-    hipLaunchKernelGGL(pt::probe_sample_kernel, dim3((unsigned)((points + 255) / 256)), dim3(256), 0, c->stream, d_positions, d_normals,
-                       points, V, reinterpret_cast<float4 *>(d_out));
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
+    // probe_sample_kernel (pt_probe_sample.hip.h): one thread per point
+    return launch_per_item(c, pt::probe_sample_kernel, points, d_positions, d_normals, points, V, reinterpret_cast<float4 *>(d_out));
 }
 
 int ptrt_query_probe_light(ptrt_ctx *c, const float *d_origins, const float *d_directions, int n, const ptrt_probe_volume *volume,
@@ -990,10 +956,7 @@ int ptrt_camera_rays(ptrt_ctx *c, int frame_index, int sample, float *d_origins,
     const size_t rays = (size_t)K.rows * K.width;
     if (int rc = check_spans(c, "ptrt_camera_rays", {{"d_origins", d_origins, rays * 12}, {"d_directions", d_directions, rays * 12}}))
         return rc;
-    c->touched = true;
-    hipLaunchKernelGGL(pt::camera_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, c->stream, K, d_origins, d_directions);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
+    return launch_per_item(c, pt::camera_rays_kernel, rays, K, d_origins, d_directions);
 }
 
 int ptrt_init_rng_states(ptrt_ctx *c, unsigned long long seed, unsigned long long first_subsequence, int n, uint32_t *d_states) {
@@ -1013,11 +976,8 @@ int ptrt_init_rng_states(ptrt_ctx *c, unsigned long long seed, unsigned long lon
     if (int rc = ensure_jump(c, last, "ptrt_init_rng_states"))
         return rc;
     const XorwowSeed s = xorwow_seed(seed);
-    c->touched = true;
-    hipLaunchKernelGGL(pt::rng_states_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream, d_states, (size_t)n,
-                       first_subsequence, s.d, s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], c->d_jump, c->n_jump);
-    HIP_TRY(c, hipGetLastError());
-    return PTRT_OK;
+    return launch_per_item(c, pt::rng_states_kernel, (size_t)n, d_states, (size_t)n, first_subsequence, s.d, s.v[0], s.v[1], s.v[2], s.v[3],
+                           s.v[4], c->d_jump, c->n_jump);
 }
 
 } // extern "C"

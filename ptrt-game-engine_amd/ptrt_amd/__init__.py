@@ -472,10 +472,37 @@ def _is_tensor(a):
     return type(a).__module__.split(".")[0] == "torch"
 
 
+def _named_columns(records, columns, reinterpret=None):
+    """{name: view of its columns} for the (n, cols) rows of a query, a tensor or an array, by a `*_COLUMNS` table (name ->
+    (first, last + 1, ..)): one column as (n,), several as (n, k).  `reinterpret`: (the other 4-byte type's name, the names of
+    the columns that hold its bits), viewed as it."""
+    as_type, names = reinterpret or (None, ())
+    if names and _is_tensor(records):
+        import torch
+        as_type = getattr(torch, as_type)
+    out = {}
+    for name, (a, b, *_) in columns.items():
+        col = records[:, a:b]
+        if name in names:
+            col = col.view(as_type)
+        out[name] = col[:, 0] if b - a == 1 else col
+    return out
+
+
+def _flagged(columns, flag):
+    """the names of a (first, last + 1, is float) table whose third entry is `flag`"""
+    return {name for name, c in columns.items() if c[2] is flag}
+
+
 # columns of the (n, 16) int32 rows of Scene.query_closest on torch tensors: the fields of ptrt_hit / HIT_DTYPE
 HIT_COLUMNS = dict(hit=(0, 1, False), t=(1, 2, True), point=(2, 5, True), normal=(5, 8, True), mesh_index=(8, 9, False),
                    front_face=(9, 10, False), u=(10, 11, True), v=(11, 12, True), face_index=(12, 13, False),
                    local_point=(13, 16, True))
+
+
+def hit_fields(hits):
+    """Named views of query_closest's (n, 16) int32 tensor: float fields reinterpreted as float32, scalars as (n,)."""
+    return _named_columns(hits, HIT_COLUMNS, ("float32", _flagged(HIT_COLUMNS, True)))
 
 
 # columns of the (n, 8) float32 rows of Scene.query_radiance: the fields of ptrt_radiance / RADIANCE_DTYPE
@@ -484,13 +511,7 @@ RADIANCE_COLUMNS = dict(radiance=(0, 3, True), depth=(3, 4, True), normal=(4, 7,
 
 def radiance_fields(records):
     """Named views of query_radiance's (n, 8) float32 tensor: object_id reinterpreted as int32, scalars as (n,)."""
-    import torch
-    i = records.view(torch.int32)
-    out = {}
-    for name, (a, b, is_f) in RADIANCE_COLUMNS.items():
-        col = (records if is_f else i)[:, a:b]
-        out[name] = col[:, 0] if b - a == 1 else col
-    return out
+    return _named_columns(records, RADIANCE_COLUMNS, ("int32", _flagged(RADIANCE_COLUMNS, False)))
 
 
 # columns of the (n, 32) float32 rows of Scene.query_probes: the fields of ptrt_probe / PROBE_DTYPE
@@ -499,10 +520,8 @@ PROBE_COLUMNS = dict(sh=(0, 27), mean_distance=(27, 28), mean_distance_sq=(28, 2
 
 def probe_fields(probes):
     """Named views of query_probes's (n, 32) float32 tensor: sh as (n, 9, 3) -- coefficient, colour channel --, scalars as (n,)."""
-    out = {}
-    for name, (a, b) in PROBE_COLUMNS.items():
-        col = probes[:, a:b]
-        out[name] = col.reshape(-1, 9, 3) if name == "sh" else col[:, 0] if b - a == 1 else col
+    out = _named_columns(probes, PROBE_COLUMNS)
+    out["sh"] = out["sh"].reshape(-1, 9, 3)
     return out
 
 
@@ -512,11 +531,7 @@ IRRADIANCE_COLUMNS = dict(radiance=(0, 3), mean_distance=(3, 4), mean_distance_s
 
 def irradiance_fields(records):
     """Named views of query_irradiance's (n, 8) float32 rows (a tensor or an array): radiance as (n, 3), scalars as (n,)."""
-    out = {}
-    for name, (a, b) in IRRADIANCE_COLUMNS.items():
-        col = records[:, a:b]
-        out[name] = col[:, 0] if b - a == 1 else col
-    return out
+    return _named_columns(records, IRRADIANCE_COLUMNS)
 
 
 # columns of the (n, 8) float32 rows of Scene.query_direct: the fields of ptrt_direct / DIRECT_DTYPE
@@ -525,11 +540,7 @@ DIRECT_COLUMNS = dict(irradiance=(0, 3), lit_fraction=(3, 4), shadowed_fraction=
 
 def direct_fields(records):
     """Named views of query_direct's (n, 8) float32 rows (a tensor or an array): irradiance as (n, 3), scalars as (n,)."""
-    out = {}
-    for name, (a, b) in DIRECT_COLUMNS.items():
-        col = records[:, a:b]
-        out[name] = col[:, 0] if b - a == 1 else col
-    return out
+    return _named_columns(records, DIRECT_COLUMNS)
 
 
 # columns of the (n, 8) float32 rows of Scene.query_bounce: the fields of ptrt_bounce / BOUNCE_DTYPE
@@ -538,11 +549,7 @@ BOUNCE_COLUMNS = dict(radiance=(0, 3), lit_fraction=(3, 4), shadowed_fraction=(4
 
 def bounce_fields(records):
     """Named views of query_bounce's (n, 8) float32 rows (a tensor or an array): radiance as (n, 3), scalars as (n,)."""
-    out = {}
-    for name, (a, b) in BOUNCE_COLUMNS.items():
-        col = records[:, a:b]
-        out[name] = col[:, 0] if b - a == 1 else col
-    return out
+    return _named_columns(records, BOUNCE_COLUMNS)
 
 
 # columns of the (n, 8) int32 rows of Scene.atlas_texels: the fields of ptrt_atlas_texel / ATLAS_TEXEL_DTYPE
@@ -552,13 +559,7 @@ ATLAS_COLUMNS = dict(position=(0, 3), face=(3, 4), normal=(4, 7), mesh=(7, 8))
 def atlas_fields(records):
     """Named views of atlas_texels' (n, 8) int32 rows (a tensor or an array): position and normal reinterpreted as float32,
     (n, 3); face and mesh int32, (n,)."""
-    import torch
-    f32 = torch.float32 if _is_tensor(records) else np.float32
-    out = {}
-    for name, (a, b) in ATLAS_COLUMNS.items():
-        col = records[:, a:b]
-        out[name] = col[:, 0] if b - a == 1 else col.view(f32)
-    return out
+    return _named_columns(records, ATLAS_COLUMNS, ("float32", ("position", "normal")))
 
 
 # columns of the (n, 8) int32 rows of Scene.atlas_sample / query_lightmap: the fields of ptrt_lightmap_sample / LIGHTMAP_SAMPLE_DTYPE
@@ -569,26 +570,7 @@ LIGHTMAP_SAMPLE_COLUMNS = dict(rgb=(0, 3, True), weight=(3, 4, True), x=(4, 5, T
 def lightmap_sample_fields(records):
     """Named views of atlas_sample's and query_lightmap's (n, 8) int32 rows (a tensor or an array): rgb (n, 3), weight, x and y
     (n,) reinterpreted as float32; face and mesh int32, (n,)."""
-    import torch
-    f32 = torch.float32 if _is_tensor(records) else np.float32
-    out = {}
-    for name, (a, b, is_f) in LIGHTMAP_SAMPLE_COLUMNS.items():
-        col = records[:, a:b]
-        if is_f:
-            col = col.view(f32)
-        out[name] = col[:, 0] if b - a == 1 else col
-    return out
-
-
-def hit_fields(hits):
-    """Named views of query_closest's (n, 16) int32 tensor: float fields reinterpreted as float32, scalars as (n,)."""
-    import torch
-    f = hits.view(torch.float32)
-    out = {}
-    for name, (a, b, is_f) in HIT_COLUMNS.items():
-        col = (f if is_f else hits)[:, a:b]
-        out[name] = col[:, 0] if b - a == 1 else col
-    return out
+    return _named_columns(records, LIGHTMAP_SAMPLE_COLUMNS, ("float32", _flagged(LIGHTMAP_SAMPLE_COLUMNS, True)))
 
 
 class Scene:
@@ -1085,6 +1067,53 @@ class Scene:
         if not a.is_contiguous():
             raise ValueError(f"{what}: tensors must be contiguous")
 
+    def _out_rows(self, what, out, n, cols, dtype, device, rows_for):
+        """The answer's tensor: a new (n, cols) one of `dtype` on `device`, or the caller's `out`, checked.  `rows_for`: how the
+        refusal of another row count ends -- "out has .. rows for <rows_for>"."""
+        if out is None:
+            import torch
+            return torch.empty((n, cols), dtype=getattr(torch, dtype.split(".")[1]), device=device)
+        self._device_tensor(f"{what}: out", out, cols, dtype)
+        if out.shape[0] != n:
+            raise ValueError(f"{what}: out has {out.shape[0]} rows for {rows_for}")
+        return out
+
+    @staticmethod
+    def _ray_rows(rows, device):
+        """the (rows, 3), (rows, 3), (rows,), (rows, 3) float32 tensors direct_rays and bounce_terms answer with"""
+        import torch
+        return tuple(torch.empty(shape, dtype=torch.float32, device=device) for shape in ((rows, 3), (rows, 3), (rows,), (rows, 3)))
+
+    def _phases(self, what, phases, n, noun):
+        """`phases` of the texel queries, checked where given: an (n,) float32 tensor, one per texel.  `noun`: what the refusal
+        of another count calls the n."""
+        if phases is None:
+            return
+        if not _is_tensor(phases) or phases.dim() != 1:
+            raise ValueError(f"{what}: phases: needs a torch tensor of shape (n,) on the scene's device")
+        self._device_tensor(f"{what}: phases", phases.unsqueeze(1), 1, "torch.float32")
+        if phases.shape[0] != n:
+            raise ValueError(f"{what}: {n} {noun}, {phases.shape[0]} phases")
+
+    @staticmethod
+    def _atlas_shape(what, image):
+        """(w, h) of an (H, W, 4) atlas image, before its device is looked at: a 3-d tensor, 1 x 1 .. 2^28 texels, contiguous"""
+        if not _is_tensor(image) or image.dim() != 3:
+            raise ValueError(f"{what}: image: needs a torch tensor of shape (H, W, 4) on the scene's device")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        if h < 1 or w < 1 or h * w > 2 ** 28:
+            raise ValueError(f"{what}: a {w} x {h} atlas (1 x 1 .. 2^28 texels)")
+        if not image.is_contiguous():
+            raise ValueError(f"{what}: image: tensors must be contiguous")
+        return w, h
+
+    def _atlas_image(self, what, image):
+        """(w, h) of an atlas image, checked: _atlas_shape, then float32 texels of four on the scene's device.  atlas_filter
+        checks its numbers between the two, as it always has."""
+        w, h = self._atlas_shape(what, image)
+        self._device_tensor(f"{what}: image", image.view(h * w, -1), 4, "torch.float32")
+        return w, h
+
     def _enqueue_between_streams(self, dev, call, back=True):
         """`call()` enqueues on the context's stream.  Stream order by events, both ways: the context's stream waits for what
         torch enqueued on its current stream before the call (the inputs), and torch's current stream waits for the call
@@ -1114,13 +1143,7 @@ class Scene:
             raise ValueError(f"query_radiance: {n} origins, {directions.shape[0]} directions, {rng_states.shape[0]} states")
         if n >= 2 ** 31:
             raise ValueError(f"query_radiance: {n} rays (at most 2^31 - 1 per call)")
-        import torch
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=origins.device)
-        else:
-            self._device_tensor("query_radiance: out", out, 8, "torch.float32")
-            if out.shape[0] != n:
-                raise ValueError(f"query_radiance: out has {out.shape[0]} rows for {n} rays")
+        out = self._out_rows("query_radiance", out, n, 8, "torch.float32", origins.device, f"{n} rays")
         if n == 0:
             return out
         self._enqueue_between_streams(origins.device, lambda: self._chk(lib.hs_query_radiance(
@@ -1147,13 +1170,7 @@ class Scene:
             raise ValueError(f"query_probes: {n} probes x {k} directions need {n * k} states, got {rng_states.shape[0]}")
         if n >= 2 ** 31 or k >= 2 ** 31:
             raise ValueError(f"query_probes: {n} probes x {k} directions (at most 2^31 - 1 of each per call)")
-        import torch
-        if out is None:
-            out = torch.empty((n, 32), dtype=torch.float32, device=positions.device)
-        else:
-            self._device_tensor("query_probes: out", out, 32, "torch.float32")
-            if out.shape[0] != n:
-                raise ValueError(f"query_probes: out has {out.shape[0]} rows for {n} probes")
+        out = self._out_rows("query_probes", out, n, 32, "torch.float32", positions.device, f"{n} probes")
         if n == 0:
             return out
         self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_probes(
@@ -1173,12 +1190,7 @@ class Scene:
             raise ValueError(f"{what}: no directions")
         if n >= 2 ** 31 or k >= 2 ** 31:
             raise ValueError(f"{what}: {n} texels x {k} directions (at most 2^31 - 1 of each per call)")
-        if phases is not None:
-            if not _is_tensor(phases) or phases.dim() != 1:
-                raise ValueError(f"{what}: phases: needs a torch tensor of shape (n,) on the scene's device")
-            self._device_tensor(f"{what}: phases", phases.unsqueeze(1), 1, "torch.float32")
-            if phases.shape[0] != n:
-                raise ValueError(f"{what}: {n} positions, {phases.shape[0]} phases")
+        self._phases(what, phases, n, "positions")
         return n, k
 
     def query_irradiance(self, positions, normals, samples2, rng_states, samples=1, max_depth=None, max_distance=1e30, offset=1e-4,
@@ -1197,13 +1209,7 @@ class Scene:
         self._device_tensor("query_irradiance: rng_states", rng_states, 6, "torch.int32|torch.uint32")
         if rng_states.shape[0] != n * k:
             raise ValueError(f"query_irradiance: {n} texels x {k} directions need {n * k} states, got {rng_states.shape[0]}")
-        import torch
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=positions.device)
-        else:
-            self._device_tensor("query_irradiance: out", out, 8, "torch.float32")
-            if out.shape[0] != n:
-                raise ValueError(f"query_irradiance: out has {out.shape[0]} rows for {n} texels")
+        out = self._out_rows("query_irradiance", out, n, 8, "torch.float32", positions.device, f"{n} texels")
         if n == 0:
             return out
         self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_irradiance(
@@ -1232,13 +1238,7 @@ class Scene:
     def _direct_inputs(self, what, positions, normals, samples2, phases, lights):
         """the shared inputs of query_direct / direct_rays, checked; returns (n texels, samples2, shadow samples, first light,
         light count)"""
-        have = self.lightCount()
-        try:
-            first, count = (0, have) if lights is None else (int(lights[0]), int(lights[1]))
-        except (TypeError, IndexError):
-            raise ValueError(f"{what}: lights={lights!r}, expected None or (first, count)") from None
-        if first < 0 or count < 0 or first + count > have:
-            raise ValueError(f"{what}: lights ({first}, {count}) of the scene's {have}")
+        first, count = self._light_range(what, lights)
         self._device_tensor(f"{what}: positions", positions, 3, "torch.float32")
         if samples2 is None:
             import torch
@@ -1260,13 +1260,7 @@ class Scene:
         of samples that reached the texel (3) and that were blocked (4); `out` takes such a tensor to write into.
         `ptrt_amd.lightmap` adds it to a gather's rows.  No synchronisation."""
         n, samples2, k, first, count = self._direct_inputs("query_direct", positions, normals, samples2, phases, lights)
-        import torch
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=positions.device)
-        else:
-            self._device_tensor("query_direct: out", out, 8, "torch.float32")
-            if out.shape[0] != n:
-                raise ValueError(f"query_direct: out has {out.shape[0]} rows for {n} texels")
+        out = self._out_rows("query_direct", out, n, 8, "torch.float32", positions.device, f"{n} texels")
         if n == 0:
             return out
         self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_direct(
@@ -1280,12 +1274,8 @@ class Scene:
         Q = light count * k and q = light * k + sample (ptrt_direct_rays) -- for the samples query_direct does not walk too
         (weight not positive, NaN included).  Arguments as for query_direct.  No synchronisation."""
         n, samples2, k, first, count = self._direct_inputs("direct_rays", positions, normals, samples2, phases, lights)
-        import torch
         rays = n * count * k
-        o = torch.empty((rays, 3), dtype=torch.float32, device=positions.device)
-        d = torch.empty((rays, 3), dtype=torch.float32, device=positions.device)
-        t = torch.empty((rays,), dtype=torch.float32, device=positions.device)
-        w = torch.empty((rays, 3), dtype=torch.float32, device=positions.device)
+        o, d, t, w = self._ray_rows(rays, positions.device)
         if rays == 0:
             return o, d, t, w
         self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_direct_rays(
@@ -1295,7 +1285,7 @@ class Scene:
         return o, d, t, w
 
     def _light_range(self, what, lights):
-        """`lights` of query_bounce / bounce_terms, checked; returns (first light, light count)"""
+        """`lights` of the direct and bounce queries, checked; returns (first light, light count)"""
         have = self.lightCount()
         try:
             first, count = (0, have) if lights is None else (int(lights[0]), int(lights[1]))
@@ -1333,13 +1323,7 @@ class Scene:
         first, count = self._light_range("query_bounce", lights)
         n, k = self._texel_inputs("query_bounce", positions, normals, samples2, phases)
         shadow2, m = self._shadow_samples("query_bounce", positions.device, shadow2, count, k)
-        import torch
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=positions.device)
-        else:
-            self._device_tensor("query_bounce: out", out, 8, "torch.float32")
-            if out.shape[0] != n:
-                raise ValueError(f"query_bounce: out has {out.shape[0]} rows for {n} texels")
+        out = self._out_rows("query_bounce", out, n, 8, "torch.float32", positions.device, f"{n} texels")
         if n == 0:
             return out
         self._enqueue_between_streams(positions.device, lambda: self._chk(lib.hs_query_bounce(
@@ -1364,19 +1348,10 @@ class Scene:
         if k < 1 or r % k:
             raise ValueError(f"bounce_terms: {r} hits are not a multiple of n_dirs = {k}")
         n = r // k
-        if phases is not None:
-            if not _is_tensor(phases) or phases.dim() != 1:
-                raise ValueError("bounce_terms: phases: needs a torch tensor of shape (n,) on the scene's device")
-            self._device_tensor("bounce_terms: phases", phases.unsqueeze(1), 1, "torch.float32")
-            if phases.shape[0] != n:
-                raise ValueError(f"bounce_terms: {n} texels, {phases.shape[0]} phases")
+        self._phases("bounce_terms", phases, n, "texels")
         shadow2, m = self._shadow_samples("bounce_terms", hits.device, shadow2, count, k)
-        import torch
         rows = r * count * m
-        o = torch.empty((rows, 3), dtype=torch.float32, device=hits.device)
-        d = torch.empty((rows, 3), dtype=torch.float32, device=hits.device)
-        t = torch.empty((rows,), dtype=torch.float32, device=hits.device)
-        v = torch.empty((rows, 3), dtype=torch.float32, device=hits.device)
+        o, d, t, v = self._ray_rows(rows, hits.device)
         if rows == 0:
             return o, d, t, v
         self._enqueue_between_streams(hits.device, lambda: self._chk(lib.hs_bounce_terms(
@@ -1402,15 +1377,9 @@ class Scene:
         faces = self.meshCounts(int(mesh))[1]
         if uv.shape[0] != faces:
             raise ValueError(f"atlas_texels: uv has {uv.shape[0]} rows, mesh {mesh} has {faces} faces")
-        import torch
-        if out is None:
-            if not clear:
-                raise ValueError("atlas_texels: clear=False needs the atlas of an earlier call as `out`")
-            out = torch.empty((width * height, 8), dtype=torch.int32, device=uv.device)
-        else:
-            self._device_tensor("atlas_texels: out", out, 8, "torch.int32")
-            if out.shape[0] != width * height:
-                raise ValueError(f"atlas_texels: out has {out.shape[0]} rows for {width} x {height} texels")
+        if out is None and not clear:
+            raise ValueError("atlas_texels: clear=False needs the atlas of an earlier call as `out`")
+        out = self._out_rows("atlas_texels", out, width * height, 8, "torch.int32", uv.device, f"{width} x {height} texels")
         self._enqueue_between_streams(uv.device, lambda: self._chk(lib.hs_atlas_texels(
             self._h, int(mesh), _vp(uv.data_ptr()), width, height, 1 if clear else 0, _vp(out.data_ptr()))))
         return out
@@ -1422,14 +1391,7 @@ class Scene:
         in one pass spread in the next.  The passes alternate between `image` and a second buffer allocated here; returns the
         tensor that holds the result -- `image` itself for an even `passes` (it is overwritten from the second pass on).  No
         synchronisation."""
-        if not _is_tensor(image) or image.dim() != 3:
-            raise ValueError("atlas_dilate: image: needs a torch tensor of shape (H, W, 4) on the scene's device")
-        h, w = int(image.shape[0]), int(image.shape[1])
-        if h < 1 or w < 1 or h * w > 2 ** 28:
-            raise ValueError(f"atlas_dilate: a {w} x {h} atlas (1 x 1 .. 2^28 texels)")
-        if not image.is_contiguous():
-            raise ValueError("atlas_dilate: image: tensors must be contiguous")
-        self._device_tensor("atlas_dilate: image", image.view(h * w, -1), 4, "torch.float32")
+        w, h = self._atlas_image("atlas_dilate", image)
         passes = int(passes)
         if passes < 1 or passes > 64:
             raise ValueError(f"atlas_dilate: {passes} passes (1 .. 64)")
@@ -1451,13 +1413,7 @@ class Scene:
         recommends the sigmas.  The passes alternate between `image` and a second buffer allocated here; returns the tensor
         that holds the result -- `image` itself for an even `passes` (it is overwritten from the second pass on).  No
         synchronisation."""
-        if not _is_tensor(image) or image.dim() != 3:
-            raise ValueError("atlas_filter: image: needs a torch tensor of shape (H, W, 4) on the scene's device")
-        h, w = int(image.shape[0]), int(image.shape[1])
-        if h < 1 or w < 1 or h * w > 2 ** 28:
-            raise ValueError(f"atlas_filter: a {w} x {h} atlas (1 x 1 .. 2^28 texels)")
-        if not image.is_contiguous():
-            raise ValueError("atlas_filter: image: tensors must be contiguous")
+        w, h = self._atlas_shape("atlas_filter", image)
         passes, normal_power = int(passes), int(normal_power)
         if passes < 1 or passes > 8:
             raise ValueError(f"atlas_filter: {passes} passes (1 .. 8)")
@@ -1487,24 +1443,10 @@ class Scene:
             raise ValueError(f"{what}: chart_first: needs an (M,) int32 tensor on the scene's device, one entry per uploaded mesh")
         self._device_tensor(f"{what}: chart_first", chart_first.view(-1, 1) if chart_first.is_contiguous() else chart_first[:, None],
                             1, "torch.int32")
-        if not _is_tensor(image) or image.dim() != 3:
-            raise ValueError(f"{what}: image: needs a torch tensor of shape (H, W, 4) on the scene's device")
-        h, w = int(image.shape[0]), int(image.shape[1])
-        if h < 1 or w < 1 or h * w > 2 ** 28:
-            raise ValueError(f"{what}: a {w} x {h} atlas (1 x 1 .. 2^28 texels)")
-        if not image.is_contiguous():
-            raise ValueError(f"{what}: image: tensors must be contiguous")
-        self._device_tensor(f"{what}: image", image.view(h * w, -1), 4, "torch.float32")
+        w, h = self._atlas_image(what, image)
         if n >= 2 ** 31:
             raise ValueError(f"{what}: {n} rows (at most 2^31 - 1 per call)")
-        import torch
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.int32, device=image.device)
-        else:
-            self._device_tensor(f"{what}: out", out, 8, "torch.int32")
-            if out.shape[0] != n:
-                raise ValueError(f"{what}: out has {out.shape[0]} rows for {n}")
-        return w, h, LIGHTMAP_MODES[mode], out
+        return w, h, LIGHTMAP_MODES[mode], self._out_rows(what, out, n, 8, "torch.int32", image.device, f"{n}")
 
     def atlas_sample(self, hits, charts, chart_first, image, mode="bilinear", out=None):
         """The baked atlas read at ray hits (ptrt_atlas_sample).  torch tensors on this scene's device, contiguous, read in
@@ -1575,14 +1517,7 @@ class Scene:
             raise ValueError(f"{what}: probes has {probes.shape[0]} rows for a volume of {rows} probes")
         if n >= 2 ** 31:
             raise ValueError(f"{what}: {n} rows (at most 2^31 - 1 per call)")
-        import torch
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.int32, device=probes.device)
-        else:
-            self._device_tensor(f"{what}: out", out, 8, "torch.int32")
-            if out.shape[0] != n:
-                raise ValueError(f"{what}: out has {out.shape[0]} rows for {n}")
-        return out
+        return self._out_rows(what, out, n, 8, "torch.int32", probes.device, f"{n}")
 
     def probe_sample(self, positions, normals, volume, probes, mode="visibility", normal_bias=0.0, out=None):
         """A probe volume read at surface points (ptrt_probe_sample).  torch tensors on this scene's device, contiguous, read

@@ -130,19 +130,8 @@ def _light_rows(rows):
 def probe_light_fields(rows):
     """Named views of probe_sample's and query_probe_light's (n, 8) int32 rows (a tensor or an array): irradiance (n, 3) and
     weight (n,) reinterpreted as float32; cell, used, face and mesh int32, (n,)."""
-    rows = _light_rows(rows)
-    if hasattr(rows, "cpu"):
-        import torch
-        f32 = torch.float32
-    else:
-        f32 = np.float32
-    out = {}
-    for name, (a, b, is_f) in PROBE_LIGHT_COLUMNS.items():
-        col = rows[:, a:b]
-        if is_f:
-            col = col.view(f32)
-        out[name] = col[:, 0] if b - a == 1 else col
-    return out
+    from . import _flagged, _named_columns
+    return _named_columns(_light_rows(rows), PROBE_LIGHT_COLUMNS, ("float32", _flagged(PROBE_LIGHT_COLUMNS, True)))
 
 
 def shade_probe_light(rows, albedo, background=(0.0, 0.0, 0.0)):
