@@ -355,8 +355,11 @@ def mat_arrays(meshes, idx):
     return {k: g(k, v) for k, v in names.items()}
 
 
-def shade_direct(meshes, lights, ambient, m, P, Ng, t, d, allow, O):
-    """The direct part of calculatePBRLightingCore for hits with material arrays m."""
+def shade_direct(meshes, lights, ambient, m, P, Ng, t, d, allow, O, detail=None):
+    """The direct part of calculatePBRLightingCore for hits with material arrays m.  `detail` (a dict) receives what is
+    computed on the way: "amb" (the ambient term) and, per light, "Lo" (zero where shadowed), "shadow", and the terms of Lo
+    whether shadowed or not: "D", "G", "Fs" (Fresnel after the iridescence blend), "kD", "dif" (the diffuse colour) and
+    "ccB" (the clearcoat BRDF, zero without clearcoat)."""
     n = len(t)
     Vv = -d
     rough = mn(mx(m["roughness"], f32(0.02)), f32(1))
@@ -374,9 +377,15 @@ def shade_direct(meshes, lights, ambient, m, P, Ng, t, d, allow, O):
     kDa = ((f32(1) - Famb) * (f32(1) - metal)[:, None]).astype(f32)
     kDa[glass] = 0
     color = (color + kDa * m["albedo"] * V(ambient)).astype(f32)
+    if detail is not None:
+        detail.update(amb=(kDa * m["albedo"] * V(ambient)).astype(f32), Lo=np.zeros((n, len(lights), 3), f32),
+                      shadow=np.zeros((n, len(lights)), bool), D=np.zeros((n, len(lights)), f32),
+                      G=np.zeros((n, len(lights)), f32), Fs=np.zeros((n, len(lights), 3), f32),
+                      kD=np.zeros((n, len(lights), 3), f32), dif=np.zeros((n, len(lights), 3), f32),
+                      ccB=np.zeros((n, len(lights), 3), f32))
     eps = f32(1e-3) * mx(f32(1), t)
     so = (P + Ng * eps[:, None]).astype(f32)
-    for lt in lights:
+    for li, lt in enumerate(lights):
         ltype = lt.type
         lpos = V([lt.position.x, lt.position.y, lt.position.z])
         ldir = V([lt.direction.x, lt.direction.y, lt.direction.z])
@@ -461,6 +470,9 @@ def shade_direct(meshes, lights, ambient, m, P, Ng, t, d, allow, O):
                 thin = np.where(glass[:, None], (f32(1) - F) * m["transmission"][:, None], thin).astype(f32)
             Lo = ((((((kD * diffuse + spec) + thin) * lcol) * f32(lt.intensity)) * f32(20)) * NdotL[:, None]) * att[:, None]
             Lo = Lo.astype(f32)
+            if detail is not None:
+                for k, v in (("D", D), ("G", G), ("Fs", F), ("kD", kD), ("dif", diffuse)):
+                    detail[k][:, li] = v
             cc = m["clearcoat"] > 0
             if cc.any():
                 ccr = m["clearcoat_roughness"]
@@ -472,7 +484,12 @@ def shade_direct(meshes, lights, ambient, m, P, Ng, t, d, allow, O):
                 Lcc = Lo * (f32(1) - ccw * ccF) + (((((ccB * lcol) * f32(lt.intensity)) * f32(20)) * NdotL[:, None]) *
                                                     att[:, None]) * ccw
                 Lo = np.where(cc[:, None], Lcc, Lo).astype(f32)
+                if detail is not None:
+                    detail["ccB"][:, li] = np.where(cc[:, None], ccB, f32(0))
         color = np.where(lit[:, None], color + Lo, color).astype(f32)
+        if detail is not None:
+            detail["Lo"][:, li] = np.where(lit[:, None], Lo, f32(0))
+            detail["shadow"][:, li] = shadow
     return color
 
 
@@ -484,8 +501,10 @@ def sky(view, d):
     return lerp(bot[None, :], top[None, :], f32(0.5) * (d[:, 1] + f32(1)))
 
 
-def shade_segment(meshes, lights, view, o, d, allow, O, counts=None):
-    """closest hit + direct shading (or the sky): (colour, hit, t, material arrays, point, normal)."""
+def shade_segment(meshes, lights, view, o, d, allow, O, counts=None, detail=None):
+    """closest hit + direct shading (or the sky): (colour, hit, t, material arrays, point, normal).  `detail` (a dict)
+    receives the segment's records over all its rays: hit, t, mesh, face, point, normal, linear, and shade_direct's
+    amb, Lo, shadow, D, G, Fs, kD, dif, ccB."""
     hit, t, mi, face = trace(meshes, o, d)
     c = sky(view, d)
     h = np.nonzero(hit)[0]
@@ -504,15 +523,30 @@ def shade_segment(meshes, lights, view, o, d, allow, O, counts=None):
             Ng[sel] = normalize(mat_mul(M.R, nl))
         m = mat_arrays(meshes, mi[h])
         amb = V([view.ambient.x, view.ambient.y, view.ambient.z])
-        c[h] = shade_direct(meshes, lights, amb, m, P, Ng, th, d[h], allow, O)
+        dd = None if detail is None else {}
+        c[h] = shade_direct(meshes, lights, amb, m, P, Ng, th, d[h], allow, O, dd)
+    if detail is not None:
+        n, nl = len(t), len(lights)
+        detail.update(hit=hit, t=np.where(hit, t, f32(0)), mesh=np.where(hit, mi, -1), face=np.where(hit, face, -1),
+                      point=np.zeros((n, 3), f32), normal=np.zeros((n, 3), f32), linear=c.copy(),
+                      amb=np.zeros((n, 3), f32), Lo=np.zeros((n, nl, 3), f32), shadow=np.zeros((n, nl), bool),
+                      D=np.zeros((n, nl), f32), G=np.zeros((n, nl), f32), Fs=np.zeros((n, nl, 3), f32),
+                      kD=np.zeros((n, nl, 3), f32), dif=np.zeros((n, nl, 3), f32), ccB=np.zeros((n, nl, 3), f32))
+        if len(h):
+            detail["point"][h], detail["normal"][h] = P, Ng
+            for k in ("amb", "Lo", "shadow", "D", "G", "Fs", "kD", "dif", "ccB"):
+                detail[k][h] = dd[k]
     return c, hit, t, h, m, P, Ng
 
 
-def render(snap, W, H, O, counts=None):
+def render(snap, W, H, O, counts=None, detail=None):
     """The image of rt_render_kernel for `snap` (Scene.snapshot()) as (H, W, 3) uint8 in the buffer's bottom-up order.
     `counts` (a dict) receives the rays the frame traces: "primary" (one per pixel), "shadow" (one per light at every
     shaded hit, whatever the light's contribution), "reflection" and "refraction" (glass pixels; no refraction ray
-    under total internal reflection)."""
+    under total internal reflection).  `detail` (a dict) receives what the frame computes on the way, per pixel in the
+    order y * W + x of the kernel's threads: "dir", the segments' records "0", "R", "T" (see shade_segment; R and T over
+    "glass" pixels, T over those with "refr_ok"), "Fr", "Rdir", "Tdir", "thickness", "seed" (before the first draw),
+    "linear" (before Reinhard) and "final" (after gamma, before the clamp)."""
     if counts is not None:
         counts.update(primary=W * H, shadow=0, reflection=0, refraction=0)
     meshes = [MeshData(m) for m in snap["meshes"]]
@@ -527,7 +561,14 @@ def render(snap, W, H, O, counts=None):
     org = V([view.origin.x, view.origin.y, view.origin.z])
     d = normalize(((cmo + u[:, None] * hor) + v[:, None] * ver).astype(f32))
     o = np.broadcast_to(org, d.shape).astype(f32)
-    color, hit, t, h, m, P, Ng = shade_segment(meshes, lights, view, o, d, True, O, counts)
+    want = detail is not None
+    d0 = {} if want else None
+    color, hit, t, h, m, P, Ng = shade_segment(meshes, lights, view, o, d, True, O, counts, d0)
+    if want:
+        n = W * H
+        detail.update({"dir": d, "0": d0, "glass": np.zeros(n, bool), "refr_ok": np.zeros(n, bool),
+                       "Fr": np.zeros((n, 3), f32), "Rdir": np.zeros((n, 3), f32), "Tdir": np.zeros((n, 3), f32),
+                       "thickness": np.zeros(n, f32), "seed": np.zeros(n, np.uint32), "R": None, "T": None})
     if len(h):
         metal = mn(mx(m["metallic"], f32(0)), f32(1))
         gl = (m["transmission"] > 0) & (metal < f32(0.1))
@@ -549,6 +590,8 @@ def render(snap, W, H, O, counts=None):
             seed = (Pg[:, 0] * f32(12.9898) + Pg[:, 1] * f32(78.233) + Pg[:, 2] * f32(45.164)).astype(f32).view(np.uint32)
             with np.errstate(over="ignore"):
                 seed = seed * np.uint32(747796405) + np.uint32(2891336453)
+            if want:
+                detail["seed"][g] = seed
             Rdir = normalize((I - (f32(2) * dot(I, Nf))[:, None] * Nf).astype(f32))
             rr = mx(m["roughness"][gl], m["transmission_roughness"][gl])
             pr = rr > f32(0.02)
@@ -569,22 +612,32 @@ def render(snap, W, H, O, counts=None):
             if counts is not None:
                 counts["reflection"] += len(g)
                 counts["refraction"] += int(ok.sum())
-            Rcol, *_ = shade_segment(meshes, lights, view, (Pg + Nf * eps[:, None]).astype(f32), Rdir, False, O, counts)
+            dR = {} if want else None
+            Rcol, *_ = shade_segment(meshes, lights, view, (Pg + Nf * eps[:, None]).astype(f32), Rdir, False, O, counts, dR)
             Tcol = np.zeros_like(Rcol)
             if ok.any():
                 oo = (Pg[ok] - Nf[ok] * eps[ok][:, None]).astype(f32)
-                beh, h2, t2, *_ = shade_segment(meshes, lights, view, oo, Tdir[ok], False, O, counts)
+                dT = {} if want else None
+                beh, h2, t2, *_ = shade_segment(meshes, lights, view, oo, Tdir[ok], False, O, counts, dT)
                 thick = np.where(h2, t2, f32(1)).astype(f32)
+                if want:
+                    detail["T"] = dT
+                    detail["thickness"][g[ok]] = thick
                 a = mn(mx(m["albedo"][gl][ok], f32(0)), f32(1))
                 absorb = np.stack([pos_pow(a[:, c], thick, O) for c in range(3)], axis=1)
                 Tcol[ok] = (absorb * beh).astype(f32)
             Fr[~ok] = 1
+            if want:
+                detail["glass"][g], detail["refr_ok"][g], detail["R"] = True, ok, dR
+                detail["Fr"][g], detail["Rdir"][g], detail["Tdir"][g] = Fr, Rdir, Tdir
             tm = m["transmission"][gl]
             color[g] = ((color[g] + Fr * Rcol) + ((f32(1) - Fr) * tm[:, None]) * Tcol).astype(f32)
     with np.errstate(all="ignore"):
         c = (color / (color + f32(1))).astype(f32)
     gch = np.stack([pos_pow(c[:, k], GAMMA, O) for k in range(3)], axis=1)
     rgb = (mn(mx(gch, f32(0)), f32(1)) * f32(255.0)).astype(f32)
+    if want:
+        detail.update(linear=color, final=gch, rgb=rgb)
     img = np.zeros((H, W, 3), np.uint8)
     img[H - 1 - y, x] = rgb.astype(np.int32).astype(np.uint8)
     return img
