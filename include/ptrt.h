@@ -1045,6 +1045,55 @@ int ptrt_init_rng_states(ptrt_ctx *ctx, unsigned long long seed, unsigned long l
  * PTRT_E_NOT_READY before geometry and materials are uploaded.  (ABI 6, addition only.) */
 int ptrt_render_wireframe(ptrt_ctx *ctx, float thickness, void *out_rgb8, int out_is_device);
 
+/* The baked-light view: the scene lit by what was baked for it -- a lightmap atlas (ptrt_query_lightmap's four arguments), a probe
+ * volume (ptrt_query_probe_light's), both or neither -- as one frame, in one launch: primary ray, closest hit, the two samplers,
+ * the context's own materials, the path frame's tonemap.  `view` is HOST memory and is copied into the launch; the pointers in
+ * it are DEVICE memory.  d_image NULL: no lightmap (its other fields are not looked at); d_probes NULL: no probes; with neither
+ * the frame shows emission and sky only.  Like the wireframe view it is always the full width x height: the render size of the
+ * path tracer, bloom and the denoiser play no part.
+ * A pixel is ONE definition in fp32, every operation rounded on its own (no contraction), `/` the IEEE quotient.  For pixel
+ * (x, y) of the context's rows:
+ *   1. The primary ray is the one ptrt_camera_rays(frame_index, 0) writes for the pixel when no reduced render size is set: the
+ *      TAA and blue-noise jitter of frame_index over the full width and height, the pinhole camera.
+ *   2. The closest hit is what ptrt_query_rays(PTRT_QUERY_CLOSEST) answers for that ray.
+ *   3. A miss:  c = use_sky ? sampleSky(direction) : 0  (ptrt_set_sky, ptrt_set_env_map).
+ *   4. A hit on face f of mesh m at (u, v): the irradiance E is, in this order,
+ *        the `rgb` of ptrt_query_lightmap's sample        where a lightmap is given and the sample's weight > 0;
+ *        the `irradiance` of ptrt_query_probe_light's      otherwise, where a volume is given and its weight > 0: the sample at
+ *                                                          the hit's `point` and face-forwarded `normal`;
+ *        +0                                                otherwise.
+ *      The probe sample runs only in pixels the lightmap left empty -- a mesh without a chart (d_chart_first[m] < 0: a moving
+ *      object is lit by the volume, a baked wall by its atlas), a texel that is invalid or outside the atlas, a non-finite chart
+ *      point -- and the skip is by selection: what an unused sample holds reaches nothing.  A NaN weight is not > 0.
+ *   5. c = (albedo_m * E) / 3.14159265f + emission_m per channel -- the product, the quotient, then the sum -- with albedo_m and
+ *      emission_m the context's materials as uploaded (ptrt_upload_materials): ptrt_amd.lightmap.shade_samples' three operations.
+ *   6. The outputs, each optional, at least one of out_rgb8 and d_hdr given:
+ *        d_hdr                        rows*W*3 floats, pixel yl*W + x, the order of PTRT_BUF_ACCUM:  c;
+ *        d_normal, d_depth,           rows*W*3 floats, rows*W floats, rows*W int32, the layouts ptrt_post_frame takes: what a frame
+ *        d_object_id                  keeps of a first hit -- the face-forwarded normal or zeros, t or 1e30f, the mesh or -1;
+ *        out_rgb8                     the path frame's tonemap of c (ACES + sRGB), bottom-up, as for ptrt_render_wireframe:
+ *                                     PTRT_OUT_HOST synchronous, PTRT_OUT_DEVICE the context's rows, PTRT_OUT_DEVICE_FRAME the
+ *                                     whole frame (a band context writes its rows where they belong in it).
+ * tests/baked_view_restatement.py states 3 to 6 in numpy over the rows of the entry points named above.
+ * Ordering and side effects are the wireframe view's: enqueued on the context's stream, behind any earlier ptrt_render of the
+ * context (pipelined ones included); touches no generator state, accumulation, G-buffer or PTRT_BUF_RGB8 image, no counter of
+ * ptrt_get_stats and no timing history.  The grid is the device queries' -- persistent one-wave workgroups striding over the
+ * frame's 8x8 tiles, the traversal a frame would walk (ptrt_get_option "query_pmode"); option "persist" sizes it.
+ * PTRT_E_INVALID (nothing enqueued, every output untouched) for an interleaved context, a thin lens (as ptrt_camera_rays), a
+ * negative frame_index, a NULL view, no target at all (out_rgb8 and d_hdr both NULL, or an out_is_device outside the three), a
+ * lightmap half ptrt_query_lightmap would refuse, a probe half ptrt_query_probe_light would refuse, an output that is not the
+ * context's device memory, is too small, is not 4-byte aligned or overlaps an input or another output (byte counts in size_t).
+ * PTRT_E_NOT_READY before geometry and materials are uploaded, or with fewer materials than meshes.  Not built: more than one
+ * atlas or volume per frame, a reduced render size, exposure, RT-context and tile-farm variants.  (ABI 6, addition only.) */
+typedef struct ptrt_baked_view {           /* HOST memory, copied into the launch */
+    const float *d_charts; int32_t n_chart_faces; const int32_t *d_chart_first;
+    const float *d_image; int32_t atlas_w, atlas_h, lightmap_mode;   /* d_image NULL: no lightmap */
+    ptrt_probe_volume volume; const ptrt_probe *d_probes;
+    int32_t probe_mode; float normal_bias;                           /* d_probes NULL: no probes  */
+    float *d_hdr, *d_normal, *d_depth; int32_t *d_object_id;         /* each may be NULL          */
+} ptrt_baked_view;
+int ptrt_render_baked(ptrt_ctx *ctx, int frame_index, const ptrt_baked_view *view, void *out_rgb8, int out_is_device);
+
 /* counters accumulated by ptrt_render since the last call (reset on read);
  * only maintained when ptrt_set_option(ctx,"count_rays",1). */
 int ptrt_get_stats(ptrt_ctx *ctx, ptrt_stats *out);

@@ -27,6 +27,7 @@
 #include "pt_atlas_filter.hip.h"
 #include "pt_lightmap.hip.h"
 #include "pt_probe_sample.hip.h"
+#include "pt_baked.hip.h"
 #include "rt_render.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -1254,6 +1255,154 @@ int ptrt_render_wireframe(ptrt_ctx *c, float thickness, void *out_rgb8, int out_
     if (out_is_device == PTRT_OUT_DEVICE)
         ring_mark_rendered(out_rgb8, c->stream);
     if (!out_is_device) {
+        HIP_TRY(c, hipMemcpyAsync(out_rgb8, c->wire_rgb8, c->npix * 3, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return PTRT_OK;
+}
+
+// The baked-light view: baked_view_kernel (pt_baked.hip.h) through the queries' plan, variant and persistent grid, into the
+// wireframe view's targets.  Every refusal comes before anything is enqueued.
+int ptrt_render_baked(ptrt_ctx *c, int frame_index, const ptrt_baked_view *view, void *out_rgb8, int out_is_device) {
+    const char *fn = "ptrt_render_baked";
+    if (!ctx_live(c)) // (marks the context touched: a pipelined path frame that follows waits for the stream, and so for this)
+        return fail(c, PTRT_E_INVALID, "%s: bad context", fn);
+    if (c->il_period > 1)
+        return fail(c, PTRT_E_INVALID, "%s: an interleaved context (its strips are assembled by the tile farm, which has no baked "
+                                       "view); use a full-frame or band context", fn);
+    if (!view)
+        return fail(c, PTRT_E_INVALID, "%s: view is NULL", fn);
+    if (frame_index < 0)
+        return fail(c, PTRT_E_INVALID, "%s: frame_index=%d", fn, frame_index);
+    if (c->cam.lens_radius > 0.0f)
+        return fail(c, PTRT_E_INVALID, "%s: a thin lens (lens_radius %g): the lens sample of a primary ray is drawn from the pixel's "
+                                       "generator stream", fn, (double)c->cam.lens_radius);
+    if (out_is_device < PTRT_OUT_HOST || out_is_device > PTRT_OUT_DEVICE_FRAME || (!out_rgb8 && !view->d_hdr))
+        return fail(c, PTRT_E_INVALID, "%s: needs a target (out_rgb8 %p, out_is_device %d, d_hdr %p)", fn, out_rgb8, out_is_device,
+                    (const void *)view->d_hdr);
+    const bool lightmap = view->d_image != nullptr, probes = view->d_probes != nullptr;
+    // the lightmap half: what ptrt_query_lightmap refuses
+    if (lightmap) {
+        if (view->n_chart_faces < 1 || !view->d_charts || !view->d_chart_first || !atlas_size_ok(view->atlas_w, view->atlas_h) ||
+            (view->lightmap_mode != PTRT_LIGHTMAP_NEAREST && view->lightmap_mode != PTRT_LIGHTMAP_BILINEAR))
+            return fail(c, PTRT_E_INVALID, "%s: lightmap: bad argument (charts %p, n_chart_faces %d: >= 1, chart_first %p, atlas %d x %d: "
+                                           "1 x 1 .. 2^28 texels, mode %d: 0 or 1)", fn, (const void *)view->d_charts, view->n_chart_faces,
+                        (const void *)view->d_chart_first, view->atlas_w, view->atlas_h, view->lightmap_mode);
+        if (!aligned16(view->d_image) || ((uintptr_t)view->d_charts & 3u) || ((uintptr_t)view->d_chart_first & 3u))
+            return fail(c, PTRT_E_INVALID, "%s: lightmap: image %p must be 16-byte aligned, charts %p and chart_first %p 4-byte", fn,
+                        (const void *)view->d_image, (const void *)view->d_charts, (const void *)view->d_chart_first);
+    }
+    // the probe half: what ptrt_query_probe_light refuses
+    long long probe_rows = 1;
+    if (probes) {
+        if ((view->probe_mode != PTRT_PROBES_TRILINEAR && view->probe_mode != PTRT_PROBES_VISIBILITY) || !(view->normal_bias >= 0.0f) ||
+            !std::isfinite(view->normal_bias))
+            return fail(c, PTRT_E_INVALID, "%s: probes: bad argument (mode %d: 0 or 1, normal_bias %g: >= 0 and finite)", fn,
+                        view->probe_mode, (double)view->normal_bias);
+        for (int a = 0; a < 3; ++a) {
+            const ptrt_probe_volume &vol = view->volume;
+            if (vol.counts[a] < 1 || !(vol.spacing[a] > 0.0f) || !std::isfinite(vol.spacing[a]) || !std::isfinite(vol.origin[a]))
+                return fail(c, PTRT_E_INVALID, "%s: volume axis %d: count %d (>= 1), spacing %g (positive and finite), origin %g (finite)",
+                            fn, a, vol.counts[a], (double)vol.spacing[a], (double)vol.origin[a]);
+            probe_rows *= vol.counts[a]; // each factor < 2^31 and the product so far <= 2^24: no overflow
+            if (probe_rows > (1ll << 24))
+                return fail(c, PTRT_E_INVALID, "%s: a volume of %d x %d x %d probes (at most 2^24)", fn, vol.counts[0], vol.counts[1],
+                            vol.counts[2]);
+        }
+        if (!aligned16(view->d_probes))
+            return fail(c, PTRT_E_INVALID, "%s: probes %p must be 16-byte aligned", fn, (const void *)view->d_probes);
+    }
+    if (((uintptr_t)view->d_hdr & 3u) || ((uintptr_t)view->d_normal & 3u) || ((uintptr_t)view->d_depth & 3u) || ((uintptr_t)view->d_object_id & 3u))
+        return fail(c, PTRT_E_INVALID, "%s: hdr %p, normal %p, depth %p and object_id %p must be 4-byte aligned", fn, (const void *)view->d_hdr,
+                    (const void *)view->d_normal, (const void *)view->d_depth, (const void *)view->d_object_id);
+    if (!c->have_geometry || !c->have_materials)
+        return fail(c, PTRT_E_NOT_READY, "%s: %s not uploaded", fn, c->have_geometry ? "materials" : "geometry");
+    if (c->n_materials < c->n_meshes)
+        return fail(c, PTRT_E_NOT_READY, "%s: %d materials for %d meshes", fn, c->n_materials, c->n_meshes);
+    // the spans: every output apart from every input and from every other output, all of them the context's device memory
+    const size_t pix = (size_t)c->rows * (size_t)c->W;
+    const Span ins[4] = {{"charts", view->d_charts, lightmap ? (size_t)view->n_chart_faces * 24 : 0},
+                         {"chart_first", view->d_chart_first, lightmap ? (size_t)c->n_meshes * sizeof(int32_t) : 0},
+                         {"image", view->d_image, lightmap ? (size_t)view->atlas_w * (size_t)view->atlas_h * 16 : 0},
+                         {"probes", view->d_probes, probes ? (size_t)probe_rows * sizeof(ptrt_probe) : 0}};
+    const Span outs[5] = {{"hdr", view->d_hdr, pix * 12},
+                          {"normal", view->d_normal, pix * 12},
+                          {"depth", view->d_depth, pix * 4},
+                          {"object_id", view->d_object_id, pix * 4},
+                          {"out_rgb8", out_is_device ? out_rgb8 : nullptr,
+                           (out_is_device == PTRT_OUT_DEVICE_FRAME ? (size_t)c->H : (size_t)c->rows) * (size_t)c->W * 3}};
+    for (int i = 0; i < 5; ++i) {
+        if (!outs[i].p)
+            continue;
+        for (const Span &s : ins)
+            if (s.bytes && !spans_apart(outs[i], s))
+                return fail(c, PTRT_E_INVALID, "%s: %s %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, outs[i].name, outs[i].p, outs[i].bytes,
+                            s.name, s.p, s.bytes);
+        for (int j = 0; j < i; ++j)
+            if (outs[j].p && !spans_apart(outs[i], outs[j]))
+                return fail(c, PTRT_E_INVALID, "%s: %s %p (%zu bytes) overlaps %s %p (%zu bytes)", fn, outs[i].name, outs[i].p, outs[i].bytes,
+                            outs[j].name, outs[j].p, outs[j].bytes);
+    }
+    if (int rc = set_device(c))
+        return rc;
+    for (const Span &s : ins)
+        if (s.bytes && !device_span(c, s.p, s.bytes))
+            return fail(c, PTRT_E_INVALID, "%s: %s is not %zu bytes of device memory on device %d", fn, s.name, s.bytes, c->device);
+    for (const Span &s : outs)
+        if (s.p && !device_span(c, s.p, s.bytes))
+            return fail(c, PTRT_E_INVALID, "%s: %s is not %zu bytes of device memory on device %d", fn, s.name, s.bytes, c->device);
+    if (!out_is_device && out_rgb8 && !c->wire_rgb8)
+        HIP_TRY(c, hipMalloc((void **)&c->wire_rgb8, c->npix * 3));
+
+    pt::BakedViewParams B{};
+    if (lightmap) {
+        B.L.charts = view->d_charts;
+        B.L.chart_first = view->d_chart_first;
+        B.L.image = reinterpret_cast<const float4 *>(view->d_image);
+        B.L.n_chart_faces = view->n_chart_faces;
+        B.L.n_meshes = c->n_meshes;
+        B.L.aw = view->atlas_w;
+        B.L.ah = view->atlas_h;
+        B.L.mode = view->lightmap_mode;
+    }
+    if (probes) {
+        B.V.probes = reinterpret_cast<const float4 *>(view->d_probes);
+        for (int a = 0; a < 3; ++a) {
+            B.V.origin[a] = view->volume.origin[a];
+            B.V.spacing[a] = view->volume.spacing[a];
+            B.V.counts[a] = view->volume.counts[a];
+        }
+        B.V.mode = view->probe_mode;
+        B.V.bias = view->normal_bias;
+    }
+    B.hdr = view->d_hdr;
+    B.normal = view->d_normal;
+    B.depth = view->d_depth;
+    B.object_id = view->d_object_id;
+    QueryPlan P;
+    if (int rc = plan_query(c, false, 0, 0, P))
+        return rc;
+    // the full frame, whatever the render size of the path tracer; the context's own per-pixel buffers are no business of the view's
+    P.K.width = c->W;
+    P.K.height = c->H;
+    P.K.y0 = c->y0;
+    P.K.rows = c->rows;
+    P.K.tiles_x = (c->W + 7) / 8;
+    P.K.frame_count = frame_index;
+    P.K.rng = nullptr;
+    P.K.accum = P.K.normal = P.K.depth = nullptr;
+    P.K.object_id = nullptr;
+    P.K.counters = nullptr;
+    P.K.rgb8 = !out_rgb8 ? nullptr : out_is_device ? (unsigned char *)out_rgb8 : c->wire_rgb8;
+    P.K.rgb8_frame = out_is_device == PTRT_OUT_DEVICE_FRAME ? 1 : 0;
+    const size_t tiles = (size_t)P.K.tiles_x * (size_t)((c->rows + 7) / 8);
+    if (int rc = with_variant(P.geom, P.pmode, [&](auto G, auto PM) {
+            return launch_persistent(c, pt::baked_view_kernel<G, PM>, P.lds, tiles, true, P.K, B);
+        }))
+        return rc;
+    if (out_rgb8 && out_is_device == PTRT_OUT_DEVICE)
+        ring_mark_rendered(out_rgb8, c->stream);
+    if (out_rgb8 && !out_is_device) {
         HIP_TRY(c, hipMemcpyAsync(out_rgb8, c->wire_rgb8, c->npix * 3, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }

@@ -532,6 +532,17 @@ int hs_render_wireframe_to_host(void *s, void *host_pixels, float thickness) {
     HS_TRY(static_cast<Scene *>(s)->render_wireframe_to_host(static_cast<unsigned char *>(host_pixels), thickness));
     return 0;
 }
+// `frame` < 0: the frame index render_to_device would use next
+int hs_render_baked(void *s, int frame, const void *view, void *pixels, int is_device) {
+    if (!view) {
+        g_err = "render_baked: no view";
+        return -1;
+    }
+    Scene *sc = static_cast<Scene *>(s);
+    HS_TRY(sc->renderBaked(frame < 0 ? sc->getFrameCount() : frame, static_cast<unsigned char *>(pixels),
+                           *static_cast<const ptrt_baked_view *>(view), is_device));
+    return 0;
+}
 int hs_post_frame(void *s, const float *accum, const float *normal, const float *depth, const int *object_id,
                   void *pixels, int is_device) {
     HS_TRY(static_cast<Scene *>(s)->postFrameFromDevice(accum, normal, depth, object_id,

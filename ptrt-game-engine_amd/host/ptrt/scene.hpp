@@ -841,6 +841,28 @@ class Scene {
     void render_wireframe_to_host(unsigned char *host_pixels, float wireframeThickness) {
         renderWireframe(host_pixels, wireframeThickness, PTRT_OUT_HOST);
     }
+    // The baked-light view (ptrt_render_baked): the scene lit by a lightmap atlas, a probe volume, both or neither -- `view`
+    // names them, with the HDR image and G-buffers to fill beside the RGB8 target (each may be null) -- at the frame index
+    // render_to_device would use next, which it does not advance.  Leaves the accumulation, the generator states and the
+    // denoiser history alone and does not synchronise.  `device_pixels`: this scene's rows, bottom-up; nullptr: no RGB8.
+    void render_to_device_baked(unsigned char *device_pixels, const ptrt_baked_view &view) {
+        renderBaked(frame_count_, device_pixels, view, PTRT_OUT_DEVICE);
+    }
+    // the same image into HOST memory (synchronous), like render_to_host
+    void render_baked_to_host(unsigned char *host_pixels, const ptrt_baked_view &view) {
+        renderBaked(frame_count_, host_pixels, view, PTRT_OUT_HOST);
+    }
+    // the same at a frame index of the caller's and any of ptrt_render's three targets (PTRT_OUT_DEVICE_FRAME: a band scene's
+    // rows into the whole frame)
+    void renderBaked(int frame, unsigned char *pixels, const ptrt_baked_view &view, int is_device) {
+        if (meshes.empty()) {
+            std::cerr << "Error: no meshes in scene\n";
+            return;
+        }
+        needBackend();
+        updateDeviceScene();
+        check(ptrt_render_baked(ctx, frame, &view, pixels, is_device), "Baked view failed");
+    }
 
     // ---- upload + render -------------------------------------------------------------
     void uploadToGPU() { // scene.cuh:1643-1657

@@ -399,6 +399,8 @@ _sig("hs_query_lightmap", C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _v
 _sig("hs_probe_sample", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, _vp)
 _sig("hs_query_probe_light", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, _vp)
 _sig("hs_camera_rays", C.c_int, _vp, C.c_int, C.c_int, _vp, _vp)
+_sig("hs_render_baked", C.c_int, _vp, C.c_int, _vp, _vp, C.c_int)
+_sig("ptrt_render_baked", C.c_int, _vp, C.c_int, _vp, _vp, C.c_int)
 _sig("hs_init_rng_states", C.c_int, _vp, C.c_ulonglong, C.c_ulonglong, C.c_int, _vp)
 _sig("hs_post_frame", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int)
 _sig("hs_get_frame_count", C.c_int, _vp)
@@ -894,6 +896,79 @@ class Scene:
         """The wireframe view into a host array (tile_rows, width, 3), in the buffer's bottom-up order like render_to_host."""
         out = np.empty((self.tile_rows, self.width, 3), dtype=np.uint8)
         self._chk(lib.hs_render_wireframe_to_host(self._h, out.ctypes.data_as(_vp), float(thickness)))
+        return out
+
+    def render_baked(self, target=None, *, frame=None, charts=None, chart_first=None, image=None, lightmap_mode="bilinear",
+                     volume=None, probes=None, probe_mode="visibility", normal_bias=0.0, hdr=None, gbuffers=False):
+        """The baked-light view (ptrt_render_baked): the scene lit by a lightmap atlas -- `charts`, `chart_first`, `image` as for
+        query_lightmap --, by a probe volume -- `volume`, `probes` as for query_probe_light --, by both (the atlas where it has a
+        sample, the volume elsewhere: moving objects, invalid texels) or by neither (emission and sky), shaded with the scene's
+        own materials, in one launch.  `frame`: the frame index whose jitter the primary rays take (None: the one
+        render_to_device would use next; it is not advanced).  torch tensors on this scene's device, contiguous, used in place.
+        `target`: None -- RGB8 into a host array (tile_rows, width, 3), bottom-up like render_to_host, synchronous; a uint8
+        tensor (tile_rows, width, 3) -- this scene's rows on the device; on a band scene a uint8 tensor (height, width, 3) --
+        the scene's rows where they belong in the whole frame; False -- no RGB8.  `hdr`: True or an (n, 3) float32 tensor, n =
+        tile_rows * width: the linear colour in the order of read(BUF_ACCUM).  `gbuffers`: True or (normal (n, 3) float32, depth
+        (n,) float32, object_id (n,) int32): what a frame keeps of a first hit, the layouts post_frame takes.  Returns the host
+        array when that is all that was asked for, else a dict of what was filled (rgb8, hdr, normal, depth, object_id).  Only
+        a host target synchronises."""
+        from . import baked
+        import numpy as _np
+        if frame is not None and (int(frame) != frame or frame < 0):
+            raise ValueError(f"render_baked: frame {frame!r} (None or an integer >= 0)")
+        n = self.tile_rows * self.width
+        out = {}
+        lazy = []  # (key, shape, dtype name) of the tensors to make once the inputs have passed
+        if hdr is True:
+            lazy.append(("hdr", (n, 3), "float32"))
+        elif hdr is not None and hdr is not False:
+            out["hdr"] = hdr
+        if gbuffers is True:
+            lazy += [("normal", (n, 3), "float32"), ("depth", (n,), "float32"), ("object_id", (n,), "int32")]
+        elif gbuffers is not False and gbuffers is not None:
+            try:
+                out["normal"], out["depth"], out["object_id"] = gbuffers
+            except (TypeError, ValueError):
+                raise ValueError("render_baked: gbuffers: True or the three tensors (normal, depth, object_id)") from None
+        mode = 0  # PTRT_OUT_HOST
+        if target is not None and target is not False:
+            shapes = {(self.tile_rows, self.width, 3): 1, (self.height, self.width, 3): 2}  # PTRT_OUT_DEVICE, _FRAME
+            if not hasattr(target, "data_ptr") or tuple(target.shape) not in shapes:
+                raise ValueError(f"render_baked: target: None, False or a uint8 tensor of shape {(self.tile_rows, self.width, 3)}" +
+                                 (f" or {(self.height, self.width, 3)}" if self.tile_rows != self.height else "") +
+                                 f", got {tuple(getattr(target, 'shape', ())) or type(target).__name__}")
+            mode = 1 if tuple(target.shape) == (self.tile_rows, self.width, 3) else 2
+            baked._tensor(self, "target", target, tuple(target.shape), "torch.uint8")
+            out["rgb8"] = target
+        if target is False and "hdr" not in out and not any(k == "hdr" for k, _, _ in lazy):
+            raise ValueError("render_baked: no target at all: target=False needs hdr")
+        view, keep = baked.baked_view(self, charts=charts, chart_first=chart_first, image=image, lightmap_mode=lightmap_mode,
+                                      volume=volume, probes=probes, probe_mode=probe_mode, normal_bias=normal_bias,
+                                      hdr=out.get("hdr"), normal=out.get("normal"), depth=out.get("depth"),
+                                      object_id=out.get("object_id"))
+        if mode:
+            baked._on_device(self, "target", target)
+        if lazy:
+            import torch
+            if self.device < 0:
+                raise ValueError("render_baked: hdr and gbuffers need a device, this scene renders on no device (host-only)")
+            for key, shape, dt in lazy:
+                out[key] = torch.empty(shape, dtype=getattr(torch, dt), device=torch.device("cuda", self.device))
+                setattr(view, "d_" + key, out[key].data_ptr())
+        fr = -1 if frame is None else int(frame)
+        host = _np.empty((self.tile_rows, self.width, 3), dtype=_np.uint8) if target is None else None
+        pixels = host.ctypes.data_as(_vp) if host is not None else _vp(target.data_ptr()) if mode else None
+        call = lambda: self._chk(lib.hs_render_baked(self._h, fr, C.byref(view), pixels, mode))  # noqa: E731
+        if self.device >= 0 and (keep or out):
+            import torch
+            self._enqueue_between_streams(torch.device("cuda", self.device), call)
+        else:
+            call()
+        del keep
+        if host is not None:
+            if not out:
+                return host
+            out["rgb8"] = host
         return out
 
     def post_frame(self, accum_ptr, normal_ptr, depth_ptr, object_id_ptr, out_device_ptr=None):
@@ -1672,4 +1747,4 @@ class TileFarm:
             pass
 
 
-from . import cameras, lightmap, probes, scenes  # noqa: E402,F401
+from . import baked, cameras, lightmap, probes, scenes  # noqa: E402,F401
