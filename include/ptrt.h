@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms, + ptrt_query_radiance / ptrt_camera_rays / ptrt_init_rng_states, + ptrt_query_probes, + ptrt_lds_layout (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
+#define PTRT_ABI_VERSION 6 /* 6: + ptrt_launch_ms_history, + ptrt_set_instance_transforms / ptrt_refit_tlas / ptrt_read_tlas, + ptrt_reorder_tlas / ptrt_read_tlas_order / ptrt_set_instance_transforms_device, + ptrt_set_instance_poses_device / ptrt_read_instance_transforms, + ptrt_query_radiance / ptrt_camera_rays / ptrt_init_rng_states, + ptrt_query_probes, + ptrt_lds_layout, + ptrt_read_bvh (additions only); 2: ptrt_scene_desc gained env_rgba / env_width / env_height; 3: + ptrt_post_frame, ptrt_update_instances; 4: + ptrt_ring_*, ptrt_farm_* (additions only); 5: ptrt_stats gained shadow_rays_walked (the struct grew: rebuild callers of ptrt_get_stats) */
 
 enum {
     PTRT_OK = 0,
@@ -370,9 +370,16 @@ int ptrt_refit(ptrt_ctx *ctx);
  * Behind a TLAS with inner nodes the mesh's new root box reaches the TLAS with ptrt_refit_tlas() (or a host rebuild
  * handed to ptrt_update_instances), as after ptrt_refit; the build itself never depended on the TLAS' shape.
  * ptrt_read_prim_order returns the resulting `primIndices` (mesh.cuh:57) so a
- * host copy of the tree (and the oracle) can follow. */
+ * host copy of the tree (and the oracle) can follow.
+ *
+ * ptrt_read_bvh: synchronises; mesh `mesh_index`'s uploaded nodes (pre-order; left / right / start / count as uploaded) with
+ * the boxes the DEVICE holds now, after any ptrt_refit / ptrt_build_bvh -- the counterpart of ptrt_read_tlas for one
+ * bottom-level tree, so a test can hold every box to the triangles below it.  A node the upload's walk from node 0 did not
+ * reach keeps its uploaded box; an absent child has no node and no box to return.  PTRT_E_INVALID for a mesh index outside the
+ * upload or unless node_count is the mesh's uploaded node count.  ABI 6, additions only. */
 int ptrt_build_bvh(ptrt_ctx *ctx, int mesh_index);
 int ptrt_read_prim_order(ptrt_ctx *ctx, int mesh_index, int32_t *prim_indices_out, int count);
+int ptrt_read_bvh(ptrt_ctx *ctx, int mesh_index, ptrt_bvh_node *nodes_out, int node_count);
 
 /* Moving instances and meshes behind ANY TLAS without a host round trip (not in the reference, which rebuilds the TLAS on
  * the CPU: scene.cuh:458-594).  The TLAS topology that was uploaded -- child pairs, leaf ranges, mesh indices -- is kept;

@@ -654,6 +654,8 @@ struct FlatScene {
     std::vector<int4> face_src;
     std::vector<int> slot_pos, face_base, face_count, slot_base, slot_count;
     std::vector<unsigned char> rebuildable, is_soup;
+    // read-back bookkeeping (ptrt_read_bvh): per mesh, where the device keeps the box of each input node
+    std::vector<std::vector<int>> in_dst;
 };
 
 // Validates mesh `m` and appends it to `S`: vertices, faces, the BVH as child-pair nodes with its leaves' triangle packets,
@@ -713,7 +715,9 @@ int flatten_mesh(ptrt_ctx *c, int m, const ptrt_mesh_desc &M, FlatScene &S) {
     };
     int depth = 0;
     std::string why;
-    const int root = convert_tree(M.nodes, M.node_count, S.R.nodes, emit_leaf, depth, why, -(m + 1), &S.node_dst, &S.node_depth);
+    S.in_dst.emplace_back((size_t)M.node_count, INT32_MIN);
+    const int root = convert_tree(M.nodes, M.node_count, S.R.nodes, emit_leaf, depth, why, -(m + 1), &S.node_dst, &S.node_depth,
+                                  &S.in_dst.back());
     if (root == INT32_MIN || bad)
         return fail(c, PTRT_E_INVALID, "mesh %d: malformed BVH (%s)", m, bad ? "leaf range out of bounds" : why.c_str());
     if (depth > 23)
@@ -833,6 +837,10 @@ int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *meshes, int mesh_cou
     c->mesh_is_soup = S.is_soup;
     c->mesh_vert_base = S.vert_base;
     c->mesh_vert_count = S.vert_count;
+    c->h_mesh_in.resize((size_t)mesh_count);
+    for (int m = 0; m < mesh_count; ++m)
+        c->h_mesh_in[(size_t)m].assign(meshes[m].nodes, meshes[m].nodes + meshes[m].node_count);
+    c->h_mesh_in_dst = std::move(S.in_dst);
     c->n_slots = (int)S.slot_face.size();
     c->n_leaves = (int)R.leaves.size();
     c->n_nodes = (int)(R.nodes.size() / 4);
@@ -1312,6 +1320,39 @@ int ptrt_read_prim_order(ptrt_ctx *c, int mesh, int32_t *out, int count) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < count; ++i)
         out[pos[(size_t)i]] = sf[(size_t)i].w;
+    return PTRT_OK;
+}
+
+// The counterpart of ptrt_read_tlas for one mesh's BVH: the uploaded nodes with the boxes the device holds now.  A node's box
+// is the child-pair slot of its parent in d_nodes (dst >= 0), the root's the mesh's root box in d_mesh_recs (dst < 0); a node
+// convert_tree did not reach (INT32_MIN) keeps its uploaded box.  The canonical nodes only: d_nodes2 is derived from them.
+int ptrt_read_bvh(ptrt_ctx *c, int mesh, ptrt_bvh_node *nodes_out, int node_count) {
+    if (int rc = enter_geometry(c, "ptrt_read_bvh", nodes_out != nullptr))
+        return rc;
+    if (mesh < 0 || mesh >= c->n_meshes || node_count != (int)c->h_mesh_in[(size_t)mesh].size())
+        return fail(c, PTRT_E_INVALID, "ptrt_read_bvh: mesh %d was uploaded with %d nodes, asked for %d", mesh,
+                    (mesh >= 0 && mesh < c->n_meshes) ? (int)c->h_mesh_in[(size_t)mesh].size() : 0, node_count);
+    if (int rc = set_device(c))
+        return rc;
+    std::vector<float4> nodes((size_t)c->n_nodes * 4), rec(2);
+    if (!nodes.empty())
+        HIP_TRY(c, hipMemcpyAsync(nodes.data(), c->d_nodes, nodes.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rec.data(), c->d_mesh_recs + (size_t)mesh * pt::MESH_REC_F4, 2 * sizeof(float4), hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < node_count; ++i) {
+        ptrt_bvh_node N = c->h_mesh_in[(size_t)mesh][(size_t)i];
+        const int dst = c->h_mesh_in_dst[(size_t)mesh][(size_t)i];
+        if (dst >= 0) {
+            const float *n = reinterpret_cast<const float *>(&nodes[(size_t)(dst >> 1) * 4]) + ((dst & 1) ? 6 : 0);
+            N.bmin = ptrt_vec3{n[0], n[1], n[2]};
+            N.bmax = ptrt_vec3{n[3], n[4], n[5]};
+        } else if (dst != INT32_MIN) {
+            N.bmin = ptrt_vec3{rec[0].x, rec[0].y, rec[0].z};
+            N.bmax = ptrt_vec3{rec[1].x, rec[1].y, rec[1].z};
+        }
+        nodes_out[i] = N;
+    }
     return PTRT_OK;
 }
 

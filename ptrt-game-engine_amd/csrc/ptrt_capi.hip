@@ -130,6 +130,8 @@ struct ptrt_ctx {
     int *d_level_nodes = nullptr;   // inner nodes ordered by depth
     std::vector<int> level_offset;  // level_offset[d] .. level_offset[d+1]: nodes at depth d+1
     std::vector<int> mesh_vert_base, mesh_vert_count;
+    std::vector<std::vector<ptrt_bvh_node>> h_mesh_in; // per mesh the BVH as it was uploaded ... (ptrt_read_bvh; no render path reads these)
+    std::vector<std::vector<int>> h_mesh_in_dst;       // ... and where the device keeps each of its nodes' boxes (INT32_MIN: nowhere)
     int n_slots = 0, n_leaves = 0;
     // GPU rebuild support (ptrt_build_bvh, pt_build.hip.h)
     int4 *d_face_src = nullptr;   // per face, mesh-major, original order: global vertex indices + face index

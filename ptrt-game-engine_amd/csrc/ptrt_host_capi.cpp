@@ -204,6 +204,17 @@ int hs_mesh_set_vertices(void *s, int mesh, const float *xyz, int n_verts) {
     m->vertsDirty = true;
     return 0;
 }
+// Mesh::refitBVH alone, for a Scene without a back end (tests/test_bvh_statement.py): the mesh keeps its tree and leaf
+// assignment, every box is recomputed from the current vertices.  The TLAS is not touched.
+int hs_mesh_refit_bvh(void *s, int mesh) {
+    Mesh *m = static_cast<Scene *>(s)->getMesh((size_t)mesh);
+    if (!m || m->bvhNodes.empty()) {
+        g_err = "hs_mesh_refit_bvh: no such mesh, or no tree built yet";
+        return -1;
+    }
+    m->refitBVH();
+    return 0;
+}
 // What updatePTScene does to a `Triangles` mesh whose triangleVerts changed (PTRTtransfer.cuh:2249-2270): vertices and faces
 // rewritten as an unshared-vertex soup, both dirty flags set, the local box recomputed -- the caller commits afterwards.
 static double g_soup_us = 0.0; // host time of hs_mesh_set_triangle_soup so far: the CALLER's share of a commit (bench.py --via-commit)

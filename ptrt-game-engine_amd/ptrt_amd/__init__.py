@@ -310,6 +310,7 @@ _sig("hs_add_mesh_obj", C.c_int, _vp, C.c_char_p, _fp)
 _sig("hs_add_checkerboard", C.c_int, _vp, C.c_float, C.c_int, C.c_float, _fp, _fp)
 _sig("hs_mesh_op", C.c_int, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float)
 _sig("hs_mesh_set_vertices", C.c_int, _vp, C.c_int, _fp, C.c_int)
+_sig("hs_mesh_refit_bvh", C.c_int, _vp, C.c_int)
 _sig("hs_mesh_set_triangle_soup", C.c_int, _vp, C.c_int, _fp, C.c_int)
 _sig("hs_set_dynamic_geometry_policy", C.c_int, _vp, C.c_int)
 _sig("hs_commit_counts", C.c_int, _vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
@@ -360,6 +361,7 @@ _sig("ptrt_update_vertices", C.c_int, _vp, C.c_int, _fp, C.c_int, C.c_int)
 _sig("ptrt_refit", C.c_int, _vp)
 _sig("ptrt_build_bvh", C.c_int, _vp, C.c_int)
 _sig("ptrt_read_prim_order", C.c_int, _vp, C.c_int, C.POINTER(C.c_int), C.c_int)
+_sig("ptrt_read_bvh", C.c_int, _vp, C.c_int, C.POINTER(BvhNode), C.c_int)
 _sig("ptrt_update_triangles", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int)
 _sig("ptrt_set_instance_transforms", C.c_int, _vp, C.c_int, C.c_int, C.POINTER(InstanceXform))
 _sig("ptrt_set_instance_transforms_device", C.c_int, _vp, C.c_int, C.c_int, _vp)
@@ -658,6 +660,11 @@ class Scene:
         a = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
         self._chk(lib.hs_mesh_set_vertices(self._h, mesh, _fptr(a), a.shape[0]))
 
+    def refitMeshOnHost(self, mesh):
+        """Mesh::refitBVH alone: the host copy of the mesh keeps its tree and leaf assignment and takes its boxes from the
+        current vertices (after setVertices).  No back end needed; the TLAS is not touched."""
+        self._chk(lib.hs_mesh_refit_bvh(self._h, int(mesh)))
+
     def setTriangleSoup(self, mesh, tris):
         """What the reference's updatePTScene does to a `Triangles` mesh (PTRTtransfer.cuh:2249-2270): vertices and faces
         rewritten, bvhDirty / vertsDirty set, local box recomputed; the caller then commits (commitObjectChanges)."""
@@ -842,6 +849,17 @@ class Scene:
         n = self.flatten().contents.tlas_node_count
         out = np.zeros(n, dtype=TLAS_NODE_DTYPE)
         self._cchk(lib.ptrt_read_tlas(self.ctx, out.ctypes.data_as(C.POINTER(BvhNode)), n))
+        return out
+
+    def read_bvh(self, mesh):
+        """Mesh `mesh`'s BVH as the device holds it (ptrt_read_bvh; synchronises): the uploaded nodes, pre-order, with the boxes
+        of the last refit / rebuild -- the structured array read_tlas returns."""
+        d = self.flatten().contents
+        if not 0 <= int(mesh) < d.mesh_count:
+            raise PtrtError(f"read_bvh: no mesh {mesh}")
+        n = d.meshes[int(mesh)].node_count
+        out = np.zeros(n, dtype=TLAS_NODE_DTYPE)
+        self._cchk(lib.ptrt_read_bvh(self.ctx, int(mesh), out.ctypes.data_as(C.POINTER(BvhNode)), n))
         return out
 
     def refitFromDevice(self, mesh, device_ptr):

@@ -8,6 +8,7 @@
 //
 // Read-backs are a fixed function of what was handed over, so a trace is reproducible:
 //   ptrt_read_prim_order(mesh)  the prim order uploaded for that mesh, reversed once per ptrt_build_bvh(mesh) since;
+//   ptrt_read_bvh(mesh)         the nodes uploaded for that mesh (no refit is modelled);
 //   ptrt_read_tlas              the TLAS nodes last handed over (ptrt_upload_geometry / ptrt_update_instances);
 //   ptrt_read_tlas_order        the TLAS mesh indices last handed over, reversed once per ptrt_reorder_tlas since.
 // `fake_backend_quiet(true)` switches log and digests off (timing runs).
@@ -21,6 +22,7 @@
 
 struct ptrt_ctx {
     std::vector<std::vector<int32_t>> primOrder;
+    std::vector<std::vector<ptrt_bvh_node>> meshNodes;
     std::vector<ptrt_bvh_node> tlasNodes;
     std::vector<int32_t> tlasOrder;
 };
@@ -110,8 +112,11 @@ int ptrt_reset_rng(ptrt_ctx *, unsigned long long seed) { return Line("ptrt_rese
 int ptrt_upload_geometry(ptrt_ctx *c, const ptrt_mesh_desc *m, int n, const ptrt_bvh_node *tn, int tnn, const int32_t *ti, int tin) {
     Line l("ptrt_upload_geometry");
     c->primOrder.resize((size_t)n);
-    for (int k = 0; k < n; ++k)
+    c->meshNodes.resize((size_t)n);
+    for (int k = 0; k < n; ++k) {
         c->primOrder[(size_t)k].assign(m[k].prim_indices, m[k].prim_indices + m[k].prim_count);
+        c->meshNodes[(size_t)k].assign(m[k].nodes, m[k].nodes + m[k].node_count);
+    }
     return tlas(meshes(l, m, n), c, tn, tnn, ti, tin).done();
 }
 int ptrt_update_instances(ptrt_ctx *c, const ptrt_mesh_desc *m, int n, const ptrt_bvh_node *tn, int tnn, const int32_t *ti, int tin) {
@@ -167,6 +172,12 @@ int ptrt_read_prim_order(ptrt_ctx *c, int mesh, int32_t *out, int count) {
     for (int k = 0; k < count; ++k) // (every slot of the caller's array is written: a short array is an overflow a sanitizer sees)
         out[k] = known && (size_t)k < c->primOrder[(size_t)mesh].size() ? c->primOrder[(size_t)mesh][(size_t)k] : 0;
     return l.done();
+}
+int ptrt_read_bvh(ptrt_ctx *c, int mesh, ptrt_bvh_node *out, int n) {
+    const bool known = mesh >= 0 && (size_t)mesh < c->meshNodes.size();
+    for (int k = 0; k < n; ++k)
+        out[k] = known && (size_t)k < c->meshNodes[(size_t)mesh].size() ? c->meshNodes[(size_t)mesh][(size_t)k] : ptrt_bvh_node{};
+    return Line("ptrt_read_bvh").i("mesh", mesh).i("count", n).i("held", known ? (long long)c->meshNodes[(size_t)mesh].size() : -1).done();
 }
 int ptrt_set_instance_transforms(ptrt_ctx *, int first, int count, const ptrt_instance_xform *x) {
     return Line("ptrt_set_instance_transforms").i("first", first).a("xf", x, (size_t)count, sizeof *x).done();

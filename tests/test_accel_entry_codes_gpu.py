@@ -64,6 +64,7 @@ def calls(P, d, dev_xf, mesh=0, null=False):
     verts = np.ctypeslib.as_array(C.cast(M.verts, C.POINTER(C.c_float)), (M.vert_count * 3,)).copy()  # (as uploaded: nothing moves)
     order = (C.c_int * max(M.face_count, 1))()
     nodes = (P.BvhNode * d.tlas_node_count)()
+    bnodes = (P.BvhNode * max(M.node_count, 1))()
     ids = (C.c_int32 * d.tlas_index_count)()
     counts = (C.c_int * 2)()
     fp = C.POINTER(C.c_float)
@@ -84,9 +85,10 @@ def calls(P, d, dev_xf, mesh=0, null=False):
         "ptrt_build_bvh": None if null else lambda c: lib.ptrt_build_bvh(c, mesh),
         "ptrt_update_triangles": lambda c: lib.ptrt_update_triangles(c, mesh, None if null else verts.ctypes.data, 1, 0),
         "ptrt_read_prim_order": lambda c: lib.ptrt_read_prim_order(c, mesh, None if null else order, M.face_count),
+        "ptrt_read_bvh": lambda c: lib.ptrt_read_bvh(c, mesh, None if null else bnodes, M.node_count),
     }
     t = {k: v for k, v in t.items() if v is not None}
-    t["_keep"] = lambda c, keep=(xf, verts, order, nodes, ids, counts): OK  # (the thunks borrow these)
+    t["_keep"] = lambda c, keep=(xf, verts, order, nodes, bnodes, ids, counts): OK  # (the thunks borrow these)
     return t
 
 
@@ -99,12 +101,13 @@ def run(table, ctx, only=None):
 
 MOVED = ["ptrt_update_instances", "ptrt_set_instance_transforms", "ptrt_set_instance_transforms_device", "ptrt_refit_tlas",
          "ptrt_reorder_tlas", "ptrt_read_tlas_order", "ptrt_read_tlas", "ptrt_debug_upload_counts", "ptrt_update_vertices",
-         "ptrt_refit", "ptrt_build_bvh", "ptrt_update_triangles", "ptrt_read_prim_order"]
+         "ptrt_refit", "ptrt_build_bvh", "ptrt_update_triangles", "ptrt_read_prim_order", "ptrt_read_bvh"]
 WITH_ARRAY = ["ptrt_upload_geometry", "ptrt_upload_geometry:tlas_nodes", "ptrt_upload_geometry:tlas_mesh_indices",
               "ptrt_update_instances", "ptrt_set_instance_transforms", "ptrt_set_instance_transforms_device", "ptrt_read_tlas_order",
-              "ptrt_read_tlas", "ptrt_debug_upload_counts", "ptrt_update_vertices", "ptrt_update_triangles", "ptrt_read_prim_order"]
+              "ptrt_read_tlas", "ptrt_debug_upload_counts", "ptrt_update_vertices", "ptrt_update_triangles", "ptrt_read_prim_order",
+              "ptrt_read_bvh"]
 WITH_MESH = ["ptrt_set_instance_transforms", "ptrt_set_instance_transforms_device", "ptrt_update_vertices", "ptrt_build_bvh",
-             "ptrt_update_triangles", "ptrt_read_prim_order"]
+             "ptrt_update_triangles", "ptrt_read_prim_order", "ptrt_read_bvh"]
 
 
 @pytest.fixture(scope="module")
@@ -180,6 +183,8 @@ def test_after_an_upload(P, desc, dev_xf):
         assert lib.ptrt_update_instances(ctx, d.meshes, n - 1, d.tlas_nodes, d.tlas_node_count, d.tlas_mesh_indices, d.tlas_index_count) == INVALID
         assert lib.ptrt_read_tlas_order(ctx, (C.c_int32 * (d.tlas_index_count + 1))(), d.tlas_index_count + 1) == INVALID
         assert lib.ptrt_read_tlas(ctx, (P.BvhNode * (d.tlas_node_count + 1))(), d.tlas_node_count + 1) == INVALID
+        assert lib.ptrt_read_bvh(ctx, 0, (P.BvhNode * (d.meshes[0].node_count + 1))(), d.meshes[0].node_count + 1) == INVALID
+        assert b"ptrt_read_bvh" in lib.ptrt_last_error(ctx)
         assert lib.ptrt_update_vertices(ctx, 0, np.zeros(3, np.float32).ctypes.data_as(C.POINTER(C.c_float)), d.meshes[0].vert_count + 1, 0) == INVALID
         assert lib.ptrt_set_instance_transforms(ctx, 0, n + 1, (P.InstanceXform * 1)()) == INVALID
         assert lib.ptrt_set_instance_transforms(ctx, n, 0, (P.InstanceXform * 1)()) == OK       # an empty range at the end is in order
@@ -189,9 +194,9 @@ def test_after_an_upload(P, desc, dev_xf):
         assert lib.ptrt_debug_upload_counts(ctx, out) == OK and tuple(out) == (1, 0)
         good = run(calls(P, d, dev_xf), ctx)
         assert {k: good[k] for k in ("ptrt_refit", "ptrt_refit_tlas", "ptrt_reorder_tlas", "ptrt_read_tlas", "ptrt_read_tlas_order",
-                                     "ptrt_update_instances", "ptrt_set_instance_transforms", "ptrt_update_vertices")} == \
+                                     "ptrt_update_instances", "ptrt_set_instance_transforms", "ptrt_update_vertices", "ptrt_read_bvh")} == \
                {k: OK for k in ("ptrt_refit", "ptrt_refit_tlas", "ptrt_reorder_tlas", "ptrt_read_tlas", "ptrt_read_tlas_order",
-                                "ptrt_update_instances", "ptrt_set_instance_transforms", "ptrt_update_vertices")}
+                                "ptrt_update_instances", "ptrt_set_instance_transforms", "ptrt_update_vertices", "ptrt_read_bvh")}
         assert lib.ptrt_sync(ctx) == OK
     finally:
         lib.ptrt_destroy(ctx)
